@@ -15,7 +15,9 @@ In the same run (rank 0, N=1): the unmodified reference miniasm on the SAME file
 ours: gfa_identical), the CLI end to end (process start -> GFA on disk), the text-resident variant (device-side parse inside
 the step), BASELINE configs[1] (10M overlaps) and a tie-rich input as secondary legs.
 
-One JSON line on stdout (rank 0).
+One JSON line on stdout (rank 0): the figures without their prose and without the secondary legs' tables (compact_line); the full
+record goes to <workdir>/bench_<workload>_full.json, named in the line's `full_record`.  --dump-outputs DIR writes the GFA of the last
+timed step as .npy arrays (dump_outputs), so that two builds can be compared output for output on the same seeded input.
 """
 import argparse
 import ctypes as C
@@ -269,6 +271,53 @@ REDUCE_GROUP = ("k_arc_groups", "k_arc_group_sort", "k_arc_radix_hist", "k_arc_r
 REDUCE_DESIGN_ONLY = ("k_arc_groups", "k_arc_radix_hist", "k_arc_radix_scatter", "k_arc_permute", "k_arc_tie_census")  # their bytes are this design's, not 8(d) rows
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # --dump-outputs: bytes of all .npy files together
+
+
+def dump_outputs(dirname, gfa, budget=DUMP_BUDGET):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the GFA text -- as arrays two builds can be
+    compared on.  gfa_text.npy: the bytes of the text (float32, one per byte); gfa_lines.npy: which lines of the text those bytes are
+    (float64, in output order).  A text too large for the budget is stood for by a fixed, seeded sample of whole lines."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    lines = gfa.split(b"\n")
+    if lines and lines[-1] == b"":
+        lines.pop()
+    room = budget - 2 * 128  # (an .npy header is 128 bytes)
+    if 4 * len(gfa) + 8 * len(lines) <= room:
+        keep = np.arange(len(lines))
+        text = gfa
+    else:
+        order = np.random.default_rng(0).permutation(len(lines))
+        cost = np.cumsum(np.array([4 * (len(lines[i]) + 1) + 8 for i in order], dtype=np.int64))
+        keep = np.sort(order[:int(np.searchsorted(cost, room, side="right"))])
+        text = b"".join(lines[i] + b"\n" for i in keep)
+    np.save(os.path.join(dirname, "gfa_text.npy"), np.frombuffer(text, dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(dirname, "gfa_lines.npy"), keep.astype(np.float64))
+    return len(keep), len(lines)
+
+
+# keys whose values are prose (what a figure means, where it came from): they stay in the full record, not on the result line
+PROSE_KEYS = ("what", "note", "traffic_source", "reference", "sample", "alg_GBs_is_accounting", "source", "input", "rank0_tail_where")
+LEG_DETAIL_KEYS = ("kernels", "reduce_group", "phases", "laps", "pafgen")  # a leg's tables: in the full record (reduce_group also under roofline)
+
+
+def compact_line(out):
+    """the result line: `out` without its prose and without the secondary legs' tables (the full record is written to a file beside it)"""
+    def strip(x):
+        if isinstance(x, dict):
+            return {k: strip(v) for k, v in x.items() if k not in PROSE_KEYS}
+        if isinstance(x, list):
+            return [strip(v) for v in x]
+        return x
+    line = strip(out)
+    for leg in (line.get("legs") or {}).values():
+        if isinstance(leg, dict):
+            for k in LEG_DETAIL_KEYS:
+                leg.pop(k, None)
+    return line
+
+
 def kernel_table(recs, prof_steps, design_only=DESIGN_ONLY + ("k_arc_groups", "k_arc_radix_hist", "k_arc_radix_scatter", "k_arc_tie_census")):
     """per timed scope: launches per step, HIP-event time per launch, share, algorithmic GB/s"""
     tot_ms = sum(r["total_ms"] for r in recs) or 1.0
@@ -375,7 +424,10 @@ def main():
     ap.add_argument("--legs", default="cfg2,tie_rich,graph_heavy,latency,e2e,cfg5,realistic", help="which secondary legs to run (comma list)")
     ap.add_argument("--graph-heavy-lines", type=int, default=100000000, help="overlaps of the graph-heavy leg (pafgen -L fixed, 50 lines per read); 0 = skip it")
     ap.add_argument("--inflight", type=int, default=1, help="experiment: batches in flight on the one GPU (each on its own context and host thread)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the GFA of the last timed step to DIR as .npy arrays (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     args.tail_ctx = not args.no_tail_ctx
     want_leg = lambda name: not args.no_legs and name in args.legs.split(",")
     args.gen_extra = ([] if args.model == "lognormal" else ["-L", args.model]) + (["-q", str(args.grid), "-d", "0.3", "-x", "0.03"] if args.grid else [])
@@ -697,6 +749,9 @@ def main():
     total_lines = float(W.n_lines)
     main_phases = run.phases() if (rank == 0 and world == 1) else None
     gfa = run.output() if rank == 0 else b""
+    if rank == 0 and args.dump_outputs:
+        n_kept, n_lines = dump_outputs(args.dump_outputs, gfa)
+        log("dumped %d of %d GFA lines of the last timed step to %s" % (n_kept, n_lines, args.dump_outputs))
     tie = ctx.tie_stats() if rank == 0 else None
 
     # ---- per-kernel timing with HIP events on the launch stream (separate, instrumented steps)
@@ -996,7 +1051,12 @@ def main():
             "legs_wall_s": {k: round(v["wall_s"], 3) for k, v in legs.items() if isinstance(v, dict) and "wall_s" in v},
             "legs_identical": {k: v.get("gfa_identical", v.get("gfa_md5_matches_reference", v.get("gfa_md5_matches_recorded_reference"))) for k, v in legs.items() if isinstance(v, dict)},
         }
-        print(json.dumps(out), flush=True)
+        full = os.path.join(args.workdir, "bench_%s_full.json" % cfg_name)
+        with open(full, "w") as f:
+            json.dump(out, f)
+        line = compact_line(out)
+        line["full_record"] = full
+        print(json.dumps(line), flush=True)
     W.close(L)
     ctx.close()
     if world > 1:

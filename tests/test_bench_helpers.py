@@ -37,3 +37,39 @@ def test_pmc_traffic_scopes_sum_their_kernels():
     assert b.pmc_profile("no_such_workload") == (None, None)             # counters belong to the profiled workload only
     names4, src4 = b.pmc_profile("cfg4")
     assert "commit" in src4 and b.pmc_traffic(names4, "k_hit_sub<gather>") > 1e10
+
+
+def test_result_line_stays_short():
+    """the round-6 record (22 KB on one line) was not read back where round 5's 15 KB line was: the result line keeps the figures and
+    drops the prose and the legs' tables, which stay in the full record"""
+    b = _bench()
+    full = json.load(open(os.path.join(ROOT, "profiles", "r06_bench_cfg4.json")))
+    line = b.compact_line(full)
+    assert len(json.dumps(line)) < 12000
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "gfa_identical", "parity", "summary", "config"):
+        assert line[k] == full[k], k
+    assert line["roofline"]["sort_group"] == full["roofline"]["sort_group"]
+    assert line["kernels"] == [{k: v for k, v in row.items() if k not in b.PROSE_KEYS} for row in full["kernels"]]
+    assert all(leg["ms_per_step"] == full["legs"][n]["ms_per_step"] for n, leg in line["legs"].items() if "ms_per_step" in leg)
+    assert "note" in full["roofline"] and "note" not in line["roofline"] and "kernels" not in line["legs"]["graph_heavy"]
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs: the GFA text whole when it fits the budget, else a seeded sample of whole lines; the same text gives the same files"""
+    import numpy as np
+    b = _bench()
+    gfa = b"".join(b"S\tutg%06dl\t*\tLN:i:%d\n" % (i, 1000 + 37 * i) for i in range(2000))
+    assert b.dump_outputs(str(tmp_path / "all"), gfa) == (2000, 2000)
+    text = np.load(tmp_path / "all" / "gfa_text.npy")
+    assert text.dtype == np.float32 and bytes(text.astype(np.uint8)) == gfa
+    assert np.array_equal(np.load(tmp_path / "all" / "gfa_lines.npy"), np.arange(2000, dtype=np.float64))
+    budget = 40000
+    for d in ("s1", "s2"):
+        kept, total = b.dump_outputs(str(tmp_path / d), gfa, budget=budget)
+        assert 0 < kept < total == 2000
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget
+    for f in ("gfa_text.npy", "gfa_lines.npy"):
+        assert np.array_equal(np.load(tmp_path / "s1" / f), np.load(tmp_path / "s2" / f))
+    idx = np.load(tmp_path / "s1" / "gfa_lines.npy").astype(np.int64)
+    lines = gfa.split(b"\n")
+    assert np.all(np.diff(idx) > 0) and bytes(np.load(tmp_path / "s1" / "gfa_text.npy").astype(np.uint8)) == b"".join(lines[i] + b"\n" for i in idx)

@@ -119,7 +119,8 @@ def test_bench_py_runs_on_the_cpu_build(mode, emu_built, tmp_path):
     env["PYTHONPATH"] = os.path.join(EMU, "fake_torch") + os.pathsep + env.get("PYTHONPATH", "")
     env["MINIASM_AMD_LIB"] = os.path.join(EMU, "_build", "libminiasm_amd_emu.so")
     env["MA_BENCH_DIR"] = str(tmp_path)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "3", "--warmup", "1", "--no-legs"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "3", "--warmup", "1", "--no-legs",
+           "--dump-outputs", str(tmp_path / "dump")]
     if mode == "no_tail_ctx":
         cmd.append("--no-tail-ctx")
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1800)
@@ -136,6 +137,11 @@ def test_bench_py_runs_on_the_cpu_build(mode, emu_built, tmp_path):
     assert ("second context" in d["config"]["pipelining"]) == (mode == "default")
     assert d["roofline"]["sort_group"]["alg_bytes_per_step"] == 112.0 * d["config"]["per_gpu_hits"] and "k_hit_sub<gather>" in d["roofline"]["sort_group"]["kernels"]
     assert all(k["alg_GBs"] is None for k in d["kernels"] if k["name"] in ("k_hit_keys", "k_radix_scatter", "k_radix_hist", "k_hit_goff"))
+    import hashlib
+    import numpy as np
+    dumped = bytes(np.load(tmp_path / "dump" / "gfa_text.npy").astype(np.uint8))  # --dump-outputs: the GFA of the last timed step, whole at this size
+    assert hashlib.md5(dumped).hexdigest() == d["parity"]["gfa_md5"]
+    assert json.load(open(d["full_record"]))["value"] == d["value"]
 
 
 @pytest.mark.parametrize("grid", [0, 16])
