@@ -396,7 +396,7 @@ static int clean_sweep(mahip_ctx *c, int mode, int param, uint32_t *cnt, uint32_
 static void clean_timing(const char *what, int n_iter, uint32_t cnt, int tier = -1)
 {
 	static int on = -1;
-	if (on < 0) on = getenv("MA_PIPE_TIMING") && atoi(getenv("MA_PIPE_TIMING")) >= 2;
+	if (on < 0) on = ma_timing_level() >= 2;
 	if (!on) return;
 	if (tier < 0) fprintf(stderr, "[T::clean] %-14s %2d iterations, %u actions\n", what, n_iter, cnt);
 	else fprintf(stderr, "[T::clean] %-14s %2d iterations, %u actions; biggest probe table used so far: %u slots (tier %d)\n", what, n_iter, cnt, bub_cap(tier), tier);

@@ -10,7 +10,7 @@
 
 #define DG_BINS 128
 
-// one 16-byte load per thread, one block per 4 KB (the shape of k_paf_nl_count)
+// one 16-byte load per thread, one block per 4 KB (the shape of round 5's newline count)
 __global__ __launch_bounds__(256) void k_diag_read16_flat(const uint4 *__restrict__ src, size_t n16, uint32_t *__restrict__ out)
 {
 	const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -564,9 +564,6 @@ __global__ __launch_bounds__(256) void k_arc_group_sort(ArcCols in, ArcCols out,
 }
 
 // ------------------------------------------------------------------------------------------------ asg_arc_del_trans
-#ifndef TR_PRE
-#define TR_PRE 128u // neighbours whose CSR words are fetched with the vertex's own list (SMALL); the rest wait until they are expanded.  128 = all of them
-#endif
 #define TR_CAP 512
 #define TR_HASH 1024
 #define TR_EMPTY 0xffffffffu
@@ -583,80 +580,43 @@ __device__ __forceinline__ int tr_find(const uint32_t *hk, uint32_t x, uint32_t 
 	}
 }
 
-// One wave per vertex.  Two instantiations split the vertices by out-degree so that the common case (<= 128 arcs)
-// runs with a small LDS footprint at full occupancy: SMALL handles 1..128 arcs and also prefetches the CSR entries of
-// all neighbours (one coalesced gather instead of one dependent load per expansion); !SMALL handles 129..TR_CAP arcs
-// and sends larger vertices to the block-per-vertex tier.
+// One wave per vertex, for the vertices with 129 .. TR_CAP arcs (the first tier, 1 .. 128 arcs, is k_asg_trans_pipe below); larger vertices go to the
+// block-per-vertex tier.
 //
 // The reference walks v's arcs in order and expands neighbour i only if mark[target_i] is still 1 (asg.c:168).  Marks
 // only ever go 1 -> 2, so "the next arc to expand" is simply the lowest not-yet-passed arc whose target is still
 // marked 1 NOW: each lane watches the mark of its own arc and a ballot finds that arc -- the serial walk shrinks from
 // one step per arc to one step per expansion (about one per vertex on clean data).
-struct TrPre { uint32_t v[2], l[2], o[2]; uint32_t dead; }; // a vertex's (up to 128) arcs -- target, length, overlap word -- and its read's seq.del, a vertex ahead
-
-template <int CAP, int HASH, bool SMALL>
+template <int CAP, int HASH>
 __global__ __launch_bounds__(256) void k_asg_trans(const uint32_t *__restrict__ av, const uint32_t *__restrict__ alen, uint32_t *__restrict__ aol,
                                                     const unsigned long long *__restrict__ idx, const uint8_t *__restrict__ sdel, uint32_t v_beg, uint32_t n_vtx,
                                                     uint32_t fuzz, uint32_t *__restrict__ ovf, unsigned long long *__restrict__ ctr)
 { // processes the vertices [v_beg, n_vtx): the whole graph on one GPU, a rank's own read range in the sharded mode
 	__shared__ uint32_t s_v[4][CAP], s_l[4][CAP], s_slot[4][CAP], s_hk[4][HASH], s_hm[4][HASH];
-	__shared__ uint32_t s_ws[4][SMALL ? CAP : 1], s_nw[4][SMALL ? CAP : 1];
 	const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	uint32_t *lv = s_v[wave], *ll = s_l[wave], *slot = s_slot[wave], *hk = s_hk[wave], *hm = s_hm[wave];
 	uint32_t n_red = 0, n_inner = 0; // n_inner: bodies of the loop at asg.c:169 this lane executed (SURVEY 8(d) prices the reduction at 16 (A + I) bytes)
 	// a wave takes 64 consecutive vertices at a time: one coalesced load of their CSR entries, then only the vertices that have arcs (of this
-	// instantiation's size class) are visited -- after containment most vertices have none, and a dependent load per vertex is pure latency.
-	// A vertex is a chain of dependent trips to memory (own list -> the neighbours' CSR words -> a neighbour's list -> the overlap words to flag): at 200 M
-	// arcs, where every vertex has work, the chain is what a launch costs (round 4, visit A: 3.8 ms, 0.21 of the roofline).  SMALL therefore fetches the NEXT
-	// vertex's rows (with the overlap words, so that a flag is a plain store) and its read's seq.del while the current vertex is reduced, and a neighbour's
-	// targets travel with its lengths: two trips per vertex are left.
+	// kernel's size class) are visited -- after containment most vertices have none, and a dependent load per vertex is pure latency.
 	for (uint64_t vb = (uint64_t)v_beg + (uint64_t)(blockIdx.x * 4 + wave) * 64; vb < n_vtx; vb += (uint64_t)gridDim.x * 256) {
 	const unsigned long long xl = vb + lane < n_vtx ? idx[vb + lane] : 0ull;
 	const uint32_t nvl = (uint32_t)xl;
-	unsigned long long todo = wv_ballot(nvl != 0 && !(SMALL ? nvl > (uint32_t)CAP : nvl <= 128u));
-	TrPre cur, nxt;
+	unsigned long long todo = wv_ballot(nvl > 128u);
 	int vbit = todo ? __ffsll((long long)todo) - 1 : -1;
-	auto preload = [&](int bit, TrPre &p) {
-		const unsigned long long x = __shfl(xl, bit, 64);
-		const uint32_t st = (uint32_t)(x >> 32), nv = (uint32_t)x;
-#pragma unroll
-		for (int r = 0; r < 2; ++r) {
-			const uint32_t i = (uint32_t)r * 64u + lane;
-			p.v[r] = p.l[r] = p.o[r] = 0;
-			if (i < nv) { p.v[r] = av[st + i]; p.l[r] = alen[st + i]; p.o[r] = aol[st + i]; }
-		}
-		p.dead = sdel[((uint32_t)vb + (uint32_t)bit) >> 1];
-	};
-	if (SMALL && vbit >= 0) preload(vbit, cur);
 	while (vbit >= 0) {
 		todo &= todo - 1;
 		const int vnext = todo ? __ffsll((long long)todo) - 1 : -1;
-		if (SMALL && vnext >= 0) preload(vnext, nxt);
 		const uint32_t v = (uint32_t)vb + (uint32_t)vbit;
 		const unsigned long long x = __shfl(xl, vbit, 64);
 		uint32_t st = (uint32_t)(x >> 32), nv = (uint32_t)x;
-		if (SMALL ? cur.dead != 0 : sdel[v >> 1] != 0) { // asg.c:158-161
-			if (SMALL) {
-#pragma unroll
-				for (int r = 0; r < 2; ++r) { const uint32_t i = (uint32_t)r * 64u + lane; if (i < nv) aol[st + i] = cur.o[r] | ADEL, ++n_red; }
-			} else for (uint32_t i = lane; i < nv; i += 64) aol[st + i] |= ADEL, ++n_red;
-			vbit = vnext; cur = nxt;
+		if (sdel[v >> 1] != 0) { // asg.c:158-161
+			for (uint32_t i = lane; i < nv; i += 64) aol[st + i] |= ADEL, ++n_red;
+			vbit = vnext;
 			continue;
 		}
-		if (nv > (uint32_t)CAP) { if (lane == 0) { unsigned long long k = atomicAdd(&ctr[CT_OVF2], 1ull); ovf[k] = v; } vbit = vnext; cur = nxt; continue; }
+		if (nv > (uint32_t)CAP) { if (lane == 0) { unsigned long long k = atomicAdd(&ctr[CT_OVF2], 1ull); ovf[k] = v; } vbit = vnext; continue; }
 		uint32_t hbits = 6; while ((1u << hbits) < 2 * nv) ++hbits;
 		uint32_t hsize = 1u << hbits, hmask = hsize - 1;
-		if (SMALL) {
-#pragma unroll
-			for (int r = 0; r < 2; ++r) {
-				const uint32_t i = (uint32_t)r * 64u + lane;
-				if (i < nv) {
-					const uint32_t w = cur.v[r];
-					lv[i] = w, ll[i] = cur.l[r];
-					if (i < TR_PRE) { unsigned long long xw = idx[w]; s_ws[wave][i] = (uint32_t)(xw >> 32); s_nw[wave][i] = (uint32_t)xw; }
-				}
-			}
-		} else
 		for (uint32_t i = lane; i < nv; i += 64) {
 			uint32_t w = av[st + i];
 			lv[i] = w, ll[i] = alen[st + i];
@@ -684,9 +644,8 @@ __global__ __launch_bounds__(256) void k_asg_trans(const uint32_t *__restrict__ 
 				const unsigned l0 = (unsigned)(__ffsll((long long)cand) - 1);
 				passed |= l0 == 63 ? ~0ull : ((2ull << l0) - 1ull);
 				const uint32_t i0 = base + l0, li = ll[i0];
-				uint32_t ws, nw;
-				if (SMALL && i0 < TR_PRE) ws = s_ws[wave][i0], nw = s_nw[wave][i0];
-				else { unsigned long long xw = idx[lv[i0]]; ws = (uint32_t)(xw >> 32); nw = (uint32_t)xw; }
+				const unsigned long long xw = idx[lv[i0]];
+				const uint32_t ws = (uint32_t)(xw >> 32), nw = (uint32_t)xw;
 				for (uint32_t j0 = 0; j0 < nw; j0 += 64) { // lanes over w's arcs; sorted by len => the loop of asg.c:169 is a prefix
 					uint32_t j = j0 + lane;
 					int ok = j < nw;
@@ -706,14 +665,10 @@ __global__ __launch_bounds__(256) void k_asg_trans(const uint32_t *__restrict__ 
 		}
 		// asg.c:181-184: the sweep resets mark[target] at the first arc to a target, so of several arcs to one
 		// reduced target (multi-arcs are still present here) only the first is deleted
-		if (SMALL) {
-#pragma unroll
-			for (int r = 0; r < 2; ++r) { const uint32_t i = (uint32_t)r * 64u + lane; if (i < nv && hm[slot[i]] == (i << 2 | 2u)) aol[st + i] = cur.o[r] | ADEL, ++n_red; }
-		} else
 		for (uint32_t i = lane; i < nv; i += 64)
 			if (hm[slot[i]] == (i << 2 | 2u)) aol[st + i] |= ADEL, ++n_red;
 		wv_sync();
-		vbit = vnext; cur = nxt;
+		vbit = vnext;
 	}
 	}
 	blk_add_u64(&ctr[CT_NRED], n_red);
@@ -1622,14 +1577,9 @@ extern "C" int mahip_asg_del_trans_range(mahip_ctx_t *c, int fuzz, uint32_t v_be
 	unsigned long long *ctr = P<unsigned long long>(c->ctr);
 	if (v_end > v_beg && c->n_arc) {
 		ProfScope ps(c, "k_asg_trans", 32.0 * (double)c->n_arc); // 16*(A+I)/A per arc, I ~ A on clean data
-		static const bool old_small = getenv("MA_TRANS_OLD") != nullptr; // A/B handle: round 4's first tier (rows a vertex ahead, every other trip paid per vertex)
-		if (old_small)
-		hipLaunchKernelGGL((k_asg_trans<128, 256, true>), dim3(grid_for(((size_t)(v_end - v_beg) + 63) / 64, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint32_t*)a.v, (const uint32_t*)a.len, a.ol,
-		                   (const unsigned long long*)P<unsigned long long>(c->idx), (const uint8_t*)P<uint8_t>(c->sdel), v_beg, v_end, (uint32_t)fuzz, P<uint32_t>(c->ovf), ctr);
-		else
 		hipLaunchKernelGGL(k_asg_trans_pipe, dim3(grid_for(((size_t)(v_end - v_beg) + 63) / 64, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint32_t*)a.v, (const uint32_t*)a.len, a.ol,
 		                   (const unsigned long long*)P<unsigned long long>(c->idx), (const uint8_t*)P<uint8_t>(c->sdel), v_beg, v_end, (uint32_t)fuzz, ctr);
-		hipLaunchKernelGGL((k_asg_trans<TR_CAP, TR_HASH, false>), dim3(grid_for(((size_t)(v_end - v_beg) + 63) / 64, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint32_t*)a.v, (const uint32_t*)a.len, a.ol,
+		hipLaunchKernelGGL((k_asg_trans<TR_CAP, TR_HASH>), dim3(grid_for(((size_t)(v_end - v_beg) + 63) / 64, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint32_t*)a.v, (const uint32_t*)a.len, a.ol,
 		                   (const unsigned long long*)P<unsigned long long>(c->idx), (const uint8_t*)P<uint8_t>(c->sdel), v_beg, v_end, (uint32_t)fuzz, P<uint32_t>(c->ovf), ctr);
 	}
 	CHK(ctr_fetch(c));

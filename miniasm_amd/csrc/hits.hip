@@ -342,33 +342,13 @@ __global__ __launch_bounds__(256) void k_hit_goff(const uint64_t *__restrict__ s
 // depth sweep runs as one prefix scan over lanes plus a short in-register walk; the first-longest run is a
 // wave max-reduce on (length, -position).  Reads with more than 512 hits go to tier B.
 // Tier B: one 256-thread block per read, events in LDS (<= 8192) or in global scratch (any size).
-// grid of the coverage kernels (blocks of 4 waves, one read per wave at a time); env MA_SUB_BLOCKS for experiments
-static unsigned sub_blocks() { static unsigned v = 0; if (!v) { const char *e = getenv("MA_SUB_BLOCKS"); v = e ? (unsigned)atoi(e) : 2 * MA_STREAM_BLOCKS; /* 2 x the resident capacity: the dispatcher evens out the tail (measured 2048: 0.51, 4096: 0.46, 8192: 0.45 ms; more blocks = more end-of-block atomics) */ if (v < 1) v = 1; } return v; }
-#ifndef MA_SUB_ORDER_DEFAULT
-#define MA_SUB_ORDER_DEFAULT "012"
-#endif
-#define MA_SUB_BLOCKS sub_blocks()
-// The three size classes of a coverage pass run side by side on three streams.  Which is QUEUED first matters: the first tier's blocks live for the whole launch (a wave walks
-// ~ 120 reads) and fill every slot they are given, so classes queued behind it start when its blocks retire -- a tail (rocprofv3: all three kernels span the same 5 ms although
-// the larger classes own a quarter of the hits).  MA_SUB_ORDER: "012" = first tier first (until round 5), "210" = the larger classes first.  MA_SUB_BIG_GRID: blocks of the two
-// larger classes (0: as many as the first tier's).
-struct SubOrder { int o[3]; };
-static const int *sub_order()
-{ // (a function-local static with an initialiser: built once, by one thread -- several host threads drive contexts of their own)
-	static const SubOrder so = [] {
-		SubOrder r;
-		const char *e = getenv("MA_SUB_ORDER");
-		const char *d = (e && strlen(e) == 3) ? e : MA_SUB_ORDER_DEFAULT;
-		int seen = 0;
-		for (int k = 0; k < 3; ++k) { r.o[k] = d[k] - '0'; if (r.o[k] < 0 || r.o[k] > 2) r.o[k] = k; seen |= 1 << r.o[k]; }
-		if (seen != 7) { r.o[0] = 0; r.o[1] = 1; r.o[2] = 2; }
-		return r;
-	}();
-	return so.o;
-}
-static unsigned sub_big_grid(unsigned g0) { static long v = -1; if (v < 0) { const char *e = getenv("MA_SUB_BIG_GRID"); v = e ? atol(e) : 0; } return v > 0 && (unsigned)v < g0 ? (unsigned)v : g0; }
+// grid of the coverage kernels (blocks of 4 waves, one read per wave at a time): 2 x the resident capacity, the dispatcher evens out the tail
+// (measured 2048: 0.51, 4096: 0.46, 8192: 0.45 ms; more blocks = more end-of-block atomics)
+#define SUB_BLOCKS (2u * MA_STREAM_BLOCKS)
+// The three size classes of a coverage pass run side by side on three streams, the first tier queued first, every class on the same grid (other orders and
+// smaller grids for the larger classes did no better: profiles/r05_experiments.txt, visit 18).
 // reads per bounds fetch in the larger tiers: up to SUB_CHUNK, fewer when there are not enough reads to give every wave of the grid a chunk
-static uint32_t sub_chunk(uint32_t R) { uint64_t waves = 4ull * grid_for(R, 4, MA_SUB_BLOCKS), k = waves ? R / waves : 1; return (uint32_t)(k < 1 ? 1 : k > 16 ? 16 : k); }
+static uint32_t sub_chunk(uint32_t R) { uint64_t waves = 4ull * grid_for(R, 4, SUB_BLOCKS), k = waves ? R / waves : 1; return (uint32_t)(k < 1 ? 1 : k > 16 ? 16 : k); }
 #define EV_PAD 0xffffffffu
 #define SUB_REG_MAX_HITS 512u
 #define SUB_CHUNK 16u // most reads whose bounds a wave of the larger size classes fetches at once
@@ -1583,9 +1563,8 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 	// ---- RUNS of records as the sort's elements (the kernels' comment): when the caller said how the records of one query's own lines stand in the input
 	// (mahip_set_run_stride: 2 with mirrored records, 1 without), the ids are dense and the three fields fit a word.  Falls back to sorting records when the
 	// input has few runs, or two runs of one read interleave.
-	static const int runs_on = getenv("MA_SORT_RUNS") ? atoi(getenv("MA_SORT_RUNS")) : 1;
 	const int bl_runs = 64 - bq - bi;
-	if (!sharded && runs_on && c->run_stride && c->n_seq && bl_runs >= RUN_MIN_LEN_BITS && bi <= 32) {
+	if (!sharded && c->run_stride && c->n_seq && bl_runs >= RUN_MIN_LEN_BITS && bi <= 32) {
 		const int bl = bl_runs > 16 ? 16 : bl_runs;
 		const size_t nb1 = (n + RUN_TILE - 1) / RUN_TILE;
 		uint32_t *ticket; unsigned long long *state; uint32_t ticket_base, epoch;
@@ -1660,9 +1639,8 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 		return 0;
 	}
 	if (runs_done) first_hist = true; // (nothing below needs keys)
-	static const int fuse_goff = getenv("MA_GOFF_FUSE") ? atoi(getenv("MA_GOFF_FUSE")) : 1;
 	if (runs_done) { /* sorted as runs above: sidx and goff are made */ }
-	else if (!sharded && fuse_goff && c->n_seq) { // the group offsets come out of the sort's last pass (ids are < n_seq by contract, checked by the kernel)
+	else if (!sharded && c->n_seq) { // the group offsets come out of the sort's last pass (ids are < n_seq by contract, checked by the kernel)
 		const RadixGroups grp = {P<uint32_t>(c->goff), bi, c->n_seq};
 		CHK(radix_sort_keys(c, n, bi, bi + bq, &gen, first_hist, &grp));
 	} else {
@@ -1752,7 +1730,7 @@ extern "C" int mahip_hits_sub(mahip_ctx_t *c, int min_dp, float min_iden, int en
 	uint2 *sub = P<uint2>(c->sub[slot]);
 	SubFuse nofuse = {nullptr, 0, 0, 0, nullptr};
 	SubGather nog = {nullptr, 0, 0, nullptr, nullptr, 0, sub_chunk(Rr), q_lo};
-	const bool fuse_gather = c->gather_pending && R && c->n_hits && !getenv("MA_NO_GATHER_FUSE");
+	const bool fuse_gather = c->gather_pending && R && c->n_hits;
 	if (c->gather_pending && !fuse_gather) CHK(hits_need_cols(c, "mahip_hits_sub"));
 	if (fuse_gather) { // the sweep fetches the records itself and writes the columns on the way
 		const uint32_t pmask = c->gk_bi >= 32 ? 0xffffffffu : (1u << c->gk_bi) - 1u;
@@ -1760,30 +1738,26 @@ extern "C" int mahip_hits_sub(mahip_ctx_t *c, int min_dp, float min_iden, int en
 		                               : SubGather{(const uint32_t*)P<uint64_t>(c->key[c->gk_gen]), 2u, pmask, c->d_aos, P<uint32_t>(c->sidx), (uint32_t)c->n_hits, sub_chunk(Rr), q_lo};
 		ProfScope ps(c, "k_hit_sub<gather>", (64.0 + 48.0) * (double)c->n_hits); // hit sort 64 (32 r + 32 w, counted once whatever the digit passes) + ma_hit_sub 48 B per stored hit
 		SubFork fk(c);
-		const dim3 grd(grid_for(Rr, 4, MA_SUB_BLOCKS)), blk(256);
+		const dim3 grd(grid_for(Rr, 4, SUB_BLOCKS)), blk(256);
 		const uint32_t *gf = (const uint32_t*)P<uint32_t>(c->goff);
-		auto launch = [&](int cls) {
-			const dim3 gr = cls == 0 ? grd : dim3(sub_big_grid(grd.x));
-			if (c->gk_runs) { // positions from sidx (k_runs_expand), which is not written again
-				if (cls == 0) hipLaunchKernelGGL((k_hit_sub<false, 0, 2>), gr, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-				else if (cls == 1) hipLaunchKernelGGL((k_hit_sub<false, 1, 2>), gr, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-				else hipLaunchKernelGGL((k_hit_sub<false, 2, 2>), gr, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			} else {
-				if (cls == 0) hipLaunchKernelGGL((k_hit_sub<false, 0, 1>), gr, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-				else if (cls == 1) hipLaunchKernelGGL((k_hit_sub<false, 1, 1>), gr, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-				else hipLaunchKernelGGL((k_hit_sub<false, 2, 1>), gr, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			}
-		};
-		for (int k = 0; k < 3; ++k) launch(sub_order()[k]);
+		if (c->gk_runs) { // positions from sidx (k_runs_expand), which is not written again
+			hipLaunchKernelGGL((k_hit_sub<false, 0, 2>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+			hipLaunchKernelGGL((k_hit_sub<false, 1, 2>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+			hipLaunchKernelGGL((k_hit_sub<false, 2, 2>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+		} else {
+			hipLaunchKernelGGL((k_hit_sub<false, 0, 1>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+			hipLaunchKernelGGL((k_hit_sub<false, 1, 1>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+			hipLaunchKernelGGL((k_hit_sub<false, 2, 1>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
+		}
 		fk.join();
 		c->gather_pending = false;
 	} else if (R) {
 		ProfScope ps(c, "k_hit_sub", 48.0 * (double)c->n_hits + 8.0 * R); // 32 r + 8 w events + 8 r events per stored hit
-		hipLaunchKernelGGL((k_hit_sub<false, 0>), dim3(grid_for(Rr, 4, MA_SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
+		hipLaunchKernelGGL((k_hit_sub<false, 0>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
 		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
-		hipLaunchKernelGGL((k_hit_sub<false, 1>), dim3(grid_for(Rr, 4, MA_SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
+		hipLaunchKernelGGL((k_hit_sub<false, 1>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
 		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
-		hipLaunchKernelGGL((k_hit_sub<false, 2>), dim3(grid_for(Rr, 4, MA_SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
+		hipLaunchKernelGGL((k_hit_sub<false, 2>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
 		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
 	}
 	if (R) { // tier B always runs behind the register tiers on a small grid: it finds its work list (usually empty) in the device counter
@@ -1817,16 +1791,12 @@ extern "C" int mahip_hits_cutflt_sub(mahip_ctx_t *c, int cut_slot, int min_span,
 	if (R) {
 		ProfScope ps(c, "k_hit_sub<cut+flt>", (80.0 + 80.0 + 48.0) * (double)c->n_hits + 8.0 * R); // cut 80 + flt 80 + sub 48 B per hit
 		SubFork fk(c);
-		const dim3 grd(grid_for(Rr, 4, MA_SUB_BLOCKS)), blk(256);
+		const dim3 grd(grid_for(Rr, 4, SUB_BLOCKS)), blk(256);
 		const uint32_t *gf = (const uint32_t*)P<uint32_t>(c->goff);
 		const SubGather nog2 = SubGather{nullptr, 0, 0, nullptr, nullptr, 0, sub_chunk(Rr), q_lo};
-		auto launch = [&](int cls) {
-			const dim3 gr = cls == 0 ? grd : dim3(sub_big_grid(grd.x));
-			if (cls == 0) hipLaunchKernelGGL((k_hit_sub<true, 0>), gr, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-			else if (cls == 1) hipLaunchKernelGGL((k_hit_sub<true, 1>), gr, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-			else hipLaunchKernelGGL((k_hit_sub<true, 2>), gr, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-		};
-		for (int k = 0; k < 3; ++k) launch(sub_order()[k]);
+		hipLaunchKernelGGL((k_hit_sub<true, 0>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
+		hipLaunchKernelGGL((k_hit_sub<true, 1>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
+		hipLaunchKernelGGL((k_hit_sub<true, 2>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
 		fk.join();
 	}
 	if (R) {

@@ -13,6 +13,7 @@
 #include "ma_core.h"
 
 void mahip_set_error(const char *fmt, ...);
+extern "C" int ma_timing_level(void); // MA_PIPE_TIMING: 0 unset, else max(1, its value) (host/timers.c)
 
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	mahip_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); return -1; } } while (0)
@@ -152,11 +153,11 @@ struct ProfScope {
 	~ProfScope() { if (c->prof) prof_end(c); }
 };
 
-// MA_PIPE_TIMING >= 2: wall time of the steps of the tie repair (a stream sync per lap), `[T::ties]   <step> <ms>` on stderr
+// timing level >= 2: wall time of the steps of the tie repair (a stream sync per lap), `[T::ties]   <step> <ms>` on stderr
 struct TieLaps {
 	mahip_ctx *c; bool on; double t0 = 0;
 	static double now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; }
-	explicit TieLaps(mahip_ctx *c_) : c(c_) { const char *s = getenv("MA_PIPE_TIMING"); on = s && atoi(s) >= 2; if (on) { (void)hipStreamSynchronize(c->st); t0 = now(); } }
+	explicit TieLaps(mahip_ctx *c_) : c(c_) { on = ma_timing_level() >= 2; if (on) { (void)hipStreamSynchronize(c->st); t0 = now(); } }
 	void lap(const char *what) { if (!on) return; (void)hipStreamSynchronize(c->st); const double t1 = now(); fprintf(stderr, "[T::ties]   %-34s %9.3f ms\n", what, (t1 - t0) * 1e3); t0 = t1; }
 };
 

@@ -18,8 +18,6 @@
 #include "mahip_internal.hpp"
 #include <time.h>
 
-#define PAF_TILE 4096u            // bytes per block in the newline passes (256 threads x 16 B)
-#define PAF_LDS_BYTES 49152u      // text of 256 consecutive lines is staged in LDS when it fits
 #define PAF_PROBE_LIMIT 2048u
 #define PAF_EMPTY 0xffffffffffffffffull
 
@@ -37,7 +35,7 @@ struct PafBufs {
 	DevBuf text, lstart, tile;
 	DevBuf glast, gmax, tfirst; // tile parser: last newline per granule / per group of granules, first line start per tile
 	DevBuf flags, num[8], tnoff, qlen, tlen, hq, ht, qslot, tslot;
-	DevBuf tab, tmin, info, slot_id, blv, scal, excl;
+	DevBuf tab, tmin, slot_id, blv, scal, excl;
 	DevBuf name_off, name_len, name_pos, seq_len, names;
 	size_t nbytes = 0, name_bytes = 0;
 	uint32_t n_seq = 0;
@@ -62,71 +60,12 @@ void paf_free(mahip_ctx *c)
 {
 	PafBufs *b = (PafBufs*)c->paf;
 	if (!b) return;
-	DevBuf *all[] = { &b->text, &b->lstart, &b->tile, &b->glast, &b->gmax, &b->tfirst, &b->flags, &b->tnoff, &b->qlen, &b->tlen, &b->hq, &b->ht, &b->qslot, &b->tslot, &b->tab, &b->tmin, &b->info,
+	DevBuf *all[] = { &b->text, &b->lstart, &b->tile, &b->glast, &b->gmax, &b->tfirst, &b->flags, &b->tnoff, &b->qlen, &b->tlen, &b->hq, &b->ht, &b->qslot, &b->tslot, &b->tab, &b->tmin,
 		&b->slot_id, &b->blv, &b->scal, &b->excl, &b->name_off, &b->name_len, &b->name_pos, &b->seq_len, &b->names };
 	for (DevBuf *d : all) dev_free(c, *d);
 	for (int k = 0; k < 8; ++k) dev_free(c, b->num[k]);
 	delete b;
 	c->paf = nullptr;
-}
-
-// ------------------------------------------------------------------------------------------------ line starts
-
-__device__ __forceinline__ uint32_t nl_mask(uint32_t v) // 0x80 in every byte of v that equals '\n'
-{
-	v ^= 0x0A0A0A0Au;
-	uint32_t t = (v & 0x7F7F7F7Fu) + 0x7F7F7F7Fu;
-	return ~(t | v | 0x7F7F7F7Fu);
-}
-
-__device__ __forceinline__ uint4 load16(const unsigned char *__restrict__ text, size_t off, size_t n)
-{
-	if (off + 16 <= n) return *(const uint4*)(text + off);
-	uint32_t w[4] = { 0, 0, 0, 0 };
-	for (int k = 0; k < 16; ++k) if (off + k < n) w[k >> 2] |= (uint32_t)text[off + k] << (8 * (k & 3));
-	return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__global__ __launch_bounds__(256) void k_paf_nl_count(const unsigned char *__restrict__ text, size_t n, uint32_t *__restrict__ tile_cnt)
-{
-	__shared__ uint32_t s_w[4];
-	size_t off = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
-	uint32_t cnt = 0;
-	if (off < n) {
-		uint4 v = load16(text, off, n);
-		cnt = __popc(nl_mask(v.x)) + __popc(nl_mask(v.y)) + __popc(nl_mask(v.z)) + __popc(nl_mask(v.w));
-	}
-	cnt = wv_sum_u32(cnt);
-	if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = cnt;
-	__syncthreads();
-	if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// lstart[k+1] = byte after the k-th newline; lstart[0] = 0; an unterminated last line gets the sentinel n+1
-__global__ __launch_bounds__(256) void k_paf_nl_pos(const unsigned char *__restrict__ text, size_t n, const uint32_t *__restrict__ tile_off,
-                                                     const uint32_t *__restrict__ d_total, uint64_t *__restrict__ lstart, unsigned long long *__restrict__ ctr)
-{
-	__shared__ uint32_t s_w[4];
-	size_t off = ((size_t)blockIdx.x * 256 + threadIdx.x) * 16;
-	uint32_t m[4] = { 0, 0, 0, 0 }, cnt = 0, tot;
-	if (off < n) {
-		uint4 v = load16(text, off, n);
-		m[0] = nl_mask(v.x); m[1] = nl_mask(v.y); m[2] = nl_mask(v.z); m[3] = nl_mask(v.w);
-		cnt = __popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]);
-	}
-	uint32_t k = tile_off[blockIdx.x] + block_excl_scan_256(cnt, s_w, &tot);
-	for (int w = 0; w < 4; ++w)
-		for (uint32_t x = m[w]; x; x &= x - 1) {
-			int byte = (__ffs(x) - 1) >> 3;
-			lstart[++k] = off + (size_t)(w * 4 + byte) + 1;
-		}
-	if (blockIdx.x == 0 && threadIdx.x == 0) {
-		uint32_t nl = *d_total;
-		int open = n > 0 && text[n - 1] != '\n';
-		lstart[0] = 0;
-		if (open) lstart[(size_t)nl + 1] = (uint64_t)n + 1;
-		ctr[PC_LINES] = (unsigned long long)nl + (unsigned long long)open;
-	}
 }
 
 // ------------------------------------------------------------------------------------------------ per-line parse
@@ -227,44 +166,6 @@ __device__ __forceinline__ void paf_line(PTR p, uint32_t l, FsCols fs /* LDS, 12
 	if (o.hasbl) o.bl = paf_num(p, fs[10], fs[11] - 1);
 }
 
-__global__ __launch_bounds__(256) void k_paf_parse(const unsigned char *__restrict__ text, size_t n, const uint64_t *__restrict__ lstart, uint32_t L,
-                                                    int min_span, int min_match, PafCols o, uint32_t *__restrict__ f_hasbl, unsigned long long *__restrict__ ctr, uint32_t lds_bytes)
-{
-	extern __shared__ __attribute__((aligned(16))) unsigned char s_text[]; // lds_bytes (+ slack); read and written 16 / 8 bytes at a time: sized by the host from the mean line length, so that several blocks fit a CU
-	__shared__ uint32_t s_fs[256 * 12];
-	const uint32_t i0 = blockIdx.x * 256u, i1 = i0 + 256u < L ? i0 + 256u : L;
-	const uint64_t b0 = lstart[i0], e1 = lstart[i1] - 1; // bytes of these lines: [b0, e1)
-	const uint64_t a0 = b0 & ~(uint64_t)15;
-	const bool in_lds = e1 - a0 <= lds_bytes;
-	if (in_lds) {
-		for (uint64_t x = (uint64_t)threadIdx.x * 16; a0 + x < e1; x += 256 * 16) *(uint4*)(s_text + x) = load16(text, a0 + x, n);
-		__syncthreads();
-	}
-	const uint32_t i = i0 + threadIdx.x;
-	uint32_t valid = 0, pass = 0, nobl = 0;
-	uint64_t mq = 0;
-	if (i < i1) {
-		const uint64_t ls = lstart[i];
-		const uint32_t l = (uint32_t)(lstart[i + 1] - 1 - ls);
-		PafLine r;
-		const FsCols fs = { s_fs + threadIdx.x };
-		if (in_lds) paf_line((const unsigned char*)(s_text + (ls - a0)), l, fs, r); // LDS byte reads
-		else paf_line(text + ls, l, fs, r);                                              // oversized lines: straight from global memory
-		valid = r.valid;
-		pass = valid && !(r.qe - r.qs < (uint32_t)min_span || r.te - r.ts < (uint32_t)min_span || (int)r.ml < min_match); // hit.c:85
-		nobl = valid && !r.hasbl;
-		o.flags[i] = (uint8_t)(valid | pass << 1 | r.hasbl << 2 | r.rev << 3);
-		f_hasbl[i] = r.hasbl;
-		o.ql[i] = r.ql; o.qs[i] = r.qs; o.qe[i] = r.qe; o.tl[i] = r.tl; o.ts[i] = r.ts; o.te[i] = r.te; o.ml[i] = r.ml; o.bl[i] = r.bl;
-		o.tnoff[i] = r.tnoff; o.qlen[i] = r.qlen; o.tlen[i] = r.tlen; o.hq[i] = r.hq; o.ht[i] = r.ht;
-		if (pass) mq = r.qs > r.ts ? r.qs : r.ts;
-	}
-	blk_add_u64(&ctr[PC_VALID], valid);
-	blk_add_u64(&ctr[PC_PASS], pass);
-	blk_add_u64(&ctr[PC_NOBL], nobl);
-	blk_max_u64(&ctr[PC_MAXQS], mq);
-}
-
 // the `bl` a 10-column line inherits: value of the nearest earlier line with an 11th column (paf.c leaves the field alone)
 __global__ __launch_bounds__(256) void k_paf_bl_compact(const uint32_t *__restrict__ f_hasbl, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ bl, uint32_t L, uint32_t *__restrict__ blv)
 {
@@ -278,8 +179,8 @@ __global__ __launch_bounds__(256) void k_paf_bl_fill(const uint32_t *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------------ tile parser (round 6)
-// The lane-per-line parser above walks every byte of its line twice in divergent loops: 2 100 scalar + 1 340 vector instructions per 64 lines, bound by the
-// CU's ONE scalar unit (profiles/r04_sq_counters_cfg4.txt: 12.6 ms per 100 M lines).  This one has no per-byte loop at all:
+// Round 5 parsed a line per lane with paf_line, every byte twice in divergent loops: bound by the CU's ONE scalar unit (profiles/r04_sq_counters_cfg4.txt:
+// 12.6 ms per 100 M lines).  This one has no per-byte loop at all:
 //   * the text is cut into tiles of K KiB (K from the mean line length: about 240 lines a tile); a tile owns the lines that END in it and keeps the up to
 //     960 bytes in front of it in LDS as well, where its first line may start;
 //   * while the 16-byte pieces travel from HBM to LDS their TABs and newlines are found by SWAR compares and leave as one BIT per byte (two 2-KiB arrays);
@@ -431,11 +332,13 @@ __device__ __forceinline__ uint64_t lds_name_key(const uint32_t *__restrict__ w,
 #ifndef PAF_TILE_WAVES
 #define PAF_TILE_WAVES 1 // __launch_bounds__' second argument (waves per SIMD the register allocation has to leave room for): an experiment handle
 #endif
+// the block's dynamic LDS (declared outside the template: the CPU test build's g++ gets an extern thread_local declared inside a template wrong)
+extern __shared__ __attribute__((aligned(16))) unsigned char s_text[];
 template <int CH> // a block stages up to CH * 16 KiB of text: CH * 64 bytes per thread in the newline ranking
 __global__ __launch_bounds__(256, PAF_TILE_WAVES) void k_paf_parse_tile(const TileArgs a, PafCols o, uint64_t *__restrict__ lstart, unsigned long long *__restrict__ ctr)
 {
 	constexpr uint32_t REG = (uint32_t)CH * 16384u;
-	extern __shared__ __attribute__((aligned(16))) unsigned char s_text[]; // the text: REG + 32; behind it:
+	// s_text: the text, REG + 32; behind it:
 	uint16_t *s_tb = (uint16_t*)(s_text + REG + 32);        // REG / 16 + 8: TAB bits, one u16 per 16-byte piece
 	uint16_t *s_nb = s_tb + REG / 16 + 8;                   // the same for newlines
 	uint32_t *s_lend = (uint32_t*)(s_nb + REG / 16 + 8);    // [0] end of the line in front of the batch, [1 + j] newline of the batch's j-th line
@@ -711,12 +614,12 @@ __global__ __launch_bounds__(256) void k_dict_exact_tmin(const XSlot *__restrict
 
 // A PAF file lists a query's overlaps together (the reference's own all-vs-all pipeline writes them so; so does every overlapper that works query by
 // query): the QUERY name of a line is, 49 times in 50 at BASELINE coverage, the previous line's.  A wave holds 64 consecutive lines; a lane whose query
-// name equals its left neighbour's (same hash, same length, same bytes) does not probe but takes the slot of the nearest lane to its left that did (the
+// name equals its left neighbour's (PF_QCONT: the tile parser compared the bytes in LDS) does not probe but takes the slot of the nearest lane to its left that did (the
 // head of its run: its occurrence number is the run's smallest, so tmin is right as well).  Round 2 probed once per name occurrence: 200 M probes and
 // 68 GB of fetches for 100 M lines; the query column now costs one probe per run and wave.  Target names change from line to line and probe as before.
 __global__ __launch_bounds__(256) void k_dict_insert(const unsigned char *__restrict__ text, const uint64_t *__restrict__ lstart, uint32_t L, PafCols o,
-                                                      XSlot *__restrict__ tab, uint32_t mask, unsigned long long *__restrict__ ctr, int runs_flagged)
-{ // runs_flagged: the tile parser compared every line's query name with the line in front (PF_QCONT, bytes in LDS); else (round 5's parser) it is done here, on the text
+                                                      XSlot *__restrict__ tab, uint32_t mask, unsigned long long *__restrict__ ctr)
+{
 	uint32_t fail = 0, fresh = 0;
 	const unsigned lane = threadIdx.x & 63;
 	for (uint32_t base = blockIdx.x * 256u; base < L; base += gridDim.x * 256u) { // wave-uniform: the lanes talk to each other below
@@ -727,11 +630,8 @@ __global__ __launch_bounds__(256) void k_dict_insert(const unsigned char *__rest
 		const uint64_t hq = stored ? o.hq[i] : 0;
 		const uint32_t qlen = stored ? o.qlen[i] : 0;
 		// does this line continue its left neighbour's run of one query name?
-		const uint64_t hq_l = (uint64_t)__shfl_up((uint32_t)(hq >> 32), 1, 64) << 32 | __shfl_up((uint32_t)hq, 1, 64);
-		const uint32_t qlen_l = __shfl_up(qlen, 1, 64);
-		const uint64_t ls_l = (uint64_t)__shfl_up((uint32_t)(ls >> 32), 1, 64) << 32 | __shfl_up((uint32_t)ls, 1, 64);
 		const int stored_l = __shfl_up((int)stored, 1, 64);
-		const bool cont = stored && lane > 0 && stored_l && (runs_flagged ? (fl & PF_QCONT) != 0 : hq_l == hq && qlen_l == qlen && name_eq(text + ls, text + ls_l, qlen));
+		const bool cont = stored && lane > 0 && stored_l && (fl & PF_QCONT) != 0;
 		uint32_t qslot = 0xffffffffu;
 		if (stored && !cont) qslot = dict_probe(text, lstart, o, tab, mask, hq, qlen, i * 2u, ls, &fresh);
 		const unsigned long long heads = __ballot(stored && !cont);
@@ -972,35 +872,7 @@ __global__ __launch_bounds__(256) void k_bl_fill_from(const uint32_t *__restrict
 
 // ------------------------------------------------------------------------------------------------ records
 
-__global__ __launch_bounds__(256) void k_paf_ids(PafCols o, const uint32_t *__restrict__ slot_id, uint32_t L, int bi_dir, uint32_t *__restrict__ keep)
-{
-	uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= L) return;
-	uint32_t cnt = 0;
-	if (o.flags[i] & 2) {
-		const uint32_t qid = slot_id[o.qslot[i]], tid = slot_id[o.tslot[i]];
-		o.qslot[i] = qid; o.tslot[i] = tid;
-		cnt = 1 + (bi_dir && qid != tid); // hit.c:87-98
-	}
-	keep[i] = cnt;
-}
-
-__global__ __launch_bounds__(256) void k_paf_emit(PafCols o, const uint32_t *__restrict__ keep, const uint32_t *__restrict__ pos, uint32_t L, uint4 *__restrict__ rec)
-{
-	uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i >= L || keep[i] == 0) return;
-	const uint32_t qid = o.qslot[i], tid = o.tslot[i];
-	const uint32_t mlrev = o.ml[i] | (uint32_t)(o.flags[i] >> 3 & 1) << 31, bl = o.bl[i] & 0x7fffffffu;
-	const size_t k = (size_t)pos[i] * 2;
-	rec[k] = make_uint4(o.qs[i], qid, o.qe[i], tid);       // qns = qid<<32 | qs ; qe ; tn
-	rec[k + 1] = make_uint4(o.ts[i], o.te[i], mlrev, bl);   // ts ; te ; ml|rev ; bl|del=0
-	if (keep[i] == 2) {
-		rec[k + 2] = make_uint4(o.ts[i], tid, o.te[i], qid);
-		rec[k + 3] = make_uint4(o.qs[i], o.qe[i], mlrev, bl);
-	}
-}
-
-// ids + record slots + records in ONE pass (until round 5: k_paf_ids, a scan, k_paf_emit -- the columns read twice, ids and counts written and read back):
+// ids + record slots + records in ONE pass (round 5 took three launches -- ids, a scan, records -- and read the columns twice):
 // a tile of 1 024 lines looks up its ids, counts its records, learns where they go from the tiles in front of it (chained look-back, scan.hip) and writes them.
 // A lane has a LINE (row r of the tile = lines 64 r .. 64 r + 63, wave w takes rows w, w + 4, ...): a line's 32 or 64 bytes of records leave from one lane, so the
 // lanes of a store instruction fill neighbouring 64-byte stretches (four lines per lane, as the first version had it, put them 256 bytes apart: 4.7 ms against
@@ -1081,7 +953,7 @@ static int paf_reserve_text(mahip_ctx *c, size_t nbytes)
 		const char *e = getenv("MA_PAF_MAX_BYTES");
 		if (e && nbytes > (size_t)atoll(e)) { mahip_set_error("text of %zu bytes exceeds MA_PAF_MAX_BYTES", nbytes); return -1; }
 	}
-	const bool timing = getenv("MA_PIPE_TIMING") != nullptr;
+	const bool timing = ma_timing_level() >= 1;
 	struct timespec ts0, ts1;
 	if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
 	CHK(dev_reserve(c, b->text, nbytes + 64));
@@ -1148,7 +1020,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	memset(info, 0, sizeof(*info));
 	b->n_seq = 0; b->name_bytes = 0;
 	// MA_PIPE_TIMING=2: wall-clock laps of this function's parts on stderr (each lap waits for the stream: a diagnostic, it changes what it measures by the waits)
-	const bool laps = []{ const char *e = getenv("MA_PIPE_TIMING"); return e && atoi(e) >= 2; }();
+	const bool laps = ma_timing_level() >= 2;
 	struct timespec lap_t0;
 	if (laps) clock_gettime(CLOCK_MONOTONIC, &lap_t0);
 	auto lap = [&](const char *what) {
@@ -1161,7 +1033,6 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	};
 
 	// ---- line starts
-	const bool old_path = []{ const char *e = getenv("MA_PAF_OLD"); return e && atoi(e) != 0; }(); // round 5's kernels (lane-per-line parser, text-comparing dictionary, ids / scan / emit): the A/B switch
 	CHK(dev_reserve(c, b->scal, 64));
 	CHK(ctr_zero(c));
 	uint32_t L = 0;
@@ -1174,27 +1045,8 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 		HIPCHK(hipStreamSynchronize(c->st));
 		open_line = last != '\n';
 	}
-	if (n && old_path) {
-		const size_t n_tiles4k = (n + PAF_TILE - 1) / PAF_TILE;
-		if (n_tiles4k > 0x7fffffffull) { mahip_set_error("mahip_paf_parse: text too large"); return -1; }
-		CHK(dev_reserve(c, b->tile, (n_tiles4k + 8) * 4));
-		{
-			ProfScope ps(c, "k_paf_nl_count", (double)n);
-			hipLaunchKernelGGL(k_paf_nl_count, dim3((unsigned)n_tiles4k), dim3(256), 0, c->st, text, n, P<uint32_t>(b->tile));
-		}
-		CHK(scan_exclusive_u32(c, P<uint32_t>(b->tile), P<uint32_t>(b->tile), n_tiles4k, P<uint32_t>(b->scal)));
-		uint32_t n_nl = 0;
-		HIPCHK(hipMemcpyAsync(&n_nl, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		if ((uint64_t)n_nl + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse: more than 2^31 lines"); return -1; }
-		CHK(dev_reserve(c, b->lstart, ((size_t)n_nl + 4) * 8));
-		{
-			ProfScope ps(c, "k_paf_nl_pos", (double)n + 8.0 * (double)n_nl);
-			hipLaunchKernelGGL(k_paf_nl_pos, dim3((unsigned)n_tiles4k), dim3(256), 0, c->st, text, n, (const uint32_t*)P<uint32_t>(b->tile), (const uint32_t*)P<uint32_t>(b->scal), P<uint64_t>(b->lstart), ctr);
-		}
-		L = n_nl + (uint32_t)open_line;
-	} else if (n) { // newline census per KiB; the tile parser writes the line starts itself
-		// every line ends with a newline: a text that does not gets one (the buffer has 64 spare bytes; the line's sentinel n + 1 is what k_paf_nl_pos gives it),
+	if (n) { // newline census per KiB; the tile parser writes the line starts itself
+		// every line ends with a newline: a text that does not gets one (the buffer has 64 spare bytes; the line start after it is n + 1),
 		// and zeros follow, so that the kernels read whole 16-byte pieces
 		HIPCHK(hipMemsetAsync((void*)(text + n), 0, 64, c->st));
 		if (open_line) HIPCHK(hipMemsetAsync((void*)(text + n), '\n', 1, c->st));
@@ -1251,15 +1103,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	if (L) {
 		CHK(dev_reserve(c, c->keep, ((size_t)L + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)L + 16) * 4));
 		lap("columns reserved");
-		if (old_path) {
-			ProfScope ps(c, "k_paf_parse", (double)n + 61.0 * (double)L);
-			// LDS tile: 1.5 x the mean text of 256 lines, in 4 KiB steps (blocks whose lines are longer read global memory)
-			uint32_t lds_bytes = (uint32_t)((double)n / (double)L * 256.0 * 1.5);
-			lds_bytes = (lds_bytes + 4095u) & ~4095u;
-			if (lds_bytes < 8192u) lds_bytes = 8192u;
-			if (lds_bytes > PAF_LDS_BYTES) lds_bytes = PAF_LDS_BYTES;
-			hipLaunchKernelGGL(k_paf_parse, dim3(grid_for(L, 256)), dim3(256), lds_bytes + 32, c->st, text, n, (const uint64_t*)P<uint64_t>(b->lstart), L, min_span, min_match, o, P<uint32_t>(c->keep), ctr, lds_bytes);
-		} else {
+		{
 			ProfScope ps(c, "k_paf_parse", (double)n + 69.0 * (double)L);
 			TileArgs ta;
 			ta.text = text; ta.n = n_eff; ta.K = tile_k; ta.n_gran = n_gran; ta.n_tiles = n_tiles; ta.L = L;
@@ -1273,17 +1117,17 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			else hipLaunchKernelGGL(k_paf_parse_tile<2>, dim3(grid), dim3(256), lds, c->st, ta, o, P<uint64_t>(b->lstart), ctr);
 		}
 		CHK(ctr_fetch(c));
-		if (!old_path && c->h_ctr[PC_ODD]) { // lines the straight-line parser does not cover: the byte-wise routine on them (the counters add up)
+		if (c->h_ctr[PC_ODD]) { // lines the straight-line parser does not cover: the byte-wise routine on them (the counters add up)
 			ProfScope ps(c, "k_paf_parse_odd", 0.0);
 			hipLaunchKernelGGL(k_paf_parse_odd, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, min_span, min_match, o, ctr);
 			CHK(ctr_fetch(c));
 		}
 		n_valid = (size_t)c->h_ctr[PC_VALID]; n_pass = (size_t)c->h_ctr[PC_PASS]; n_nobl = (size_t)c->h_ctr[PC_NOBL];
-		n_long = old_path ? n_pass : (size_t)c->h_ctr[PC_LONG];
+		n_long = (size_t)c->h_ctr[PC_LONG];
 		max_qs = (uint32_t)c->h_ctr[PC_MAXQS];
 		if (n_nobl && !sharded) { // stale bl: rare (PAF writers emit 12+ columns)
 			CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
-			if (!old_path) hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
+			hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
 			CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, nullptr));
 			hipLaunchKernelGGL(k_paf_bl_compact, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)o.bl, L, P<uint32_t>(b->blv));
 			hipLaunchKernelGGL(k_paf_bl_fill, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->blv), L, o.bl);
@@ -1307,7 +1151,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			uint32_t n_has = 0, last_bl = 0;
 			if (L) {
 				CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
-				if (!old_path) hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
+				hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
 				CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, P<uint32_t>(b->scal)));
 				hipLaunchKernelGGL(k_paf_bl_compact, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)o.bl, L, P<uint32_t>(b->blv));
 				HIPCHK(hipMemcpyAsync(&n_has, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
@@ -1332,7 +1176,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 		const uint32_t cap_max = pow2_at_least(4 * (uint64_t)n_pass + 65536); // load <= 1/2 whatever the file holds
 		uint32_t cap = pow2_at_least(n_pass / 16 + 65536);
 		if (const char *e = getenv("MA_DICT_CAP_LOG2")) { int l2 = atoi(e); if (l2 >= 4 && l2 <= 31) cap = 1u << l2; } // tests: force the growth path
-		const bool short_names = !old_path && n_long == 0 && !getenv("MA_DICT_EXACT_TEXT"); // every name is its own key: no text compared (k_dict_insert_short)
+		const bool short_names = n_long == 0 && !getenv("MA_DICT_EXACT_TEXT"); // every name is its own key: no text compared (k_dict_insert_short)
 		for (int attempt = 0;; ++attempt) {
 			CHK(dev_reserve(c, b->tab, (size_t)cap * 16)); CHK(dev_reserve(c, b->tmin, (size_t)cap * 4)); CHK(dev_reserve(c, b->slot_id, (size_t)cap * 4));
 			CHK(ctr_zero(c));
@@ -1343,7 +1187,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			} else {
 				HIPCHK(hipMemsetAsync(b->tab.p, 0xff, (size_t)cap * 16, c->st));
 				ProfScope ps(c, "k_dict_insert", 2.0 * 40.0 * (double)n_pass);
-				hipLaunchKernelGGL(k_dict_insert, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, o, (XSlot*)b->tab.p, cap - 1, ctr, old_path ? 0 : 1);
+				hipLaunchKernelGGL(k_dict_insert, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, o, (XSlot*)b->tab.p, cap - 1, ctr);
 			}
 			CHK(ctr_fetch(c));
 			const uint64_t distinct = c->h_ctr[PC_DISTINCT];
@@ -1485,22 +1329,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 
 	// ---- records: hit (+ mirrored hit) per stored line, in line order
 	size_t n_hits = 0;
-	if (n_pass && old_path) {
-		CHK(dev_reserve(c, c->keep, ((size_t)L + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)L + 16) * 4));
-		hipLaunchKernelGGL(k_paf_ids, dim3(grid_for(L, 256)), dim3(256), 0, c->st, o, slot_to_id, L, bi_dir, P<uint32_t>(c->keep));
-		uint32_t nh = 0;
-		CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, P<uint32_t>(b->scal)));
-		HIPCHK(hipMemcpyAsync(&nh, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		n_hits = nh;
-		CHK(mahip_hits_adopt(c, nullptr, n_hits, R)); // resets the per-upload state and sizes the read arrays
-		CHK(dev_reserve(c, c->aos_own, (n_hits + 1) * sizeof(ma_hit_t)));
-		c->d_aos = (const ma_hit_t*)c->aos_own.p;
-		if (n_hits) {
-			ProfScope ps(c, "k_paf_emit", 45.0 * (double)n_pass + 32.0 * (double)n_hits);
-			hipLaunchKernelGGL(k_paf_emit, dim3(grid_for(L, 256)), dim3(256), 0, c->st, o, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), L, (uint4*)c->aos_own.p);
-		}
-	} else if (n_pass) { // one pass: ids, record slots (chained tiles), records
+	if (n_pass) { // one pass: ids, record slots (chained tiles), records
 		const size_t max_hits = bi_dir ? 2 * n_pass : n_pass;
 		if (max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
 		CHK(dev_reserve(c, c->aos_own, (max_hits + 1) * sizeof(ma_hit_t)));
@@ -1527,7 +1356,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(c->st));
 	c->hint_max_qs = c->paf_max_qs = max_qs;
-	c->run_stride = sharded ? 0 : bi_dir ? 2 : 1; // k_paf_emit wrote a line's record and its mirror side by side (hit.c:87-98): the sort may take RUNS of records (hits.hip)
+	c->run_stride = sharded ? 0 : bi_dir ? 2 : 1; // k_paf_emit_chain wrote a line's record and its mirror side by side (hit.c:87-98): the sort may take RUNS of records (hits.hip)
 	info->n_records = n_valid; info->n_stored_lines = n_pass; info->n_hits = n_hits; info->n_seq = R; info->max_qs = max_qs; info->name_bytes = b->name_bytes; info->n_lines = L;
 	if (sharded) { info->n_records = valid_total; info->n_stored_lines = pass_total; info->n_lines = lines_total; }
 	return 0;

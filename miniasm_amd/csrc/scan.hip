@@ -144,9 +144,9 @@ static int scan_rec(mahip_ctx *c, const uint32_t *in, uint32_t *out, size_t n, u
 	return 0;
 }
 
-// tiles up to which the one-launch chained scan is used (MA_SCAN_CHAIN_MAX); beyond it the launches of the three-phase scan do not matter and its
+// tiles up to which the one-launch chained scan is used; beyond it the launches of the three-phase scan do not matter and its
 // traffic pattern is the safer one
-static size_t scan_chain_max() { static long v = -1; if (v < 0) { const char *e = getenv("MA_SCAN_CHAIN_MAX"); v = e ? atol(e) : 256; } return (size_t)v; }
+#define SCAN_CHAIN_MAX 256u
 
 // the published words + ticket of ONE chained launch of nb tiles (k_scan_chain, graph.hip: k_arc_rm_chain): the tiles behind one ticket word; fresh memory
 // is cleared once, afterwards the launch epoch tells this launch's words from older ones
@@ -179,7 +179,7 @@ int scan_exclusive_u32(mahip_ctx *c, const uint32_t *in, uint32_t *out, size_t n
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
-	if (nb > scan_chain_max()) { // a big array: reduce / scan of the tile sums / downsweep
+	if (nb > SCAN_CHAIN_MAX) { // a big array: reduce / scan of the tile sums / downsweep
 		CHK(scan_rec(c, in, out, n, d_total, 0));
 		HIPCHK(hipGetLastError());
 		return 0;

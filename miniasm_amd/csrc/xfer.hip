@@ -129,7 +129,7 @@ static int xfer_run(mahip_ctx *c, void *dev_ptr, void *host_ptr, int fd, size_t 
 		if (!started[w]) xfer_worker(&job[w]); // no thread: do this worker's slices here
 	}
 	int rc = 0;
-	const bool timing = getenv("MA_PIPE_TIMING") != nullptr;
+	const bool timing = ma_timing_level() >= 1;
 	struct timespec ts0, ts1;
 	if (timing) clock_gettime(CLOCK_MONOTONIC, &ts0);
 	for (int w = 0; w < W; ++w) {

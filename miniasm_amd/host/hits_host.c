@@ -45,7 +45,7 @@ mahip_ctx_t *ma_gpu(void)
 	if (g_ctx == 0) {
 		const char *s = getenv("MA_GPU_DEVICE");
 		if (s == 0) s = getenv("LOCAL_RANK");
-		const int timing = getenv("MA_PIPE_TIMING") != 0;
+		const int timing = ma_timing_level() >= 1;
 		double t0 = sys_realtime(), t1, t2, t3;
 		int n_dev = mahip_device_count(); /* the first HIP call: the runtime comes up here (driver, queues, the code objects are registered) */
 		t1 = sys_realtime();

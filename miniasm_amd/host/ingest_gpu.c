@@ -53,7 +53,7 @@ int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d
 /* no_cont: -R, the reference's Step 0 (hit.c:38-68) folded into the same parse; prints its log line first */
 int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release, int no_cont, int max_hang, float int_frac)
 {
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	double t1 = sys_realtime(), t2, t3;
 	mahip_paf_info_t info;
 	size_t tot_len = 0;
@@ -127,7 +127,7 @@ int ma_hit_ingest_gpu(mahip_ctx_t *c, const char *fn, int min_span, int min_matc
 
 int ma_hit_ingest_gpu_excl(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int no_cont, int max_hang, float int_frac)
 {
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime();
 	{
 		int rc = ma_paf_load_file(c, fn);

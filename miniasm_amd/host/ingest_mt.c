@@ -278,7 +278,7 @@ ma_hit_t *ma_hit_ingest_mt(const char *fn, int min_span, int min_match, sdict_t 
 	uint32_t mx = 0, prev_bl = 0;
 	char namebuf[65536];
 
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime(), t1, t2, t3;
 	if (T < 2 || fn == 0 || strcmp(fn, "-") == 0) return 0;
 	fd = open(fn, O_RDONLY);

@@ -60,7 +60,7 @@ int ma_ingest_sharded_possible(const char *fn)
 int ma_hit_ingest_sharded(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits_total, int bi_dir, ma_ingest_shard_info_t *si)
 {
 	const int world = mahip_comm_world(c), rank = mahip_comm_rank(c);
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime(), t1, t2, t3;
 	mahip_paf_info_t info;
 	struct stat st;

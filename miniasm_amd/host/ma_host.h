@@ -9,6 +9,8 @@
 extern "C" {
 #endif
 
+int ma_timing_level(void); /* MA_PIPE_TIMING: 0 unset, else max(1, its value) (timers.c) */
+
 /* log sink of the [M::...] lines (stderr unless redirected; bench.py silences it) */
 extern FILE *ma_log_fp;
 #define MA_LOG (ma_log_fp ? ma_log_fp : stderr)
@@ -47,9 +49,9 @@ void ma_ug_print_mem(const ma_ug_t *ug, const sdict_t *d, const ma_sub_t *sub, c
 void ma_sd_reindex(sdict_t *d);    /* build the name index from seq[] (for dictionaries assembled by hand) */
 void ma_sd_drop_index(sdict_t *d);
 void ma_sd_fill(sdict_t *d, char *arena, size_t arena_len, uint32_t n_seq, const uint32_t *lens); /* bulk fill; the dictionary owns arena */
-void ma_sd_adopt(sdict_t *d, char *arena, size_t arena_len, uint32_t n_seq, sd_seq_t *seq);
+void ma_sd_adopt(sdict_t *d, char *arena, size_t arena_len, uint32_t n_seq, sd_seq_t *seq); /* records ready-made; the dictionary owns both blocks */
 int ma_sd_recycle(sdict_t *d, size_t arena_len, uint32_t n_seq, char **arena, sd_seq_t **seq); /* the dictionary's own blocks, if they can hold the next fill */
-void *ma_big_alloc(size_t n); /* 2 MiB-aligned, huge pages advised; free() releases it */         /* records ready-made; the dictionary owns both blocks */
+void *ma_big_alloc(size_t n); /* 2 MiB-aligned, huge pages advised; free() releases it */
 
 /* the process-wide GPU context of the per-symbol entry points; exits with an error if no GPU is usable */
 mahip_ctx_t *ma_gpu(void);

@@ -61,7 +61,7 @@ int ma_pipeline_head(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, cons
 	const int fused = !no_first && !no_second && stage >= 5 && graph_out && !getenv("MA_NO_FUSE");
 	size_t n_cont_hits = 0;
 
-	const int ht = getenv("MA_PIPE_TIMING") && atoi(getenv("MA_PIPE_TIMING")) >= 2; /* per-pass wall time (adds a device sync per pass) */
+	const int ht = ma_timing_level() >= 2; /* per-pass wall time (adds a device sync per pass) */
 	double ht0 = sys_realtime();
 #define HT(label) do { if (ht) { mahip_sync(c); fprintf(stderr, "[T::head] %-28s %8.3f ms\n", label, (sys_realtime() - ht0) * 1e3); ht0 = sys_realtime(); } } while (0)
 	GPU(mahip_hits_sort(c)); /* hit.c:104 */
@@ -137,7 +137,7 @@ int ma_pipeline_head(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, cons
 		}
 		GPU(mahip_sg_gen(c, opt, have_sub, len, sdel, &n_arc));
 		HT("sg_gen");
-		if (getenv("MA_PIPE_TIMING")) { /* what the tie census found and what was done about it */
+		if (ma_timing_level() >= 1) { /* what the tie census found and what was done about it */
 			mahip_tie_info_t ti;
 			mahip_tie_stats(c, &ti);
 			char reads[64] = "";
@@ -333,7 +333,7 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 	}
 	j->t_fetch[3] = sys_realtime();
 	g_tail_laps[0] = (j->t_fetch[1] - j->t_fetch[0]) * 1e3; g_tail_laps[1] = j->t_fetch[2] > 0 ? (j->t_fetch[2] - j->t_fetch[1]) * 1e3 : 0; g_tail_laps[2] = j->t_fetch[2] > 0 ? (j->t_fetch[3] - j->t_fetch[2]) * 1e3 : 0;
-	if (getenv("MA_PIPE_TIMING") && j->have_graph && strcmp(outfmt, "paf") != 0 && strcmp(outfmt, "bed") != 0)
+	if (ma_timing_level() >= 1 && j->have_graph && strcmp(outfmt, "paf") != 0 && strcmp(outfmt, "bed") != 0)
 		fprintf(stderr, "[T::tail] names+sub %.3f  device cleaners %.3f  unitigs/graph to host %.3f ms\n", (j->t_fetch[1]-j->t_fetch[0])*1e3, (j->t_fetch[2]-j->t_fetch[1])*1e3, (j->t_fetch[3]-j->t_fetch[2])*1e3);
 	return j;
 }
@@ -347,7 +347,7 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	const int squeezed = j->squeezed;
 	sdict_t *view = &j->view;
 	ma_sub_t *sub = j->sub;
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime();
 	FILE *ms = 0;
 	if (out == 0 && !(j->ug && strcmp(outfmt, "bed") != 0 && strcmp(outfmt, "paf") != 0)) { ms = open_memstream(buf, len); if (ms == 0) return -1; out = ms; }
@@ -393,7 +393,7 @@ int ma_pipeline_device(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, co
 	ma_pipeline_head(c, opt, d, outfmt, stage, flags, st);
 	t1 = sys_realtime();
 	rc = ma_pipeline_tail(c, opt, d, outfmt, stage, st, out);
-	if (getenv("MA_PIPE_TIMING")) fprintf(stderr, "[T::pipeline] head %.3f ms  tail %.3f ms\n", (t1 - t0) * 1e3, (sys_realtime() - t1) * 1e3);
+	if (ma_timing_level() >= 1) fprintf(stderr, "[T::pipeline] head %.3f ms  tail %.3f ms\n", (t1 - t0) * 1e3, (sys_realtime() - t1) * 1e3);
 	return rc;
 }
 
@@ -406,7 +406,7 @@ int ma_pipeline_device_mem(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d
 	ma_pipeline_head(c, opt, d, outfmt, stage, flags, st);
 	t1 = sys_realtime();
 	rc = tail_finish_to(ma_pipeline_tail_fetch(c, opt, d, outfmt, stage, st), 0, buf, len);
-	if (getenv("MA_PIPE_TIMING")) fprintf(stderr, "[T::pipeline] head %.3f ms  tail %.3f ms\n", (t1 - t0) * 1e3, (sys_realtime() - t1) * 1e3);
+	if (ma_timing_level() >= 1) fprintf(stderr, "[T::pipeline] head %.3f ms  tail %.3f ms\n", (t1 - t0) * 1e3, (sys_realtime() - t1) * 1e3);
 	return rc;
 }
 
@@ -449,7 +449,7 @@ int ma_pipeline_run(const ma_opt_t *opt, const char *fn, const char *outfmt, int
 		if (!dev_parse || (flags & 8)) fprintf(lg, "[M::%s] ===> Step 1: reading read mappings <===\n", "main");
 	}
 	if (!on_device) { /* MA_HOST_PARSE=1, stdin (a stream cannot be re-read after a failed device attempt), or a text too big for the device stage */
-		const int timing = getenv("MA_PIPE_TIMING") != 0;
+		const int timing = ma_timing_level() >= 1;
 		double t0 = sys_realtime(), t1, t2;
 		hit = ma_hit_ingest(fn, opt->min_span, opt->min_match, d, &n_hits, !(flags & 4), excl);
 		if (gpu_bg) pthread_join(th_gpu, 0);

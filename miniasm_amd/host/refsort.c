@@ -28,9 +28,6 @@ static int rs_timing = -1;
 #define RS_T0 double t0_ = rs_now()
 #define RS_LAP(what) do { if (rs_timing < 0) rs_timing = getenv("MA_REFSORT_TIMING") != 0; if (rs_timing) { double t1_ = rs_now(); fprintf(stderr, "[T::refsort] %-12s %.3f s\n", what, t1_ - t0_); t0_ = t1_; } } while (0)
 
-static int rs_late_flag = -1;
-static int rs_late(void) { if (rs_late_flag < 0) rs_late_flag = getenv("MA_REFSORT_LATE") != 0; return rs_late_flag; }
-
 #define RS_MAX_THREADS 128
 #define RS_SMALL 64           /* RS_MIN_SIZE ksort.h:132 */
 /* The walk touches the 256 bucket heads in an order the hardware prefetchers cannot follow (they track a few dozen streams), so every
@@ -276,7 +273,7 @@ int ma_refsort_perm(const uint64_t *keys, size_t n, uint32_t *perm)
 	bh = bits_of64(f.mhi); bl = bits_of64(f.mlo); bi = bits_of64(n - 1);
 	if (bl == 0) bl = 1;
 	if (bi == 0) bi = 1;
-	if (bh + bl + bi <= 64 && !getenv("MA_REFSORT_WIDE")) { /* one word per element */
+	if (bh + bl + bi <= 64) { /* one word per element */
 		f.cfg.bi = bi; f.cfg.bl = bl; f.cfg.lomask = (1ull << bl) - 1;
 		f.pk = (uint64_t*)malloc(n * sizeof(uint64_t));
 		if (f.pk == 0) return -1;
@@ -291,7 +288,7 @@ int ma_refsort_perm(const uint64_t *keys, size_t n, uint32_t *perm)
 	}
 	/* Too wide for one word -- BASELINE configs[4]: 23 id + 14 start + 30 index bits.  Below the top level every element of a bucket has the same top digit,
 	 * so those bits need not travel: if the rest fits, the top level's digits are taken from the raw keys and the elements are packed without them. */
-	if (nt > 1 && n >= (1u << 17) && !getenv("MA_REFSORT_WIDE")) {
+	if (nt > 1 && n >= (1u << 17)) {
 		int shift = 56;
 		fill_run(&f, n, 5, nt);
 		while (shift > 0 && (f.diff >> shift & 0xff) == 0) shift -= 8;

@@ -116,7 +116,7 @@ static void RS_NAME(permute_top)(rs_pool_t *pool, RS_T *a, const size_t *cnt, co
 	 * that are not full only.  With worker threads around it is handed over THEN (ksort.h:177-182 does not care when: the ranges are disjoint), and the buckets
 	 * below the top level are sorted beside the walk instead of behind it (BASELINE configs[4]: top walk 1.68 s, then buckets 1.23 s on 64 threads).  The
 	 * buckets too small for a task of their own wait in `later` for this thread. */
-	const int early = pool->n_threads > 1 && shift != 0 && !rs_late(), next = shift > 8 ? shift - 8 : 0; /* (MA_REFSORT_LATE=1: the A/B switch) */
+	const int early = pool->n_threads > 1 && shift != 0, next = shift > 8 ? shift - 8 : 0;
 	uint8_t later[256];
 	int n_later = 0;
 	int k;

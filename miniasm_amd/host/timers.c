@@ -1,6 +1,7 @@
 /* sys.c -- wall/CPU timers and the "real*cpu/real" stamp used in the [M::fn::stamp] log lines.
  * Same interface and text format as the reference's sys.h:8-11 / sys.c:38-46 (logs double as checksums). */
 #include <stdio.h>
+#include <stdlib.h>
 #include <sys/time.h>
 #include <sys/resource.h>
 #include "miniasm_amd.h"
@@ -34,6 +35,16 @@ void sys_init(void)
 	sys_liftrlimit();
 	t_origin = 0.;
 	t_origin = wall_now();
+}
+
+/* MA_PIPE_TIMING: unset 0, else its number but at least 1 (1: per-phase laps, 2: also the laps that wait for the device).  Read per call. */
+int ma_timing_level(void)
+{
+	const char *e = getenv("MA_PIPE_TIMING");
+	int v;
+	if (!e) return 0;
+	v = atoi(e);
+	return v > 1 ? v : 1;
 }
 
 const char *sys_timestamp(void)

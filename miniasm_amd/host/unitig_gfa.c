@@ -291,7 +291,7 @@ static void ug_print_to(const ma_ug_t *ug, const sdict_t *d, const ma_sub_t *sub
 		job[t].l_lo = (uint32_t)((uint64_t)nl * (uint64_t)t / (uint64_t)T);
 		job[t].l_hi = (uint32_t)((uint64_t)nl * (uint64_t)(t + 1) / (uint64_t)T);
 	}
-	const int timing = getenv("MA_PIPE_TIMING") != 0;
+	const int timing = ma_timing_level() >= 1;
 	const double t_begin = sys_realtime();
 	double t_fmt;
 	for (t = 1; t < T; ++t) {

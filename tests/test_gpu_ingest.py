@@ -219,11 +219,6 @@ def test_tile_parser_shapes(tmpdir_s, monkeypatch):
         for name in ("long3", "empties", "tagged", "cut16384", "cut32768nl"):
             _same_as_host(ctx, os.path.join(tmpdir_s, "gi_tile_%s.paf" % name), opt)
     monkeypatch.delenv("MA_PAF_TILE_K")
-    # round 5's kernels stay behind a switch: same result
-    monkeypatch.setenv("MA_PAF_OLD", "1")
-    for name in ("long3", "mixednames", "empties"):
-        _same_as_host(ctx, os.path.join(tmpdir_s, "gi_tile_%s.paf" % name), opt)
-    monkeypatch.delenv("MA_PAF_OLD")
     # short names only, but the text-comparing dictionary forced: same ids
     monkeypatch.setenv("MA_DICT_EXACT_TEXT", "1")
     _same_as_host(ctx, os.path.join(tmpdir_s, "gi_tile_cut40000.paf"), opt)
