@@ -122,6 +122,8 @@ def lib():
         L.mahip_hits_cut.argtypes = [vp, i32, i32, C.POINTER(sz)]
         L.mahip_hits_flt.argtypes = [vp, i32, i32, i32, C.POINTER(sz), C.POINTER(C.c_float)]
         L.mahip_sub_merge.argtypes = [vp]
+        L.mahip_hits_cutflt_sub.argtypes = [vp, i32, i32, i32, i32, i32, C.c_float, i32, i32, C.POINTER(sz), C.POINTER(sz), C.POINTER(C.c_float), C.POINTER(sz)]
+        L.mahip_hits_cut_contained.argtypes = [vp, i32, i32, C.POINTER(MaOpt), C.POINTER(sz), C.POINTER(u32)]
         L.mahip_hits_contained.argtypes = [vp, C.POINTER(MaOpt), vp, C.POINTER(u32), C.POINTER(sz)]
         L.mahip_sub_upload.argtypes = [vp, i32, vp, sz]
         L.mahip_sub_download.argtypes = [vp, i32, vp, i32]
@@ -243,6 +245,21 @@ class Ctx:
 
     def sub_merge(self):
         _chk(lib().mahip_sub_merge(self.h), "sub_merge")
+
+    def cutflt_sub(self, cut_slot, min_span, max_hang, min_ovlp, min_dp, min_iden, end_clip, out_slot):
+        """fused: cut against cut_slot + filter inside the coverage pass that writes out_slot -> (n_cut, n_flt, cov, n_remained)"""
+        nc, nf, nr = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        cov = C.c_float(0)
+        _chk(lib().mahip_hits_cutflt_sub(self.h, cut_slot, min_span, max_hang, min_ovlp, min_dp, min_iden, end_clip, out_slot,
+                                         C.byref(nc), C.byref(nf), C.byref(cov), C.byref(nr)), "hits_cutflt_sub")
+        return nc.value, nf.value, cov.value, nr.value
+
+    def cut_contained(self, cut_slot, min_span, opt):
+        """fused: cut against cut_slot + the flag pass of contained (squeeze of the hits deferred) -> (n_cut, n_seq_new)"""
+        n = C.c_size_t(0)
+        r = C.c_uint32(0)
+        _chk(lib().mahip_hits_cut_contained(self.h, cut_slot, min_span, C.byref(opt), C.byref(n), C.byref(r)), "hits_cut_contained")
+        return n.value, r.value
 
     def contained(self, opt, seq_del=None):
         n = C.c_size_t(0)

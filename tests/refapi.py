@@ -96,6 +96,9 @@ def ref():
         L.ma_ug_destroy.argtypes = [vp]
         L.free_buf = C.CDLL(None).free
         L.free_buf.argtypes = [vp]
+        L.malloc_buf = C.CDLL(None).malloc  # buffers the reference will free or realloc itself
+        L.malloc_buf.restype = vp
+        L.malloc_buf.argtypes = [sz]
         _ref = L
     return _ref
 

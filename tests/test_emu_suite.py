@@ -50,6 +50,12 @@ def test_kernels_stage_parity_on_cpu(emu_built):
     run_gpu_tests(["tests/test_gpu_parity.py"] + sel, 3000)
 
 
+def test_fused_hit_passes_on_cpu(emu_built):
+    """tests/test_gpu_fused_hits.py: the fused hit passes of the resident pipeline stage by stage against the oracle and the reference library,
+    the reads on every size edge of the coverage kernel under run stride 0 / 1 / 2 (the deep_vertices input only with MA_EMU_FULL=1: a minute alone)"""
+    run_gpu_tests(["tests/test_gpu_fused_hits.py"] + ([] if FULL else ["-k", "not deep_vertices"]), 3000)
+
+
 @pytest.mark.parametrize("stride", ["1", "0"])
 def test_sort_does_not_depend_on_the_run_stride_hint(stride, emu_built):
     """the hit sort takes RUNS of records when told how a query's own records stand in the array (mahip_set_run_stride; the stage tests default to 2 = ma_hit_read's
@@ -61,8 +67,9 @@ def test_sort_does_not_depend_on_the_run_stride_hint(stride, emu_built):
 def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     """the same kernels with lanes, waves and blocks executed in DESCENDING order (code that leans on lock-step execution or on launch order
     without a barrier breaks) and every device allocation ending at a faulting page (an out-of-bounds access crashes)"""
-    run_gpu_tests(["tests/test_gpu_parity.py", "-k", "noisy or deep_groups or sort_random", "tests/test_gpu_ingest.py"], 3000,
-                  {"EMU_ORDER": "reverse", "EMU_GUARD": "1", "MA_DEV_POOL": "0"})  # (the pool hands out pieces of bigger allocations: no guard page behind them)
+    env = {"EMU_ORDER": "reverse", "EMU_GUARD": "1", "MA_DEV_POOL": "0"}  # (the pool hands out pieces of bigger allocations: no guard page behind them)
+    run_gpu_tests(["tests/test_gpu_parity.py", "-k", "noisy or deep_groups or sort_random", "tests/test_gpu_ingest.py"], 3000, env)
+    run_gpu_tests(["tests/test_gpu_fused_hits.py", "-k", "group_size_edges"], 3000, env)  # tier B's global scratch (4097 and 9001 hits) ends at a guard page too
 
 
 def test_kernels_graph_api_on_cpu(emu_built):

@@ -15,15 +15,7 @@ import stages as ST
 
 pytestmark = pytest.mark.gpu
 
-CASES = [
-    ("lognormal", 3000, 80000, 41, []),
-    ("fixed", 2500, 70000, 42, ["-L", "fixed"]),
-    ("lowid", 2000, 50000, 43, ["-i", "0.2"]),
-    ("genome_order", 2000, 50000, 44, ["-g"]),
-    ("noisy", 4000, 90000, 45, ["-L", "uniform", "-d", "0.35", "-x", "0.03"]),
-    ("deep_groups", 400, 300000, 46, []),                 # ~1500 hits per read: second tier of the coverage kernel
-    ("deep_vertices", 1500, 1200000, 47, ["-L", "fixed"]),  # ~800 arcs per vertex: second tier of the reduction kernel
-]
+CASES = ST.PAF_CASES
 
 
 @pytest.mark.parametrize("name,reads,lines,seed,extra", CASES, ids=[c[0] for c in CASES])
@@ -190,10 +182,8 @@ def test_flags_and_ragged_groups_vs_oracle(gpu_ctx, tmpdir_s):
 
 def test_custom_thresholds_vs_oracle(gpu_ctx, tmpdir_s):
     paf = R.pafgen(os.path.join(tmpdir_s, "thr.paf"), 2000, 50000, 52, ["-L", "uniform", "-d", "0.2", "-x", "0.05", "-i", "0.1"])
-    for (dp, iden, span, hang, frac, fuzz) in ((2, .05, 1500, 500, .7, 500), (5, .1, 2500, 2000, .9, 0), (3, .2, 2000, 1000, .8, 3000)):
-        opt = ma.default_opt()
-        opt.min_dp, opt.min_iden, opt.min_span, opt.max_hang, opt.int_frac, opt.gap_fuzz = dp, iden, span, hang, frac, fuzz
-        opt.min_ovlp = span
+    for (dp, iden, span, hang, frac, fuzz) in ST.THRESHOLD_SETS:
+        opt = ST.threshold_opt(dp, iden, span, hang, frac, fuzz)
         ing = ma.Ingest(paf, opt)
         G = ST.gpu_stages(gpu_ctx, ing.hits, ing.n_seq, opt)
         O = ST.orc_stages(ing.hits, ing.n_seq, opt)
@@ -231,71 +221,21 @@ def test_graph_passes_on_uploaded_graph(gpu_ctx, tmpdir_s):
     ing.close()
 
 
-def random_hits(seed):
-    """hit arrays no overlapper writes: a few very deep reads, coordinates on a coarse grid (ties everywhere, zero-length and full-length overlaps),
-    start > end, self hits, ml > bl, bl = 0 -- the passes are integer arithmetic with C's wrap-around rules, so garbage in must give the oracle's
-    garbage out, bit for bit"""
-    rng = np.random.default_rng(seed)
-    R_ = int(rng.choice([1, 3, 20, 200, 2000]))
-    n = int(rng.choice([1, 2, 50, 3000, 60000]))
-    mode = int(rng.integers(0, 4))
-    rl = rng.integers(500, 20000, R_)
-    q = rng.integers(0, R_, n) if mode != 3 else np.minimum(rng.geometric(0.05, n) - 1, R_ - 1)
-    t = rng.integers(0, R_, n)
-    ql, tl = rl[q], rl[t]
-    if mode == 0:
-        qs = (rng.random(n) * ql * 0.8).astype(np.int64); qe = qs + 1 + (rng.random(n) * (ql - qs - 1)).astype(np.int64)
-        ts = (rng.random(n) * tl * 0.8).astype(np.int64); te = ts + 1 + (rng.random(n) * (tl - ts - 1)).astype(np.int64)
-    elif mode == 1:
-        g = 250
-        qs = rng.integers(0, 8, n) * g; qe = np.minimum(qs + rng.integers(0, 40, n) * g, ql)
-        ts = rng.integers(0, 8, n) * g; te = np.minimum(ts + rng.integers(0, 40, n) * g, tl)
-    else:
-        qs = rng.integers(0, ql + 1); qe = rng.integers(0, ql + 1)
-        ts = rng.integers(0, tl + 1); te = rng.integers(0, tl + 1)
-    bl = rng.integers(0, 30000, n)
-    ml = (bl * rng.random(n) * 1.2).astype(np.int64)
-    h = np.zeros(n, dtype=ma.HIT_DT)
-    h["qns"] = (q.astype(np.uint64) << np.uint64(32)) | (qs.astype(np.uint64) & np.uint64(0xffffffff))
-    h["qe"] = qe.astype(np.uint32); h["tn"] = t.astype(np.uint32); h["ts"] = ts.astype(np.uint32); h["te"] = te.astype(np.uint32)
-    h["mlrev"] = (ml.astype(np.uint32) & np.uint32(0x7fffffff)) | (rng.integers(0, 2, n).astype(np.uint32) << np.uint32(31))
-    h["bldel"] = bl.astype(np.uint32) & np.uint32(0x7fffffff)
-    return h, R_
-
-
 @pytest.mark.parametrize("block", range(4))
 def test_random_hit_arrays_match_the_oracle_at_every_stage(block, gpu_ctx):
     opt = ma.default_opt()
     for seed in range(block * 8, block * 8 + 8):
-        h, n_seq = random_hits(seed)
+        h, n_seq = ST.random_hits(seed)
         orc = ST.orc_stages(h, n_seq, opt)
         gpu = ST.gpu_stages(gpu_ctx, h, n_seq, opt)
         ST.compare(orc, gpu, "random hits, seed %d" % seed, exact_order=True, graph=True)
 
 
-@pytest.mark.parametrize("n_seq,n,where", [(2048, 1, "last"), (2049, 100, "first"), (6000, 300, "middle"), (6000, 5000, "ends"), (70000, 20000, "sparse"), (70000, 3, "last")])
+@pytest.mark.parametrize("n_seq,n,where", ST.SPARSE_ID_SHAPES)
 def test_group_offsets_when_most_reads_have_no_hits(n_seq, n, where, gpu_ctx):
     """the group offsets come out of the sort's last pass (radix.hip: RsGroups) and the reads without hits are closed afterwards, tile of 2048 ids by tile:
     ids in use only at one end, in one tile of several, or thinly spread -- every stage behind the sort sees wrong groups if one offset is off"""
-    rng = np.random.default_rng(n_seq + n)
-    if where == "last":
-        q = np.full(n, n_seq - 1)
-    elif where == "first":
-        q = np.zeros(n, dtype=np.int64)
-    elif where == "middle":
-        q = rng.integers(2500, 2600, n)
-    elif where == "ends":
-        q = np.where(rng.integers(0, 2, n) == 0, rng.integers(0, 3, n), n_seq - 1 - rng.integers(0, 3, n))
-    else:
-        q = rng.choice(n_seq, 40, replace=False)[rng.integers(0, 40, n)]
-    t = rng.integers(0, n_seq, n)
-    qs = rng.integers(0, 5000, n); qe = qs + rng.integers(1, 5000, n)
-    ts = rng.integers(0, 5000, n); te = ts + rng.integers(1, 5000, n)
-    bl = rng.integers(1, 6000, n)
-    h = np.zeros(n, dtype=ma.HIT_DT)
-    h["qns"] = (q.astype(np.uint64) << np.uint64(32)) | qs.astype(np.uint64)
-    h["qe"] = qe.astype(np.uint32); h["tn"] = t.astype(np.uint32); h["ts"] = ts.astype(np.uint32); h["te"] = te.astype(np.uint32)
-    h["mlrev"] = (bl * 9 // 10).astype(np.uint32); h["bldel"] = bl.astype(np.uint32)
+    h = ST.sparse_id_hits(n_seq, n, where)
     opt = ma.default_opt()
     opt.min_dp = 1
     orc = ST.orc_stages(h, n_seq, opt)
