@@ -11,22 +11,28 @@ Workload: BASELINE.json configs[3] -- synthetic 100M-overlap PAF, 2M reads, logn
 data set is used at every N (strong scaling): at N>1 (launched by torch.distributed.run, one rank per GPU) the hits are
 sharded by query-read range, sub / flag arrays and the arc blocks are exchanged over RCCL, rank 0 finishes the graph.
 
-In the same run (rank 0, N=1): the unmodified reference miniasm on the SAME file (cpu_baseline, and its GFA is compared with
-ours: gfa_identical), the CLI end to end (process start -> GFA on disk), the text-resident variant (device-side parse inside
-the step), BASELINE configs[1] (10M overlaps) and a tie-rich input as secondary legs.
+A plain run does only what the headline needs: it generates its input afresh (never reusing an earlier run's file), brings it
+into HBM, warms up, times the steps, writes --dump-outputs and prints the line.  With --full the same run also measures and
+checks everything else (rank 0, N=1): the unmodified reference miniasm on the SAME file (cpu_baseline, and its GFA is compared
+with ours: gfa_identical), per-kernel HIP-event times and the roofline (instrumented steps of their own), one-input latency,
+the CLI end to end (process start -> GFA on disk), the text-resident variant (device-side parse inside the step),
+BASELINE configs[1] (10M overlaps), configs[4] by digest and a tie-rich input as secondary legs.
 
 One JSON line on stdout (rank 0): the figures without their prose and without the secondary legs' tables (compact_line); the full
 record goes to <workdir>/bench_<workload>_full.json, named in the line's `full_record`.  --dump-outputs DIR writes the GFA of the last
 timed step as .npy arrays (dump_outputs), so that two builds can be compared output for output on the same seeded input.
 """
 import argparse
+import atexit
 import ctypes as C
 import hashlib
 import json
 import os
 import re
+import shutil
 import subprocess
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -49,15 +55,27 @@ def gen_paf(path, reads, lines, seed, extra=()):
     return path
 
 
-def count_lines(path):
-    n = 0
-    with open(path, "rb") as f:  # pafgen writes one overlap per line, newline-terminated
-        while True:
-            blk = f.read(64 << 20)
-            if not blk:
-                break
-            n += blk.count(b"\n")
-    return n
+def count_lines(path, workers=8):
+    """newlines in the file (pafgen writes one overlap per line, newline-terminated), `workers` byte ranges counted at once
+    (file reads and numpy's compare run without the GIL)"""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    size = os.path.getsize(path)
+    span = max(-(-size // workers), 1)
+
+    def count(beg):
+        n, left, buf = 0, min(span, size - beg), bytearray(16 << 20)
+        with open(path, "rb", buffering=0) as f:
+            f.seek(beg)
+            while left > 0:
+                got = f.readinto(memoryview(buf)[:min(len(buf), left)])
+                if not got:
+                    break
+                n += int(np.count_nonzero(np.frombuffer(buf, np.uint8, got) == 10))
+                left -= got
+        return n
+    with ThreadPoolExecutor(workers) as ex:
+        return sum(ex.map(count, range(0, size, span)))
 
 
 def md5_pair(data):
@@ -412,16 +430,18 @@ def main():
     ap.add_argument("--model", default="lognormal", choices=["lognormal", "fixed", "uniform"])
     ap.add_argument("--grid", type=int, default=0, help="pafgen -q: coordinates on a grid -> equal sort keys (tie-rich input; not the BASELINE workload)")
     ap.add_argument("--workdir", default=os.environ.get("MA_BENCH_DIR", "/tmp/ma_bench"))
-    ap.add_argument("--no-cpu", action="store_true", help="skip the reference run (no cpu_baseline, no gfa_identical)")
-    ap.add_argument("--no-text", action="store_true", help="skip the text-resident leg (device-side parse inside the step)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (cfg2, tie-rich input, CLI end to end)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the command-line legs, the reference run on the same file (cpu_baseline, gfa_identical), "
+                    "per-kernel times and the roofline (--prof-steps), latency, the text-resident leg and the secondary legs; the --no-* and leg options below narrow it")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the reference run (no cpu_baseline, no gfa_identical)")
+    ap.add_argument("--no-text", action="store_true", help="--full without the text-resident leg (device-side parse inside the step)")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the secondary legs (cfg2, tie-rich input, CLI end to end)")
     ap.add_argument("--no-overlap", action="store_true", help="run each pass's host tail before the next pass's device part starts")
     ap.add_argument("--tail-one-stage", action="store_true", help="A/B: the tail of a batch (device part, then text) on ONE worker thread, as in round 5; default: two stages on two threads")
     ap.add_argument("--no-tail-ctx", action="store_true", help="keep the latency-bound rest of a batch (cleaners, unitigs, downloads) on the context that runs the hit passes.  "
                     "Default: it moves to a second context on the same GPU and runs beside the next batch's hit passes (mahip_tail_handoff; round 3, measured: "
                     "cfg4 20.0 -> 19.2 ms per step, cfg2 3.23 -> 2.79 ms)")
-    ap.add_argument("--prof-steps", type=int, default=3)
-    ap.add_argument("--legs", default="cfg2,tie_rich,graph_heavy,latency,e2e,cfg5,realistic", help="which secondary legs to run (comma list)")
+    ap.add_argument("--prof-steps", type=int, default=3, help="--full: instrumented steps for the per-kernel times")
+    ap.add_argument("--legs", default="cfg2,tie_rich,graph_heavy,latency,e2e,cfg5,realistic", help="--full: which secondary legs to run (comma list)")
     ap.add_argument("--graph-heavy-lines", type=int, default=100000000, help="overlaps of the graph-heavy leg (pafgen -L fixed, 50 lines per read); 0 = skip it")
     ap.add_argument("--inflight", type=int, default=1, help="experiment: batches in flight on the one GPU (each on its own context and host thread)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the GFA of the last timed step to DIR as .npy arrays (dump_outputs)")
@@ -429,7 +449,7 @@ def main():
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
     args.tail_ctx = not args.no_tail_ctx
-    want_leg = lambda name: not args.no_legs and name in args.legs.split(",")
+    want_leg = lambda name: args.full and not args.no_legs and name in args.legs.split(",")
     args.gen_extra = ([] if args.model == "lognormal" else ["-L", args.model]) + (["-q", str(args.grid), "-d", "0.3", "-x", "0.03"] if args.grid else [])
     cfg_name = {(2000000, 100000000, 2, "lognormal"): "cfg4", (200000, 10000000, 1, "lognormal"): "cfg2"}.get((args.reads, args.lines, args.seed, args.model), "custom")
 
@@ -452,24 +472,36 @@ def main():
         dist.init_process_group(backend="gloo")
     if not torch.cuda.is_available():
         sys.exit("bench.py needs a GPU (the product has no CPU path)")
-    torch.cuda.set_device(local)
     os.makedirs(args.workdir, exist_ok=True)
     if not os.path.exists(ma.LIB_PATH):
         if rank == 0:
             ma.build()
         if world > 1:
             dist.barrier()
+
+    t0 = time.perf_counter()
+    paf_name = "w_%s%s_r%d_n%d_s%d.paf" % (args.model, "_q%d" % args.grid if args.grid else "", args.reads, args.lines, args.seed)
+    gen, run_dir = None, None
+    if args.full:  # the text an earlier --full run of this configuration left in the work directory is used again (the legs below read it too)
+        paf = os.path.join(args.workdir, paf_name)
+        if rank == 0:
+            gen_paf(paf, args.reads, args.lines, args.seed, args.gen_extra)
+        if world > 1:
+            dist.barrier()
+        t_gen = time.perf_counter() - t0
+    else:  # a plain run writes its text afresh, into a directory of its own, while this process sets up the GPU
+        box = [tempfile.mkdtemp(prefix="run_", dir=args.workdir) if rank == 0 else None]
+        if world > 1:
+            dist.broadcast_object_list(box, src=0)
+        run_dir, paf = box[0], os.path.join(box[0], paf_name)
+        if rank == 0:
+            atexit.register(shutil.rmtree, run_dir, True)
+            gen = subprocess.Popen([ma.PAFGEN_PATH, "-r", str(args.reads), "-n", str(args.lines), "-s", str(args.seed), "-o", paf] + args.gen_extra, stderr=subprocess.DEVNULL)
+            atexit.register(lambda: gen.poll() is None and gen.kill())  # (runs before the rmtree)
+    torch.cuda.set_device(local)
     L = ma.lib()
     L.ma_set_log_path(b"/dev/null")
     L.sys_init()
-
-    t0 = time.perf_counter()
-    paf = os.path.join(args.workdir, "w_%s%s_r%d_n%d_s%d.paf" % (args.model, "_q%d" % args.grid if args.grid else "", args.reads, args.lines, args.seed))
-    if rank == 0:
-        gen_paf(paf, args.reads, args.lines, args.seed, args.gen_extra)
-    if world > 1:
-        dist.barrier()
-    t_gen = time.perf_counter() - t0
     opt = ma.default_opt()
 
     # ---- the command-line legs FIRST, while this process holds no device memory: a process that starts beside 30 GB of another process's buffers -- or right after they
@@ -519,8 +551,20 @@ def main():
                 box[0] = idb.raw
             dist.broadcast_object_list(box, src=0)
             ma._chk(L.mahip_comm_init(ctx.h, box[0], rank, world), "comm_init")
-    want_text = rank == 0 and world == 1 and not args.no_text
+    if gen:
+        if gen.wait() != 0:
+            raise RuntimeError("pafgen failed (exit status %d)" % gen.returncode)
+    if run_dir:
+        if world > 1:
+            dist.barrier()
+        t_gen = time.perf_counter() - t0
+    want_text = args.full and rank == 0 and world == 1 and not args.no_text
     W = Workload(ma, L, ctx, paf, opt, world, rank, keep_text=want_text)
+    if run_dir:  # the text is in HBM: nothing reads the file again (and its pages are not written back while the steps run)
+        if world > 1:
+            dist.barrier()
+        if rank == 0:
+            shutil.rmtree(run_dir, True)
     if rank == 0:
         log("workload %s: %d lines (%.2f GB text), %d stored hits (%d on this rank), %d reads; gen %.1fs, file->HBM %.3fs (%.1f GB/s), parse+dictionary %.3fs" % (
             cfg_name, W.n_lines, W.size / 1e9, W.n_all, W.n_my, W.n_seq, t_gen, W.t_load, W.size / W.t_load / 1e9, W.t_parse))
@@ -755,105 +799,105 @@ def main():
     tie = ctx.tie_stats() if rank == 0 else None
 
     # ---- per-kernel timing with HIP events on the launch stream (separate, instrumented steps)
-    roof, kernels = None, []
-    if rank == 0:
-        ctx.prof_enable(True)
-        ctx.prof_reset()
-    if world > 1:
-        L.ma_shard_phases(1)
-        run.head_wall, run.tail_wall = [], []
-    for _ in range(args.prof_steps):  # a step is collective in the sharded mode: EVERY rank runs it, rank 0 is the one instrumented
-        run.step()
-        run.fence()  # an instrumented step runs ALONE: with the previous pass's device tail on the second context beside it, whichever kernel it lands on is stretched by several ms (round 6: k_asg_trans 10.4 instead of 2.5 ms)
-    phases = None
-    if world > 1:  # where a sharded step spends its time: device time per phase (HIP events between the phases of host/sharded.c), maximum over the ranks
-        L.ma_shard_phases(0)
-        stt = run.last_stats
-        mine = [float(x) for x in stt.phase_ms] + [sum(run.head_wall) / max(len(run.head_wall), 1) * 1e3]
-        tmax = torch.tensor(mine, dtype=torch.float64)
-        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        tmin = torch.tensor(mine, dtype=torch.float64)
-        dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
+    roof, kernels, phases = None, [], None
+    if args.full:
         if rank == 0:
-            names = ma.SHARD_PHASE_NAMES
-            dev_sum = float(sum(tmax[:len(names)]))
-            phases = {"what": "one sharded head (the last instrumented step): device time between the phase marks of host/sharded.c, max over ranks [min]; x:* = exchanges",
-                      "phase_ms": {n: [round(float(tmax[i]), 4), round(float(tmin[i]), 4)] for i, n in enumerate(names)},
-                      "exchange_bytes_per_rank": {names[i]: int(stt.xchg_bytes[i]) for i in range(len(names)) if stt.xchg_bytes[i]},
-                      "device_ms_sum_of_max": round(dev_sum, 4), "head_wall_ms_max": round(float(tmax[-1]), 4), "head_wall_ms_min": round(float(tmin[-1]), 4),
-                      "host_wait_ms": round(float(tmax[-1]) - dev_sum, 4),
-                      "rank0_tail_wall_ms": round(sum(run.tail_wall) / max(len(run.tail_wall), 1) * 1e3, 4) if run.tail_wall else None,
-                      "rank0_tail_where": "second context + worker thread, beside the next step's head" if run.ctx2 else "same context, after the head"}
-    if rank == 0:
-        recs = ctx.prof_get()
-        ctx.prof_enable(False)
-        pmc, pmc_src = pmc_profile(cfg_name)
-        kernels = kernel_table(recs, args.prof_steps)
-        for k in kernels:
-            tr = pmc_traffic(pmc, k["name"])
-            # the bytes the launch really moved (rocprofv3 PMC profile of this command) / this run's launch time: cannot exceed the peak
-            k["counter_GBs"] = round(tr / (k["avg_ms"] * 1e-3) / 1e9, 1) if tr and k["avg_ms"] > 0 else None
-            k["frac_counter"] = round(k["counter_GBs"] / HBM_PEAK_GBS, 4) if k["counter_GBs"] else None  # the fraction to read: bytes the launch moved / its time / peak
-            if k.get("alg_GBs") and k["alg_GBs"] > HBM_PEAK_GBS:
-                k["alg_GBs_is_accounting"] = "SURVEY 8(d) bytes of the reference passes this fused launch replaces, not bytes it moved: read frac_counter" 
-        dom = next((k for k in kernels if k["alg_GBs"]), None)
-        if dom:
-            traffic = pmc_traffic(pmc, dom["name"])
-            roof = {"bound": "hbm", "kernel": dom["name"], "achieved": dom["alg_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(dom["alg_GBs"] / HBM_PEAK_GBS, 4), "traffic": traffic,
-                    "traffic_source": pmc_src and "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; not measured in this run)" % pmc_src,
-                    # the same kernel priced by the bytes it really moved: a fused kernel cannot exceed 1 here
-                    "frac_counter": round(traffic / (dom["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
-                    "avg_launch_ms": dom["avg_ms"], "launches_per_step": dom["launches_per_step"],
-                    "note": "achieved = SURVEY 8(d) algorithmic bytes of the reference passes this kernel replaces (k_hit_sub<gather>: hit sort 64 + ma_hit_sub 48 B per stored hit) / HIP-event launch time"}
-            # the sort + first coverage pass as a group: ALL kernels that make up the reference's hit sort + first ma_hit_sub, priced at 8(d)'s 64 + 48 B per hit
-            grp = [k for k in kernels if k["name"] in SORT_GROUP]
-            grp_ms = sum(k["avg_ms"] * k["launches_per_step"] for k in grp)
-            if grp_ms > 0:
-                grp_tr = [pmc_traffic(pmc, k["name"]) for k in grp]
-                grp_bytes = 112.0 * float(W.n_my)
-                grp_traffic = round(sum(t * k["launches_per_step"] for t, k in zip(grp_tr, grp))) if all(t is not None for t in grp_tr) else None
-                roof["sort_group"] = {"kernels": [k["name"] for k in grp], "ms_per_step": round(grp_ms, 4), "alg_bytes_per_step": grp_bytes,
-                                      "achieved": round(grp_bytes / (grp_ms * 1e-3) / 1e9, 1), "frac": round(grp_bytes / (grp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                      "traffic": grp_traffic}
-                # THE HEADLINE (round-4 review, What's weak #2): the reference's hit sort + first ma_hit_sub are done here by several kernels (keys, histograms, scatters, the
-                # gathering coverage sweep); billing the sweep alone with the whole 64 + 48 B per hit flatters it.  `roofline` is therefore the GROUP -- all of those
-                # launches together, one "launch" = one pass of the group over the input -- and the single kernel stays beside it as `dominant_kernel`.
-                single = {k: roof[k] for k in ("kernel", "achieved", "frac", "traffic", "frac_counter", "avg_launch_ms", "launches_per_step", "note")}
-                roof.update({"kernel": "sort group = " + " + ".join("%s x%g" % (k["name"], k["launches_per_step"]) for k in grp),
-                             "achieved": roof["sort_group"]["achieved"], "frac": roof["sort_group"]["frac"], "traffic": grp_traffic,
-                             "frac_counter": round(grp_traffic / (grp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if grp_traffic else None,
-                             "avg_launch_ms": round(grp_ms, 4), "launches_per_step": 1,
-                             "note": "achieved = SURVEY 8(d) algorithmic bytes of the reference passes the group replaces (hit sort 64 + first ma_hit_sub 48 B per stored hit) x stored hits / "
-                                     "sum of the HIP-event launch times of the group's kernels in one step",
-                             "dominant_kernel": single})
-            # what this GPU sustained for plain access patterns with known byte counts (csrc/diag.hip, tools/pmc_calibrate.py): the rate `frac_counter` is to be read against
-            ach = achievable_rates()
-            if ach:
-                roof["achievable"] = ach
-            # What THIS design of the sort group can reach at best: every kernel's counted traffic (the committed PMC profile of this command) at the rate this GPU sustained for that
-            # kernel's access pattern with known byte counts (csrc/diag.hip).  It is a ceiling of the design, not of the hardware: the group moves about twice SURVEY 8(d)'s bytes
-            # (keys are made from whole records, three digit passes read the keys twice and write them once, a mirrored record costs a 128-byte line for 32 bytes), so 0.5 of the
-            # 8 TB/s peak by 8(d) bytes would need the group's traffic at more than the box streams.
-            if ach and grp_ms > 0 and all(t is not None for t in grp_tr):
-                pat = {"k_hit_keys": "keys_from_records", "k_radix_hist": "stream_read", "k_radix_colscan": "stream_read", "k_radix_scatter": "radix_scatter_runs", "k_runs_expand": "copy",
-                       "k_hit_goff": "copy", "k_group_close": "copy"}
-                line_rate = 6000.0  # GB/s of 128-byte LINES the random-record gather sustained (diag.hip: gather32+cols, 2.16 TB/s of useful bytes = 160 B moved per 64 useful)
-                c_ms, parts = 0.0, {}
-                for t, k in zip(grp_tr, grp):
-                    rate = line_rate if k["name"] == "k_hit_sub<gather>" else ach.get(pat.get(k["name"], "copy"), 5500.0)
-                    ms = t * k["launches_per_step"] / (rate * 1e9) * 1e3
-                    parts[k["name"]] = round(ms, 3)
-                    c_ms += ms
-                roof["ceiling"] = {"ms_per_step": round(c_ms, 3), "frac": round(grp_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "per_kernel_ms": parts,
-                                   "what": "the sort group's counted traffic at the rates this GPU sustained for each kernel's access pattern (csrc/diag.hip, profiles/r04_diag_patterns.json): "
-                                           "what this design can reach by SURVEY 8(d) bytes; the measured `frac` stands against THIS, 0.5 is out of its reach"}
-            # the whole hit chain by the same accounting: SURVEY 8(d) sums the reference's passes to 584 B per stored hit
-            chain_bytes = 584.0 * float(W.n_my)
-            step_s = dt / args.steps
-            roof["hit_chain"] = {"alg_bytes_per_step": chain_bytes, "achieved": round(chain_bytes / step_s / 1e9, 1), "unit": "GB/s",
-                                 "frac": round(chain_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4),
-                                 "note": "584 B per stored hit (SURVEY 8(d), sum over the reference's passes) x hits of this rank / measured step time"}
+            ctx.prof_enable(True)
+            ctx.prof_reset()
+        if world > 1:
+            L.ma_shard_phases(1)
+            run.head_wall, run.tail_wall = [], []
+        for _ in range(args.prof_steps):  # a step is collective in the sharded mode: EVERY rank runs it, rank 0 is the one instrumented
+            run.step()
+            run.fence()  # an instrumented step runs ALONE: with the previous pass's device tail on the second context beside it, whichever kernel it lands on is stretched by several ms (round 6: k_asg_trans 10.4 instead of 2.5 ms)
+        if world > 1:  # where a sharded step spends its time: device time per phase (HIP events between the phases of host/sharded.c), maximum over the ranks
+            L.ma_shard_phases(0)
+            stt = run.last_stats
+            mine = [float(x) for x in stt.phase_ms] + [sum(run.head_wall) / max(len(run.head_wall), 1) * 1e3]
+            tmax = torch.tensor(mine, dtype=torch.float64)
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            tmin = torch.tensor(mine, dtype=torch.float64)
+            dist.all_reduce(tmin, op=dist.ReduceOp.MIN)
+            if rank == 0:
+                names = ma.SHARD_PHASE_NAMES
+                dev_sum = float(sum(tmax[:len(names)]))
+                phases = {"what": "one sharded head (the last instrumented step): device time between the phase marks of host/sharded.c, max over ranks [min]; x:* = exchanges",
+                          "phase_ms": {n: [round(float(tmax[i]), 4), round(float(tmin[i]), 4)] for i, n in enumerate(names)},
+                          "exchange_bytes_per_rank": {names[i]: int(stt.xchg_bytes[i]) for i in range(len(names)) if stt.xchg_bytes[i]},
+                          "device_ms_sum_of_max": round(dev_sum, 4), "head_wall_ms_max": round(float(tmax[-1]), 4), "head_wall_ms_min": round(float(tmin[-1]), 4),
+                          "host_wait_ms": round(float(tmax[-1]) - dev_sum, 4),
+                          "rank0_tail_wall_ms": round(sum(run.tail_wall) / max(len(run.tail_wall), 1) * 1e3, 4) if run.tail_wall else None,
+                          "rank0_tail_where": "second context + worker thread, beside the next step's head" if run.ctx2 else "same context, after the head"}
+        if rank == 0:
+            recs = ctx.prof_get()
+            ctx.prof_enable(False)
+            pmc, pmc_src = pmc_profile(cfg_name)
+            kernels = kernel_table(recs, args.prof_steps)
+            for k in kernels:
+                tr = pmc_traffic(pmc, k["name"])
+                # the bytes the launch really moved (rocprofv3 PMC profile of this command) / this run's launch time: cannot exceed the peak
+                k["counter_GBs"] = round(tr / (k["avg_ms"] * 1e-3) / 1e9, 1) if tr and k["avg_ms"] > 0 else None
+                k["frac_counter"] = round(k["counter_GBs"] / HBM_PEAK_GBS, 4) if k["counter_GBs"] else None  # the fraction to read: bytes the launch moved / its time / peak
+                if k.get("alg_GBs") and k["alg_GBs"] > HBM_PEAK_GBS:
+                    k["alg_GBs_is_accounting"] = "SURVEY 8(d) bytes of the reference passes this fused launch replaces, not bytes it moved: read frac_counter" 
+            dom = next((k for k in kernels if k["alg_GBs"]), None)
+            if dom:
+                traffic = pmc_traffic(pmc, dom["name"])
+                roof = {"bound": "hbm", "kernel": dom["name"], "achieved": dom["alg_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(dom["alg_GBs"] / HBM_PEAK_GBS, 4), "traffic": traffic,
+                        "traffic_source": pmc_src and "%s (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command; not measured in this run)" % pmc_src,
+                        # the same kernel priced by the bytes it really moved: a fused kernel cannot exceed 1 here
+                        "frac_counter": round(traffic / (dom["avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic else None,
+                        "avg_launch_ms": dom["avg_ms"], "launches_per_step": dom["launches_per_step"],
+                        "note": "achieved = SURVEY 8(d) algorithmic bytes of the reference passes this kernel replaces (k_hit_sub<gather>: hit sort 64 + ma_hit_sub 48 B per stored hit) / HIP-event launch time"}
+                # the sort + first coverage pass as a group: ALL kernels that make up the reference's hit sort + first ma_hit_sub, priced at 8(d)'s 64 + 48 B per hit
+                grp = [k for k in kernels if k["name"] in SORT_GROUP]
+                grp_ms = sum(k["avg_ms"] * k["launches_per_step"] for k in grp)
+                if grp_ms > 0:
+                    grp_tr = [pmc_traffic(pmc, k["name"]) for k in grp]
+                    grp_bytes = 112.0 * float(W.n_my)
+                    grp_traffic = round(sum(t * k["launches_per_step"] for t, k in zip(grp_tr, grp))) if all(t is not None for t in grp_tr) else None
+                    roof["sort_group"] = {"kernels": [k["name"] for k in grp], "ms_per_step": round(grp_ms, 4), "alg_bytes_per_step": grp_bytes,
+                                          "achieved": round(grp_bytes / (grp_ms * 1e-3) / 1e9, 1), "frac": round(grp_bytes / (grp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                          "traffic": grp_traffic}
+                    # THE HEADLINE (round-4 review, What's weak #2): the reference's hit sort + first ma_hit_sub are done here by several kernels (keys, histograms, scatters, the
+                    # gathering coverage sweep); billing the sweep alone with the whole 64 + 48 B per hit flatters it.  `roofline` is therefore the GROUP -- all of those
+                    # launches together, one "launch" = one pass of the group over the input -- and the single kernel stays beside it as `dominant_kernel`.
+                    single = {k: roof[k] for k in ("kernel", "achieved", "frac", "traffic", "frac_counter", "avg_launch_ms", "launches_per_step", "note")}
+                    roof.update({"kernel": "sort group = " + " + ".join("%s x%g" % (k["name"], k["launches_per_step"]) for k in grp),
+                                 "achieved": roof["sort_group"]["achieved"], "frac": roof["sort_group"]["frac"], "traffic": grp_traffic,
+                                 "frac_counter": round(grp_traffic / (grp_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if grp_traffic else None,
+                                 "avg_launch_ms": round(grp_ms, 4), "launches_per_step": 1,
+                                 "note": "achieved = SURVEY 8(d) algorithmic bytes of the reference passes the group replaces (hit sort 64 + first ma_hit_sub 48 B per stored hit) x stored hits / "
+                                         "sum of the HIP-event launch times of the group's kernels in one step",
+                                 "dominant_kernel": single})
+                # what this GPU sustained for plain access patterns with known byte counts (csrc/diag.hip, tools/pmc_calibrate.py): the rate `frac_counter` is to be read against
+                ach = achievable_rates()
+                if ach:
+                    roof["achievable"] = ach
+                # What THIS design of the sort group can reach at best: every kernel's counted traffic (the committed PMC profile of this command) at the rate this GPU sustained for that
+                # kernel's access pattern with known byte counts (csrc/diag.hip).  It is a ceiling of the design, not of the hardware: the group moves about twice SURVEY 8(d)'s bytes
+                # (keys are made from whole records, three digit passes read the keys twice and write them once, a mirrored record costs a 128-byte line for 32 bytes), so 0.5 of the
+                # 8 TB/s peak by 8(d) bytes would need the group's traffic at more than the box streams.
+                if ach and grp_ms > 0 and all(t is not None for t in grp_tr):
+                    pat = {"k_hit_keys": "keys_from_records", "k_radix_hist": "stream_read", "k_radix_colscan": "stream_read", "k_radix_scatter": "radix_scatter_runs", "k_runs_expand": "copy",
+                           "k_hit_goff": "copy", "k_group_close": "copy"}
+                    line_rate = 6000.0  # GB/s of 128-byte LINES the random-record gather sustained (diag.hip: gather32+cols, 2.16 TB/s of useful bytes = 160 B moved per 64 useful)
+                    c_ms, parts = 0.0, {}
+                    for t, k in zip(grp_tr, grp):
+                        rate = line_rate if k["name"] == "k_hit_sub<gather>" else ach.get(pat.get(k["name"], "copy"), 5500.0)
+                        ms = t * k["launches_per_step"] / (rate * 1e9) * 1e3
+                        parts[k["name"]] = round(ms, 3)
+                        c_ms += ms
+                    roof["ceiling"] = {"ms_per_step": round(c_ms, 3), "frac": round(grp_bytes / (c_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "per_kernel_ms": parts,
+                                       "what": "the sort group's counted traffic at the rates this GPU sustained for each kernel's access pattern (csrc/diag.hip, profiles/r04_diag_patterns.json): "
+                                               "what this design can reach by SURVEY 8(d) bytes; the measured `frac` stands against THIS, 0.5 is out of its reach"}
+                # the whole hit chain by the same accounting: SURVEY 8(d) sums the reference's passes to 584 B per stored hit
+                chain_bytes = 584.0 * float(W.n_my)
+                step_s = dt / args.steps
+                roof["hit_chain"] = {"alg_bytes_per_step": chain_bytes, "achieved": round(chain_bytes / step_s / 1e9, 1), "unit": "GB/s",
+                                     "frac": round(chain_bytes / step_s / 1e9 / HBM_PEAK_GBS, 4),
+                                     "note": "584 B per stored hit (SURVEY 8(d), sum over the reference's passes) x hits of this rank / measured step time"}
     run.close()
 
     # ---- one input at a time: device + host latency of a single batch (no second context, no overlap with a neighbour): `ms_per_step` above is a
@@ -907,7 +951,7 @@ def main():
 
     # ---- secondary legs (rank 0, one GPU)
     legs = {}
-    if rank == 0 and world == 1 and not args.no_legs:
+    if args.full and rank == 0 and world == 1 and not args.no_legs:
         def leg(name, reads, lines, seed, extra, steps, with_ref, prof_steps=0, gold_name=None):
             try:
                 p = gen_paf(os.path.join(args.workdir, "leg_%s_r%d_n%d_s%d.paf" % (name, reads, lines, seed)), reads, lines, seed, extra)
@@ -981,7 +1025,7 @@ def main():
 
     # ---- the reference on the same file: CPU baseline + the GFA every output above is compared with
     cpu, parity, e2e = None, None, None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         try:
             ref = run_reference(paf, os.path.join(args.workdir, "ref_%s.gfa" % cfg_name))
             if ref:
@@ -994,7 +1038,7 @@ def main():
                        "end_to_end_s": ref["wall"]}
         except Exception as e:  # the baseline is a reported number, never a reason to lose the bench line
             log("cpu baseline failed:", e)
-    if rank == 0 and world > 1:  # N ranks: no reference run here (65 s at cfg4), but the N = 1 run of the same work directory left its GFA behind
+    if args.full and rank == 0 and world > 1:  # N ranks: no reference run here (65 s at cfg4), but the N = 1 run of the same work directory left its GFA behind
         try:
             ref_path = os.path.join(args.workdir, "ref_%s.gfa" % cfg_name)
             if os.path.exists(ref_path) and os.path.getmtime(ref_path) >= os.path.getmtime(paf):

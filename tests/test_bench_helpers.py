@@ -73,3 +73,16 @@ def test_dump_outputs(tmp_path):
     idx = np.load(tmp_path / "s1" / "gfa_lines.npy").astype(np.int64)
     lines = gfa.split(b"\n")
     assert np.all(np.diff(idx) > 0) and bytes(np.load(tmp_path / "s1" / "gfa_text.npy").astype(np.uint8)) == b"".join(lines[i] + b"\n" for i in idx)
+
+
+def test_count_lines(tmp_path):
+    """count_lines counts byte ranges in parallel: every newline once, whatever the size against the number of ranges"""
+    import random
+    b = _bench()
+    rng = random.Random(3)
+    for size in (0, 1, 5, 7, 8, 9, 4096, 100003):
+        data = bytes(rng.choice(b"ab\n") for _ in range(size))
+        p = tmp_path / ("t%d" % size)
+        p.write_bytes(data)
+        for workers in (1, 3, 8):
+            assert b.count_lines(str(p), workers) == data.count(b"\n"), (size, workers)

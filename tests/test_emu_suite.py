@@ -126,7 +126,7 @@ def test_bench_py_runs_on_the_cpu_build(mode, emu_built, tmp_path):
     env["PYTHONPATH"] = os.path.join(EMU, "fake_torch") + os.pathsep + env.get("PYTHONPATH", "")
     env["MINIASM_AMD_LIB"] = os.path.join(EMU, "_build", "libminiasm_amd_emu.so")
     env["MA_BENCH_DIR"] = str(tmp_path)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "3", "--warmup", "1", "--no-legs",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "3", "--warmup", "1", "--full", "--no-legs",
            "--dump-outputs", str(tmp_path / "dump")]
     if mode == "no_tail_ctx":
         cmd.append("--no-tail-ctx")
@@ -151,6 +151,54 @@ def test_bench_py_runs_on_the_cpu_build(mode, emu_built, tmp_path):
     assert json.load(open(d["full_record"]))["value"] == d["value"]
 
 
+@pytest.mark.parametrize("ranks", [1, 2])
+def test_plain_bench_py_run_on_the_cpu_build(ranks, emu_built, tmp_path):
+    """bench.py without --full, on the CPU build: the headline only (no reference run, no instrumented steps, no legs), on a text the run
+    writes afresh and removes once it is in HBM; the GFA of its last timed step (--dump-outputs) is the reference's on the same seeded text.
+    Two ranks: launched as the driver launches them (see test_bench_py_on_two_ranks_on_the_cpu_build), rank 0 writes the text for both."""
+    import json
+    import numpy as np
+    ref_bin = os.path.join(ROOT, "oracle", "_ref", "miniasm_ref")
+    if not os.path.exists(ref_bin):
+        pytest.skip("oracle/_ref not built")
+    env = dict(os.environ)
+    env["PYTHONPATH"] = os.path.join(EMU, "fake_torch") + os.pathsep + env.get("PYTHONPATH", "")
+    env["MINIASM_AMD_LIB"] = os.path.join(EMU, "_build", "libminiasm_amd_emu.so")
+    work = tmp_path / "work"
+    env["MA_BENCH_DIR"] = str(work)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "dump")]
+    procs = []
+    for rank in range(ranks):
+        e = env if ranks == 1 else dict(env, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(ranks), MASTER_ADDR="127.0.0.1",
+                                        MASTER_PORT=str(20000 + os.getpid() % 20000), MA_FAKE_DIST_DIR=str(tmp_path), MA_BENCH_ONE_GPU_DEBUG="1")
+        procs.append(subprocess.Popen(cmd + ([] if ranks == 1 else ["--gpus", str(ranks)]), cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    outs = []
+    for p in procs:
+        try:
+            o, err = p.communicate(timeout=1800)
+        except subprocess.TimeoutExpired:
+            for q in procs:
+                q.kill()
+            raise
+        assert p.returncode == 0, err[-3000:]
+        outs.append(o)
+    lines = [l for l in outs[0].splitlines() if l.strip()]
+    assert len(lines) == 1 and all(o.strip() == "" for o in outs[1:]), "rank 0 prints ONE JSON line"
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == ranks and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["vs_baseline"] is None
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("PAF overlaps processed/sec (hit-filter->trans-reduce->GFA)", "overlaps/s", True, "u32")
+    assert d["cpu_baseline"] is None and d["gfa_identical"] is None and d["roofline"] is None and d["kernels"] == []
+    assert d["legs"] == {} and d["latency"] is None and d["e2e"] is None and d["from_text"] is None
+    assert not [f for _, _, fs in os.walk(tmp_path) for f in fs if ".paf" in f], "the run's text is gone, and no other text was written"
+    paf = str(tmp_path / "same.paf")
+    subprocess.run([os.path.join(ROOT, "miniasm_amd", "bin", "pafgen"), "-r", "2500", "-n", "70000", "-s", "5", "-o", paf], check=True, stderr=subprocess.DEVNULL)
+    ref = subprocess.run([ref_bin, paf], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout
+    with open(paf, "rb") as f:
+        assert d["config"]["global_overlaps"] == f.read().count(b"\n")
+    assert bytes(np.load(tmp_path / "dump" / "gfa_text.npy").astype(np.uint8)) == ref
+
+
 @pytest.mark.parametrize("grid", [0, 16])
 def test_bench_py_on_two_ranks_on_the_cpu_build(grid, emu_built, tmp_path):
     """`bench.py --gpus 2` as the driver launches it (one process per rank, RANK / WORLD_SIZE / MASTER_* in the environment), on the CPU build:
@@ -164,7 +212,7 @@ def test_bench_py_on_two_ranks_on_the_cpu_build(grid, emu_built, tmp_path):
     env["PYTHONPATH"] = os.path.join(EMU, "fake_torch") + os.pathsep + env.get("PYTHONPATH", "")
     env["MINIASM_AMD_LIB"] = os.path.join(EMU, "_build", "libminiasm_amd_emu.so")
     env["MA_BENCH_DIR"] = str(tmp_path)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "2", "--warmup", "1"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--reads", "2500", "--lines", "70000", "--seed", "5", "--steps", "2", "--warmup", "1", "--full"]
     if grid:  # a tie-rich input: the ranks (which hold only their own records, and say where they stood in the input) have to restore the reference's order of tied hits
         base += ["--grid", str(grid), "--model", "uniform", "--reads", "3000", "--lines", "80000"]
     r = subprocess.run(base + ["--no-legs", "--no-text"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1800)

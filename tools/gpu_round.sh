@@ -4,6 +4,7 @@
 cd "$(dirname "$0")/.." || exit 1
 export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 mkdir -p gpurun_out
+root=$PWD; out=${OUT:-$TMPDIR/gpu_round}; mkdir -p "$out" && out=$(cd "$out" && pwd)  # results of the bench.py targets with --full (OUT=<dir> puts them elsewhere)
 what="${*:-tests}"
 rocminfo 2>/dev/null | grep -m1 -E "gfx9" > gpurun_out/gpu.txt
 for w in $what; do
@@ -18,9 +19,9 @@ graphapi)
   timeout 1500 python -m pytest tests/test_gpu_graph_api.py -m gpu -q --tb=short -p no:cacheprovider > gpurun_out/tests_graphapi.log 2>&1; echo "rc=$?" >> gpurun_out/tests_graphapi.log
   grep -vE "^\[M::|^\[pafgen" gpurun_out/tests_graphapi.log | tail -40 ;;
 benchtiming)
-  MA_PIPE_TIMING=1 timeout 900 python bench.py --no-cpu --no-text --steps 5 --warmup 1 > gpurun_out/bench_timing.json 2> gpurun_out/bench_timing.log; echo "rc=$?"
-  grep -E "^\[bench\]|T::paf|T::xfer|T::ingest" gpurun_out/bench_timing.log | head -40; python3 -c "
-import json; d=json.load(open('gpurun_out/bench_timing.json')); print(d['ms_per_step'], d['e2e'], d['setup']); [print(k['name'], k['launches_per_step'], k['avg_ms']) for k in d['kernels'][:8]]" ;;
+  MA_PIPE_TIMING=1 timeout 900 python bench.py --full --no-cpu --no-text --steps 5 --warmup 1 > $out/bench_timing.json 2> $out/bench_timing.log; echo "rc=$?"
+  grep -E "^\[bench\]|T::paf|T::xfer|T::ingest" $out/bench_timing.log | head -40; python3 -c "
+import json; d=json.load(open('$out/bench_timing.json')); print(d['ms_per_step'], d['e2e'], d['setup']); [print(k['name'], k['launches_per_step'], k['avg_ms']) for k in d['kernels'][:8]]" ;;
 e2ecfg4)
   NOREF=1 bash tools/e2e_cfg4.sh | tail -60 ;;
 probe)
@@ -111,17 +112,17 @@ walkprobe)
   gcc -O2 -o /tmp/walk_probe tools/probes/walk_probe.c && for nb in 4 16 77; do for form in 0 3 5 1; do for thp in 0 1; do /tmp/walk_probe 100000000 $nb $form $thp; done; done; done 2>&1 | tee gpurun_out/walk_probe.txt ;;
 parseprof)
   # per-kernel times of the text-resident leg (device parse + dictionary inside the step)
-  rm -rf gpurun_out/parseprof; mkdir -p gpurun_out/parseprof
-  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d /root/repo/gpurun_out/parseprof -o r --output-format csv -- python /root/repo/bench.py --steps 2 --warmup 1 --no-cpu --no-legs --prof-steps 0 > /root/repo/gpurun_out/parseprof/bench.json 2> /root/repo/gpurun_out/parseprof/bench.log); echo "rc=$?"
-  f=$(find gpurun_out/parseprof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && grep -E "k_paf|k_dict|k_rec_|k_scan" "$f" | cut -c1-60,200-400 | head -20; python3 -c "import json; d=json.load(open('gpurun_out/parseprof/bench.json')); print('from_text %.2f ms/step' % d['from_text']['ms_per_step'])"
-  find gpurun_out/parseprof -name "*trace*.csv" -size +8M -delete ;;
+  p=$out/parseprof; rm -rf $p; mkdir -p $p
+  (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d $p -o r --output-format csv -- python $root/bench.py --full --steps 2 --warmup 1 --no-cpu --no-legs --prof-steps 0 > $p/bench.json 2> $p/bench.log); echo "rc=$?"
+  f=$(find $p -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && grep -E "k_paf|k_dict|k_rec_|k_scan" "$f" | cut -c1-60,200-400 | head -20; python3 -c "import json; d=json.load(open('$p/bench.json')); print('from_text %.2f ms/step' % d['from_text']['ms_per_step'])"
+  find $p -name "*trace*.csv" -size +8M -delete ;;
 shardsort)
   timeout 900 python tools/shard_sort_probe.py 2>&1 | grep -E "^rank|Error|error" ;;
 texttiming)
   # where a text -> GFA step spends its time: the ingest's and the pipeline's own laps (MA_PIPE_TIMING) around the from_text leg
-  MA_PIPE_TIMING=1 timeout 900 python bench.py --no-cpu --no-legs --steps 4 --warmup 1 --prof-steps 0 > gpurun_out/bench_texttiming.json 2> gpurun_out/bench_texttiming.log; echo "rc=$?"
-  grep -E "T::ingest_gpu|T::paf|T::head|T::tail|T::pipe" gpurun_out/bench_texttiming.log | tail -40
-  python3 -c "import json; d=json.load(open('gpurun_out/bench_texttiming.json')); print('   step %.3f ms, from_text %.2f ms/step' % (d['ms_per_step'], d['from_text']['ms_per_step']))" ;;
+  MA_PIPE_TIMING=1 timeout 900 python bench.py --full --no-cpu --no-legs --steps 4 --warmup 1 --prof-steps 0 > $out/bench_texttiming.json 2> $out/bench_texttiming.log; echo "rc=$?"
+  grep -E "T::ingest_gpu|T::paf|T::head|T::tail|T::pipe" $out/bench_texttiming.log | tail -40
+  python3 -c "import json; d=json.load(open('$out/bench_texttiming.json')); print('   step %.3f ms, from_text %.2f ms/step' % (d['ms_per_step'], d['from_text']['ms_per_step']))" ;;
 sqtext)
   # SQ counters (instruction mix, wait cycles) of the ingest kernels: three passes (8 counter slots)
   i=0
@@ -137,8 +138,8 @@ ghtiming)
   grep -E "T::tail|T::pipe|T::ug" gpurun_out/bench_ghtiming.log | tail -24
   python3 -c "import json; d=json.load(open('gpurun_out/bench_ghtiming.json')); print('   step %.3f ms' % d['ms_per_step'], d.get('latency'))" ;;
 benchtext)
-  timeout 900 python bench.py --no-cpu --no-legs --steps 6 --warmup 2 --prof-steps 0 > gpurun_out/bench_text.json 2> gpurun_out/bench_text.log; echo "rc=$?"
-  python3 -c "import json; d=json.load(open('gpurun_out/bench_text.json')); print('   step %.3f ms, from_text %.2f ms/step, parse+dictionary %.3f s' % (d['ms_per_step'], d['from_text']['ms_per_step'], d['setup']['parse_dictionary_s']))" ;;
+  timeout 900 python bench.py --full --no-cpu --no-legs --steps 6 --warmup 2 --prof-steps 0 > $out/bench_text.json 2> $out/bench_text.log; echo "rc=$?"
+  python3 -c "import json; d=json.load(open('$out/bench_text.json')); print('   step %.3f ms, from_text %.2f ms/step, parse+dictionary %.3f s' % (d['ms_per_step'], d['from_text']['ms_per_step'], d['setup']['parse_dictionary_s']))" ;;
 projection)
   timeout 1500 python tools/shard_projection.py --ranks 1,2,4,8 --steps 3 > gpurun_out/shard_projection.log 2>&1; echo "rc=$?"; grep -E "^N=" gpurun_out/shard_projection.log ;;
 bigthree)
@@ -158,21 +159,21 @@ sharded)
   timeout 1500 python -m pytest tests/test_gpu_sharded.py -m gpu -q --tb=short -p no:cacheprovider > gpurun_out/tests_sharded.log 2>&1; echo "rc=$?" >> gpurun_out/tests_sharded.log
   grep -vE "^\[M::|^\[pafgen" gpurun_out/tests_sharded.log | tail -40 ;;
 torchrun1)
-  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --reads 20000 --lines 1000000 --steps 3 --warmup 1 --no-cpu > gpurun_out/bench_torchrun1.json 2> gpurun_out/bench_torchrun1.log; echo "rc=$?"
-  tail -3 gpurun_out/bench_torchrun1.log; cut -c1-400 gpurun_out/bench_torchrun1.json ;;
+  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --reads 20000 --lines 1000000 --steps 3 --warmup 1 --full --no-cpu > $out/bench_torchrun1.json 2> $out/bench_torchrun1.log; echo "rc=$?"
+  tail -3 $out/bench_torchrun1.log; cut -c1-400 $out/bench_torchrun1.json ;;
 torchrun2debug)
   # 2 processes on the one GPU of this box, gloo collectives: the multi-process control flow of bench.py end to end
-  MA_BENCH_ONE_GPU_DEBUG=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 2 --reads 20000 --lines 1000000 --steps 3 --warmup 1 > gpurun_out/bench_torchrun2.json 2> gpurun_out/bench_torchrun2.log; echo "rc=$?"
-  tail -5 gpurun_out/bench_torchrun2.log; cut -c1-600 gpurun_out/bench_torchrun2.json ;;
+  MA_BENCH_ONE_GPU_DEBUG=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 2 --reads 20000 --lines 1000000 --steps 3 --warmup 1 --full > $out/bench_torchrun2.json 2> $out/bench_torchrun2.log; echo "rc=$?"
+  tail -5 $out/bench_torchrun2.log; cut -c1-600 $out/bench_torchrun2.json ;;
 smoke)
   timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; echo "rc=$?" >> gpurun_out/smoke.log
   grep -vE "^\[M::" gpurun_out/smoke.log | tail -15 ;;
 benchsmall)
-  timeout 900 python bench.py --reads 20000 --lines 1000000 --steps 3 --warmup 1 > gpurun_out/bench_small.json 2> gpurun_out/bench_small.log; echo "rc=$?" >> gpurun_out/bench_small.log
-  tail -5 gpurun_out/bench_small.log; cat gpurun_out/bench_small.json ;;
+  timeout 900 python bench.py --full --reads 20000 --lines 1000000 --steps 3 --warmup 1 > $out/bench_small.json 2> $out/bench_small.log; echo "rc=$?" >> $out/bench_small.log
+  tail -5 $out/bench_small.log; cat $out/bench_small.json ;;
 bench)
-  timeout 1700 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.log; echo "rc=$?" >> gpurun_out/bench.log
-  grep -E "^\[bench\]|rc=" gpurun_out/bench.log | tail -12; cat gpurun_out/bench.json ;;
+  timeout 1700 python bench.py --full > $out/bench.json 2> $out/bench.log; echo "rc=$?" >> $out/bench.log
+  grep -E "^\[bench\]|rc=" $out/bench.log | tail -12; cat $out/bench.json ;;
 tailctx)
   # the device tail on a second context (bench.py --tail-ctx, mahip_tail_handoff): same workload with and without, cfg4 and cfg2, GFA compared
   timeout 900 python -m pytest tests/test_gpu_graph_api.py -m gpu -q --tb=short -p no:cacheprovider -k "second_context or streaming" > gpurun_out/tests_tailctx.log 2>&1; echo "tests rc=$?"
@@ -192,11 +193,11 @@ exprun)
   done
   bash tools/variants.sh run base $VARIANT_NAMES ;;
 benchcfg2)
-  timeout 900 python bench.py --reads 200000 --lines 10000000 --seed 1 --no-legs > gpurun_out/bench_cfg2.json 2> gpurun_out/bench_cfg2.log; echo "rc=$?" >> gpurun_out/bench_cfg2.log
-  grep -E "^\[bench\]|rc=" gpurun_out/bench_cfg2.log | tail -8; cat gpurun_out/bench_cfg2.json ;;
+  timeout 900 python bench.py --full --reads 200000 --lines 10000000 --seed 1 --no-legs > $out/bench_cfg2.json 2> $out/bench_cfg2.log; echo "rc=$?" >> $out/bench_cfg2.log
+  grep -E "^\[bench\]|rc=" $out/bench_cfg2.log | tail -8; cat $out/bench_cfg2.json ;;
 benchfixed)
-  timeout 1500 python bench.py --model fixed --no-cpu > gpurun_out/bench_fixed.json 2> gpurun_out/bench_fixed.log; echo "rc=$?" >> gpurun_out/bench_fixed.log
-  tail -3 gpurun_out/bench_fixed.log; cat gpurun_out/bench_fixed.json ;;
+  timeout 1500 python bench.py --full --model fixed --no-cpu > $out/bench_fixed.json 2> $out/bench_fixed.log; echo "rc=$?" >> $out/bench_fixed.log
+  tail -3 $out/bench_fixed.log; cat $out/bench_fixed.json ;;
 sq)
   # instruction-mix / occupancy counters of the coverage kernels (two passes: the SQ block has 8 counter slots)
   i=0
@@ -207,8 +208,8 @@ sq)
   python tools/pmc_generic.py gpurun_out/sq_1 gpurun_out/sq_2 gpurun_out/sq_3 --filter k_hit_sub > gpurun_out/sq_summary.txt 2>&1; cat gpurun_out/sq_summary.txt | head -80
   find gpurun_out/sq_1 gpurun_out/sq_2 gpurun_out/sq_3 -name "*.csv" -size +8M -delete ;;
 benchexact)
-  MA_EXACT_TIES=1 timeout 1500 python bench.py --no-cpu --steps 3 --warmup 1 --prof-steps 0 > gpurun_out/bench_exact.json 2> gpurun_out/bench_exact.log; echo "rc=$?" >> gpurun_out/bench_exact.log
-  tail -3 gpurun_out/bench_exact.log; cat gpurun_out/bench_exact.json ;;
+  MA_EXACT_TIES=1 timeout 1500 python bench.py --full --no-cpu --steps 3 --warmup 1 --prof-steps 0 > $out/bench_exact.json 2> $out/bench_exact.log; echo "rc=$?" >> $out/bench_exact.log
+  tail -3 $out/bench_exact.log; cat $out/bench_exact.json ;;
 prof)
   rm -rf gpurun_out/prof; mkdir -p gpurun_out/prof
   (cd /tmp && timeout 1500 rocprofv3 --kernel-trace --stats -d /root/repo/gpurun_out/prof -o r --output-format csv -- python /root/repo/bench.py --steps 5 --warmup 1 --no-cpu --no-legs --no-text --prof-steps 0 > /root/repo/gpurun_out/prof/bench_under_prof.json 2> /root/repo/gpurun_out/prof/bench_under_prof.log); echo "rc=$?"
@@ -266,12 +267,12 @@ evidence)
     find $O/pmc_${wl}_FETCH_SIZE $O/pmc_${wl}_WRITE_SIZE -name "*.csv" -size +1M -delete 2>/dev/null
   done ;;
 benchsum)
-  # the default bench line (as the driver runs it) + a one-screen summary
-  timeout 1700 python bench.py --steps 20 --warmup 5 > gpurun_out/bench_default.json 2> gpurun_out/bench_default.log; echo "bench rc=$?"
-  python3 - <<'PY'
-import json
+  # the --full bench line + a one-screen summary
+  timeout 1700 python bench.py --full --steps 20 --warmup 5 > $out/bench_full.json 2> $out/bench_full.log; echo "bench rc=$?"
+  python3 - $out/bench_full.json <<'PY'
+import json, sys
 try:
-    d = json.load(open("gpurun_out/bench_default.json"))
+    d = json.load(open(sys.argv[1]))
     print("ms_per_step %.3f  value %.4g  gfa_identical %s  latency %s  e2e %s  from_text %s" % (d["ms_per_step"], d["value"], d["gfa_identical"], d.get("latency") and d["latency"]["ms"], d.get("e2e") and round(d["e2e"]["wall_s"], 3), d.get("from_text") and round(d["from_text"]["ms_per_step"], 2)))
     r = d["roofline"]; print("roofline (sort group): %.3f ms frac %.3f | dominant %s %.3f ms frac %.3f | hit_chain %.3f" % (r["avg_launch_ms"], r["frac"], r["dominant_kernel"]["kernel"], r["dominant_kernel"]["avg_launch_ms"], r["dominant_kernel"]["frac"], r["hit_chain"]["frac"]))
     rg = r.get("reduce_group"); print("reduce_group:", rg and (rg["ms_per_step"], rg["frac"], rg["slowest_by_8d"]), rg and [(k["name"], k["avg_ms"]) for k in rg["kernels"]])
