@@ -863,6 +863,7 @@ __global__ __launch_bounds__(256) void k_asg_trans_big(const uint32_t *__restric
 {
 	uint8_t *mark = marks + (size_t)blockIdx.x * n_vtx;
 	__shared__ uint32_t s_go;
+	uint32_t n_inner = 0; // bodies of the loop at asg.c:169 this thread executed, as in the wave tiers
 	for (uint32_t k = blockIdx.x; k < n_ovf; k += gridDim.x) {
 		uint32_t v = ovf[k];
 		unsigned long long x = idx[v];
@@ -878,7 +879,7 @@ __global__ __launch_bounds__(256) void k_asg_trans_big(const uint32_t *__restric
 				unsigned long long xw = idx[w];
 				uint32_t ws = (uint32_t)(xw >> 32), nw = (uint32_t)xw;
 				for (uint32_t j = threadIdx.x; j < nw; j += 256)
-					if (alen[ws + j] + li <= L) { uint32_t y = av[ws + j]; if (mark[y]) mark[y] = 2; } // lengths ascending: a prefix
+					if (alen[ws + j] + li <= L) { ++n_inner; uint32_t y = av[ws + j]; if (mark[y]) mark[y] = 2; } // lengths ascending: a prefix
 			}
 			__syncthreads();
 		}
@@ -893,6 +894,7 @@ __global__ __launch_bounds__(256) void k_asg_trans_big(const uint32_t *__restric
 		}
 		__syncthreads();
 	}
+	blk_add_u64(&ctr[CT_TRINNER], n_inner);
 }
 
 // ------------------------------------------------------------------------------------------------ asg_symm
@@ -1583,8 +1585,7 @@ extern "C" int mahip_asg_del_trans_range(mahip_ctx_t *c, int fuzz, uint32_t v_be
 		                   (const unsigned long long*)P<unsigned long long>(c->idx), (const uint8_t*)P<uint8_t>(c->sdel), v_beg, v_end, (uint32_t)fuzz, P<uint32_t>(c->ovf), ctr);
 	}
 	CHK(ctr_fetch(c));
-	c->tr_inner = c->h_ctr[CT_TRINNER];
-	if (c->prof && c->n_arc) prof_patch_last(c, "k_asg_trans", 16.0 * ((double)c->n_arc + (double)c->tr_inner)); // 16 (A + I) with the I this launch really ran
+	if (c->prof && c->n_arc) prof_patch_last(c, "k_asg_trans", 16.0 * ((double)c->n_arc + (double)c->h_ctr[CT_TRINNER])); // 16 (A + I) with the I this launch really ran
 	uint32_t n_ovf = (uint32_t)c->h_ctr[CT_OVF2];
 	if (n_ovf) {
 		unsigned nblk = n_ovf < 64 ? n_ovf : 64;
@@ -1596,6 +1597,7 @@ extern "C" int mahip_asg_del_trans_range(mahip_ctx_t *c, int fuzz, uint32_t v_be
 		CHK(ctr_fetch(c));
 	}
 	HIPCHK(hipGetLastError());
+	c->tr_inner = c->h_ctr[CT_TRINNER]; // all three tiers: read after the block tier has added its share
 	if (n_reduced) *n_reduced = (uint32_t)c->h_ctr[CT_NRED];
 	return 0;
 }

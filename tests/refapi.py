@@ -46,6 +46,8 @@ def orc():
         L.orc_arc_rm.argtypes = [sz, vp, vp]
         L.orc_arc_del_trans.restype = u32
         L.orc_arc_del_trans.argtypes = [u32, sz, vp, vp, vp, i32, C.POINTER(C.c_uint64)]
+        L.orc_arc_del_trans_range.restype = u32
+        L.orc_arc_del_trans_range.argtypes = [u32, sz, vp, vp, vp, i32, u32, u32, C.POINTER(C.c_uint64)]
         for f in (L.orc_arc_del_multi, L.orc_arc_del_asymm):
             f.restype = u32
             f.argtypes = [u32, sz, vp, vp]

@@ -312,6 +312,7 @@ def gpu_stages(ctx, hits, n_seq, opt, upto="trans", tie_mode=0, stride=None):
         ctx.sg_gen(opt, True)
         S["sg_arcs"], S["sg_seq"], S["sg_idx"] = ctx.asg_download()
         S["n_red"] = ctx.del_trans(opt.gap_fuzz)
+        S["n_inner"] = trans_inner(ctx)
         if S["n_red"]:
             ctx.symm()
         S["tr_arcs"], S["tr_seq"], S["tr_idx"] = ctx.asg_download()
@@ -349,6 +350,7 @@ def gpu_stages_fused(ctx, hits, n_seq, opt, tie_mode=0, stride=None, snapshots=T
     ctx.sg_gen(opt, True)
     S["sg_arcs"], S["sg_seq"], S["sg_idx"] = ctx.asg_download()
     S["n_red"] = ctx.del_trans(opt.gap_fuzz)
+    S["n_inner"] = trans_inner(ctx)
     if S["n_red"]:
         ctx.symm()
     S["tr_arcs"], S["tr_seq"], S["tr_idx"] = ctx.asg_download()
@@ -451,3 +453,445 @@ def compare(A, B, what, exact_order=False, graph=True):
             assert a.tobytes() == b.tobytes(), "%s: %s differ" % (what, k)
         assert A["sg_seq"].tobytes() == B["sg_seq"].tobytes(), "%s: seq differ" % what
         assert A["n_red"] == B["n_red"], what
+        for X, Y in ((A, B), (B, A)):  # the oracle's count of asg.c:169's loop bodies against mahip_asg_trans_inner (the reference library keeps no such count)
+            if "tr_cnt" in X and "n_inner" in Y:
+                assert X["tr_cnt"]["n_inner"] == Y["n_inner"], "%s: inner iterations of the reduction %d vs %d" % (what, X["tr_cnt"]["n_inner"], Y["n_inner"])
+
+
+# --------------------------------------------------------------------------------------------- graph size edges (tests/test_gpu_graph_edges.py)
+def graph_api():
+    """the C ABI entry points of the graph passes the thin harness does not wrap"""
+    L = ma.lib()
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.mahip_asg_trans_inner.restype = C.c_uint64
+    L.mahip_asg_trans_inner.argtypes = [vp]
+    L.mahip_asg_del_trans_range.argtypes = [vp, C.c_int, u32, u32, C.POINTER(u32)]
+    L.mahip_asg_cleanup.argtypes = [vp, C.POINTER(u32)]
+    L.mahip_asg_del_asymm.argtypes = [vp, C.POINTER(u32)]
+    return L
+
+
+def trans_inner(ctx):
+    return int(graph_api().mahip_asg_trans_inner(ctx.h))
+
+
+def asg_upload(ctx, arcs, seq, idx):
+    """a hand-made graph (arcs sorted by (u, len), seq = len | del << 31, CSR index) onto the device: mahip_asg_upload"""
+    arcs, seq, idx = np.ascontiguousarray(arcs, dtype=ARC_DT), np.ascontiguousarray(seq, dtype="<u4"), np.ascontiguousarray(idx, dtype="<u8")
+    g = ma.Asg()
+    g.arc, g.seq, g.idx = arcs.ctypes.data, seq.ctypes.data, idx.ctypes.data
+    g.m_arc, g.n_arc_srt, g.m_seq, g.n_seq_symm = max(len(arcs), 1), len(arcs) | 1 << 31, max(len(seq), 1), len(seq)
+    ma._chk(ma.lib().mahip_asg_upload(ctx.h, C.byref(g)), "asg_upload")
+    ma._chk(ma.lib().mahip_sync(ctx.h), "sync")  # (the copies are asynchronous: the arrays must outlive them)
+
+
+def graph_from_rows(n_seq, rows, deleted=(), seq_len=9000):
+    """rows of (u, v, len, ol) -> (arcs stably sorted by (u, len), seq words, index by orc_arc_index)"""
+    r = np.asarray(rows, dtype=np.uint64).reshape(-1, 4)
+    a = np.zeros(len(r), dtype=ARC_DT)
+    a["ul"], a["v"], a["oldel"] = r[:, 0] << np.uint64(32) | r[:, 2], r[:, 1], r[:, 3]
+    a = a[np.argsort(a["ul"], kind="stable")]
+    seq = np.full(n_seq, seq_len, dtype="<u4")
+    seq[np.asarray(deleted, dtype=np.int64)] |= np.uint32(1 << 31)
+    idx = np.zeros(2 * n_seq, dtype="<u8")
+    R.orc().orc_arc_index(n_seq, len(a), _ptr(a), _ptr(idx))
+    return a, seq, idx
+
+
+def with_mirrors(rows, d_len=3):
+    """every arc u -> v and its mirror v^1 -> u^1 (asg.c:104-145 expects both); the mirror is d_len longer"""
+    out = []
+    for (u, v, ln, ol) in rows:
+        out.append((u, v, ln, ol))
+        out.append((v ^ 1, u ^ 1, ln + d_len, ol))
+    return out
+
+
+def orc_trans_only(n_seq, arcs, idx, seq, fuzz, v_beg=0, v_end=None):
+    """the marking pass alone (asg.c:148-186) on a copy -> (arcs with del bits, n_reduced, n_inner)"""
+    O = R.orc()
+    a = arcs.copy()
+    sdel = (seq >> 31).astype(np.uint8)
+    inner = C.c_uint64(0)
+    n_red = O.orc_arc_del_trans_range(n_seq, len(a), _ptr(a), _ptr(idx), _ptr(sdel), fuzz, v_beg, 2 * n_seq if v_end is None else v_end, C.byref(inner))
+    return a, n_red, inner.value
+
+
+def orc_rm_index(n_seq, arcs, seq):
+    """asg_cleanup (asg.c:72-80) on a copy: orc_arc_rm + orc_arc_index"""
+    O = R.orc()
+    a = arcs.copy()
+    sdel = (seq >> 31).astype(np.uint8)
+    m = O.orc_arc_rm(len(a), _ptr(a), _ptr(sdel))
+    a = a[:m].copy()
+    idx = np.zeros(2 * n_seq, dtype="<u8")
+    O.orc_arc_index(n_seq, len(a), _ptr(a), _ptr(idx))
+    return a, idx
+
+
+ARC_EDGE_SIZES = (0, 1, 2, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512)  # arcs per read around every size edge of the arc sort per read
+ARC_EDGE_IDS = (0, 63, 64, 127, 128, 191, 300, 383, 384, 500, 640, 703, 800, -1)  # lanes 0 and 63 of 64-read chunks, > 64 arcless reads in between (192 .. 299), the dictionary's last read
+
+
+def dovetail(q, t, strand, ln, jit, rl):
+    """one hit between two reads of length rl that ma_hit2arc (miniasm.h:86-104) turns into the arc (q << 1 | strand) -> (t << 1 | strand) of length ln;
+    jit: the overhang in front of the overlap (<= max_hang), which makes the query start distinct without touching the arc"""
+    if strand == 0:
+        qs, qe, ts, te = ln + jit, rl, jit, rl - ln
+    else:
+        qs, qe, ts, te = jit, rl - ln, ln + jit, rl
+    return (q, qs, qe, t, ts, te)
+
+
+def hits_from_lines(lines, bl_of=None):
+    """(q, qs, qe, t, ts, te) forward-strand lines -> hit records"""
+    x = np.asarray(lines, dtype=np.uint64).reshape(-1, 6)
+    h = np.zeros(len(x), dtype=HIT_DT)
+    h["qns"] = x[:, 0] << np.uint64(32) | x[:, 1]
+    h["qe"], h["tn"], h["ts"], h["te"] = x[:, 2], x[:, 3], x[:, 4], x[:, 5]
+    bl = (x[:, 2] - x[:, 1]).astype(np.uint32)
+    h["bldel"], h["mlrev"] = bl, bl // np.uint32(2)
+    return h
+
+
+def arc_edge_hits(strands="split", few_lengths=False, n_seq=1024, extra=(), longest=0, seed=0):
+    """hits in which the reads ARC_EDGE_IDS get exactly ARC_EDGE_SIZES arcs (a permutation of them chosen by the seed; `extra`: more sizes, e.g. 513, on reads of
+    their own), all reads equally long so that no read contains another: every hit is a dovetail (see dovetail()) to one of 40 partner reads, which overlap among
+    themselves with short arcs (so the reduction finds transitive arcs); every other read has no hit.  strands: "0" / "1" / "split" -- which of the read's two
+    vertices its arcs leave.  few_lengths: arc lengths from a set of eight, so runs of equal (u, len) cross lane and register-row borders of the sort.
+    longest: if set, one arc of that length (the register sort holds lengths of up to 21 bits).  The records of a read stand together, in random order.
+    -> (hits, seq_len[n_seq], {read: arcs})"""
+    rng = np.random.default_rng(4200 + seed)
+    rl = max(longest, 20000) + 6000
+    sizes = list(rng.permutation(ARC_EDGE_SIZES))
+    if sizes[-1] == 0:  # the dictionary's last read must have arcs
+        sizes[-1], sizes[0] = sizes[0], sizes[-1]
+    ids = [i if i >= 0 else n_seq - 1 for i in ARC_EDGE_IDS] + [420 + 10 * k for k in range(len(extra))]
+    sizes = [int(s) for s in sizes] + [int(s) for s in extra]
+    part = np.arange(820, 860)
+    assert n_seq > 900 and not set(ids) & set(part.tolist())
+    lines = []
+    for q, n in zip(ids, sizes):
+        t = part[rng.integers(0, len(part), n)]
+        st = {"0": np.zeros(n, int), "1": np.ones(n, int), "split": np.arange(n) % 2}[strands]
+        ln = rng.choice(np.arange(1, 9) * 700, n) if few_lengths else rng.integers(1, 20000, n)
+        if longest and n == 64:
+            ln[0] = longest
+        for k in rng.permutation(n):
+            lines.append(dovetail(q, int(t[k]), int(st[k]), int(ln[k]), int(k), rl))
+    for p in part:
+        for k, t in enumerate(rng.choice(part[part != p], 4, replace=False)):
+            lines.append(dovetail(int(p), int(t), k % 2, int(rng.integers(1, 600)), k, rl))
+    return hits_from_lines(lines), np.full(n_seq, rl, dtype="<u4"), dict(zip(ids, sizes))
+
+
+SG_WORD_FILL = (0, 1, 5, 6, 64, 3, 7, 0, 64, 6, 5, 1, 20)  # arc-yielding slots per 64-slot word of the hit array, repeated (SG_DENSE = 6: lane walk below, whole wave from there on)
+
+
+def sg_emit_opt():
+    opt = ma.default_opt()
+    opt.max_hang, opt.int_frac, opt.min_ovlp = 1500, .5, 2000
+    return opt
+
+
+def sg_emit_hits(n_slots, seed=0):
+    """a hit array of exactly n_slots records, sorted by (query, start), in which 64-slot word w holds SG_WORD_FILL[w % 13] hits that yield an arc; the rest are
+    internal matches (no arc).  40 records per read, so reads cross word borders; run with sg_emit_opt().  A few reads carry a full-length hit (the query is
+    contained: asm.c:34 deletes it, and with it the arcs that other reads have to it), one a palindromic self hit (asm.c:27-31).  -> (hits, seq_len)"""
+    rng = np.random.default_rng(5200 + seed)
+    rl, per = 30000, 40
+    n_seq = (n_slots + per - 1) // per
+    lines, rev = [], []
+    killers = set(rng.choice(np.arange(3, n_seq - 1), max(n_seq // 60, 1), replace=False).tolist())
+    for s in range(n_slots):
+        q, k, w = s // per, s % per, s // 64
+        fill = SG_WORD_FILL[w % len(SG_WORD_FILL)]
+        order = np.random.default_rng(w).permutation(64)  # which slots of the word yield: fixed per word
+        t = int(rng.integers(0, n_seq - 1))
+        t += t >= q
+        qs = 1000 + 10 * k
+        r = 0
+        if k == 0 and q in killers:
+            ln = (q, 0, rl, t, 0, rl)  # query contained
+            if q % 2:
+                ln, r = (q, 500, rl - 200, q, 500, rl - 200), 1  # self hit on the other strand with an arc verdict
+        elif order[s % 64] < fill:
+            ln = (q, qs, rl, t, 1, 1 + rl - qs) if s % 2 == 0 else (q, qs, rl - (1 + 7 * (s % 1000)), t, 1 + 7 * (s % 1000) + qs, rl)
+        else:
+            ln = (q, qs, qs + 4000, t, 6000, 10000)  # ends in the middle of both reads: internal
+        lines.append(ln)
+        rev.append(r)
+    h = hits_from_lines(lines)
+    h["mlrev"] |= np.asarray(rev, dtype=np.uint32) << np.uint32(31)
+    return h, np.full(n_seq, rl, dtype="<u4")
+
+
+def sg_candidate_words(hits, seq_len, opt):
+    """per 64-slot word of a hit array the number of slots ma_hit2arc answers with an arc between two different reads (the oracle's verdict per hit)"""
+    O = R.orc()
+    arc = np.zeros(1, dtype=ARC_DT)
+    cand = np.zeros((len(hits) + 63) // 64 * 64, dtype=np.int64)
+    for i in range(len(hits)):
+        q, t = int(hits["qns"][i] >> np.uint64(32)), int(hits["tn"][i])
+        r = O.orc_hit2arc(_ptr(hits[i:i + 1]), int(seq_len[q]), int(seq_len[t]), opt.max_hang, opt.int_frac, opt.min_ovlp, _ptr(arc))
+        cand[i] = r >= 0 and q != t
+    return cand.reshape(-1, 64).sum(axis=1)
+
+
+def orc_sg(hits, seq_len, opt, presorted=False):
+    """ma_sg_gen against given read lengths (no intervals) -> (arcs, seq words, index); the hits are sorted by the oracle first unless presorted"""
+    O = R.orc()
+    a = np.ascontiguousarray(hits, dtype=HIT_DT).copy()
+    n_seq = len(seq_len)
+    if not presorted:
+        O.orc_hit_sort(len(a), _ptr(a))
+    arcs = np.zeros(max(len(a), 1), dtype=ARC_DT)
+    slen, sdel = np.zeros(n_seq, dtype="<u4"), np.zeros(n_seq, dtype=np.uint8)
+    m = O.orc_sg_gen(C.byref(opt), n_seq, None, _ptr(seq_len), None, len(a), _ptr(a), _ptr(arcs), _ptr(slen), _ptr(sdel))
+    arcs = arcs[:m].copy()
+    idx = np.zeros(2 * n_seq, dtype="<u8")
+    O.orc_arc_index(n_seq, m, _ptr(arcs), _ptr(idx))
+    return arcs, slen | (sdel.astype("<u4") << 31), idx, a
+
+
+def ref_sg(hits_sorted, seq_len, opt):
+    """the unmodified reference library's ma_sg_gen on a hit array as it stands (asm.c:9-39, no intervals: the dictionary's lengths)"""
+    L = R.ref()
+    d = L.sd_init()
+    for i, n in enumerate(seq_len):
+        L.sd_put(d, b"r%d" % i, int(n))
+    a = np.ascontiguousarray(hits_sorted, dtype=HIT_DT)
+    g = L.ma_sg_gen(C.byref(opt), d, None, len(a), _ptr(a))
+    out = R.asg_arrays(g)
+    L.asg_destroy(g)
+    L.sd_destroy(d)
+    return out
+
+
+def arc_tie_census(arcs):
+    """(groups, arcs) of equal (u, len) keys among sorted arcs: what mahip_tie_stats reports in tie mode 2"""
+    ul = arcs["ul"]
+    if len(ul) < 2:
+        return 0, 0
+    eq = ul[1:] == ul[:-1]
+    tied = np.r_[eq, False] | np.r_[False, eq]
+    return int((eq & ~np.r_[False, eq[:-1]]).sum()), int(tied.sum())
+
+
+# (k = arcs of the centre, (length, prefix inside L) of the first neighbour's list, [(arc index, list length, prefix inside L) of later candidates], centre on a deleted read)
+TRANS_GADGETS = [
+    (1, (2, 1), [], False), (2, (3, 2), [], False),
+    (40, (63, 63), [(5, 15, 15), (9, 16, 16), (13, 17, 17)], False),
+    (64, (64, 64), [(20, 40, 16), (24, 40, 17), (28, 80, 70), (58, 17, 15)], False),
+    (64, (65, 65), [(30, 16, 15)], False),
+    (100, (65, 64), [(56, 16, 15), (60, 17, 16), (63, 40, 40)], False),
+    (100, (127, 127), [(64, 17, 17), (70, 80, 65)], False),
+    (128, (128, 128), [(100, 15, 15), (120, 17, 17)], False),
+    (128, (129, 129), [(5, 40, 40), (66, 16, 16)], False),
+    (127, (300, 128), [(66, 16, 16)], False),
+    (65, (300, 129), [(10, 15, 14)], False),
+    (63, (300, 200), [(10, 17, 17)], False),
+    (30, (300, 63), [], False), (30, (127, 65), [], False), (30, (129, 127), [], False),
+    (129, (129, 64), [(3, 17, 17), (70, 80, 65)], False),  # (a centre of the wave tier behind the first one)
+    (50, (64, 64), [(5, 17, 17)], True), (3, (2, 2), [], True),
+]
+
+
+def trans_gadget_graph(fuzz, gadgets=TRANS_GADGETS):
+    """a graph made of one gadget per entry of TRANS_GADGETS.  A gadget is a centre vertex with k arcs (lengths 1000, 1010, ...; the last one 4000 longer, so
+    L = longest + fuzz leaves room) whose neighbours' lists are chosen: the first neighbour's list has the given length and prefix inside L; the entry that
+    ends the prefix has lx + li == L exactly and is the ONLY arc that reaches one neighbour of the centre (its "witness"), the entry behind it is the only
+    arc to another witness that therefore stays marked 1; the rest of the prefix reaches the centre's other neighbours ("covered") and filler reads.  A later
+    candidate stands at a chosen arc index and has a list of its own with two witnesses, which are the centre's next two arcs: the first is marked by its
+    own batch of four and must be skipped, the second is expanded after it.  Arcs are mirrored.  -> (n_seq, rows)"""
+    rows, n_read = [], 0
+    fill0, n_fill = 0, 320
+    n_read += n_fill  # filler reads: targets that are no neighbour of any centre
+    for (k, (n0, p0), cands, dead) in gadgets:
+        c = n_read
+        nb = [n_read + 1 + i for i in range(k)]
+        n_read += 1 + k
+        d = [1000 + 10 * i for i in range(k)]
+        d[-1] += 4000
+        L = d[-1] + fuzz
+        for i in range(k):
+            rows.append((2 * c, 2 * nb[i], d[i], 5000))
+        role = {0: (n0, p0)}
+        wit = set()
+        for (i, nw, p) in cands:
+            assert i + 2 < k - 1 and not {i, i + 1, i + 2} & (set(role) | wit)
+            role[i] = (nw, p)
+            wit |= {i + 1, i + 2}
+        if k > 3:
+            assert not {k - 3, k - 2} & (set(role) | wit)
+            wit |= {k - 3, k - 2}  # the first neighbour's witnesses
+        covered = [i for i in range(1, k - 1) if i not in role and i not in wit]
+        for i in range(k):
+            if i in role:
+                nw, p = role[i]
+                w_in, w_out = (i + 1, i + 2) if i else (k - 3, k - 2)
+                tg = ([2 * nb[x] for x in covered] if i == 0 else [])[:max(p - 1, 0)]
+            elif i == k - 1:
+                nw, p, tg, w_in, w_out = 1, 0, [], -1, -1
+            else:
+                nw, p, tg, w_in, w_out = 1, 1, [], -1, -1  # a witness or a covered neighbour the prefix had no room for: one arc to a filler
+            if i == k - 1:
+                p = min(p, fuzz)
+            for j in range(nw):
+                ln = L - d[i] - (p - 1 - j) if j < p else L - d[i] + 1 + (j - p)
+                if j < len(tg):
+                    v = tg[j]
+                elif j == p - 1 and w_in > 0 and k > 3:
+                    v = 2 * nb[w_in]
+                elif j == p and w_out > 0 and k > 3:
+                    v = 2 * nb[w_out]
+                else:
+                    v = 2 * (fill0 + j % n_fill)
+                rows.append((2 * nb[i], v, ln, 4000))
+        if dead:
+            rows.append(("dead", c, 0, 0))
+    deleted = [r[1] for r in rows if r[0] == "dead"]
+    rows = with_mirrors([r for r in rows if r[0] != "dead"])
+    return n_read, rows, deleted
+
+
+def trans_profile(arcs, idx, seq, fuzz):
+    """replay of asg.c:148-186 for the live vertices of 1 .. 128 arcs, as the first tier of the device walks them (candidates taken four at a time inside a
+    row of 64 arcs), to say WHAT the input contains: -> dict of sets / counts the size-edge test asserts to be present"""
+    P = dict(nv=set(), first=set(), later=set(), cand_at=set(), pending=0, skipped_in_batch=0, exact=0, rows1=0, rows2=0)
+    ul, av = arcs["ul"], arcs["v"]
+    ln_all = (ul & np.uint64(0xffffffff)).astype(np.int64)
+    for v in range(len(idx)):
+        st, nv = int(idx[v] >> np.uint64(32)), int(idx[v] & np.uint64(0xffffffff))
+        P["nv"].add(nv)
+        if nv == 0 or nv > 128 or seq[v >> 1] >> 31:
+            continue
+        tg, ln = av[st:st + nv].tolist(), ln_all[st:st + nv].tolist()
+        L = ln[-1] + fuzz
+        mark = {t: 1 for t in tg}
+
+        def expand(i):
+            ws, nw = int(idx[tg[i]] >> np.uint64(32)), int(idx[tg[i]] & np.uint64(0xffffffff))
+            p = 0
+            while p < nw and ln_all[ws + p] + ln[i] <= L:
+                if av[ws + p] in mark:
+                    mark[av[ws + p]] = 2
+                p += 1
+            P["exact"] += p > 0 and ln_all[ws + p - 1] + ln[i] == L
+            return nw, p
+        f = expand(0)
+        P["first"].add(f)
+        P["rows1" if nv <= 64 and f[0] <= 64 else "rows2"] += 1
+        P["pending"] = max(P["pending"], sum(1 for i in range(1, nv) if mark[tg[i]] == 1))
+        for base in (0, 64):
+            passed = 0 if base else 1
+            while True:
+                cand = [i for i in range(base + passed, min(base + 64, nv)) if mark[tg[i]] == 1]
+                if not cand:
+                    break
+                for i in cand[:4]:
+                    passed = i - base + 1
+                    if mark[tg[i]] != 1:
+                        P["skipped_in_batch"] += 1
+                        continue
+                    P["later"].add(expand(i))
+                    P["cand_at"].add(i)
+    return P
+
+
+def hub_graph(n, seed=0):
+    """reads on a line, an arc u -> v of length pos[v] - pos[u] to the next 2 .. 6 reads (transitive by construction), and three hubs of exactly n arcs each:
+    read 0 (alive), read 1 (flagged deleted: asg.c:158-161, all its arcs go), read 2 (alive, a tenth of its targets twice: of several arcs to one reduced
+    target only the first is deleted, asg.c:181-184).  Mirrored.  -> (n_seq, rows, deleted reads)"""
+    rng = np.random.default_rng(7700 + seed + n)
+    n_seq = n + 60
+    pos = np.sort(rng.choice(np.arange(1, 400000), n_seq, replace=False))
+    rows = []
+    for u in range(3, n_seq):
+        for v in range(u + 1, min(n_seq, u + 1 + int(rng.integers(2, 7)))):
+            rows.append((2 * u, 2 * v, int(pos[v] - pos[u]), 5000))
+    for hub in (0, 1, 2):
+        n_dup = n // 10 if hub == 2 else 0
+        tg = rng.choice(np.arange(3, n_seq), n - n_dup, replace=False)
+        for v in tg:
+            rows.append((2 * hub, 2 * int(v), int(pos[v] - pos[hub]), 4000))
+        for v in tg[:n_dup]:
+            rows.append((2 * hub, 2 * int(v), int(pos[v] - pos[hub]) + int(rng.integers(0, 3)), 3999))
+    return n_seq, with_mirrors(rows), [1]
+
+
+CHUNK_FILL = (1, 2, 3, 4, 9, 1)  # vertices with arcs per chunk of 64 consecutive vertices
+
+
+def chunk_graph():
+    """64-vertex chunks that hold exactly CHUNK_FILL vertices with arcs: the first chunk's is its last vertex (63), the last chunk's the graph's last vertex.
+    Not mirrored (a mirror would give a second vertex its arcs).  -> (n_seq, rows)"""
+    rng = np.random.default_rng(7800)
+    n_seq = 32 * len(CHUNK_FILL)
+    act = []
+    for c, n in enumerate(CHUNK_FILL):
+        if c == 0:
+            act += [63]
+        elif c == len(CHUNK_FILL) - 1:
+            act += [64 * c + 63]
+        else:
+            act += sorted((64 * c + rng.choice(64, n, replace=False)).tolist())
+    rows = []
+    for k, v in enumerate(act):
+        w = [act[(k + j) % len(act)] for j in (1, 2, 3)]
+        for j, t in enumerate(w):
+            rows.append((v, t, 100 * (j + 1), 3000))
+    return n_seq, rows
+
+
+RM_SIZES = (1, 7, 2047, 2048, 2049, 2050, 2051, 8191, 8192, 8193, 8196, 32767, 32768, 32769, 32773, 32774, 65536 + 3)  # arc counts around RM_TILE = 2048 and RMC_GROUP = 32768, every residue mod 8
+RM_PATTERNS = ("none", "all", "first_block", "all_but_last", "tail_deleted", "tail_survives", "random10", "random90")
+
+
+def rm_pattern(n, name):
+    """which of n arcs stay"""
+    keep = np.ones(n, dtype=bool)
+    rng = np.random.default_rng(n)
+    if name == "all":
+        keep[:] = False
+    elif name == "first_block":  # everything in the first group of 32768 / tile of 2048 (or the first half of a graph smaller than that)
+        keep[:32768 if n > 32768 else 2048 if n > 2048 else max(n // 2, 1)] = False
+    elif name == "all_but_last":
+        keep[:-1] = False
+    elif name == "tail_deleted":  # only behind the last multiple of 4 before the end
+        keep[(n - 1) // 4 * 4:] = False
+    elif name == "tail_survives":  # nothing but the last tile's / group's tail: behind the last multiple of 8 before the end
+        keep[:(n - 1) // 8 * 8] = False
+    elif name.startswith("random"):
+        keep = rng.random(n) >= int(name[6:]) / 100.
+    return keep
+
+
+def rm_graph(keep, chained):
+    """n arcs, arc p the only arc of vertex p (so it stands at position p).
+    chained = False: an arc that stays is p -> p^1, its own mirror; one that goes is p -> a read without arcs and has no mirror: asg_arc_del_asymm marks exactly those.
+    chained = True: an arc that goes has its del bit set already (even p), or its target is a read flagged deleted (odd p), or -- both arcs of a read going -- now and then
+    the read itself is flagged: asg_arc_rm decides by the arc's bit AND both seq.del look-ups.  -> (n_seq, arcs, seq, idx)"""
+    n = len(keep)
+    p = np.arange(n, dtype=np.int64)
+    R_ = (n + 1) // 2
+    z, dd = R_, R_ + 1
+    v = np.where(keep, p ^ 1, 2 * z)
+    ol = np.full(n, 3000, dtype=np.int64)
+    deleted = []
+    if chained:
+        both = np.flatnonzero(~keep[:n // 2 * 2:2] & ~keep[1:n // 2 * 2:2])
+        src = both[both % 3 == 0]  # reads deleted as a whole: their two arcs look like arcs that stay
+        by_read = np.zeros(n, dtype=bool)
+        by_read[2 * src], by_read[2 * src + 1] = True, True
+        v = np.where(by_read, p ^ 1, v)
+        ol = np.where(~keep & ~by_read & (p % 2 == 0), ol | (1 << 31), ol)
+        v = np.where(~keep & ~by_read & (p % 2 == 1), 2 * dd, v)
+        deleted = src.tolist() + [dd]
+    a = np.zeros(n, dtype=ARC_DT)
+    a["ul"], a["v"], a["oldel"] = (p.astype(np.uint64) << np.uint64(32)) | np.uint64(100), v, ol
+    seq = np.full(R_ + 2, 9000, dtype="<u4")
+    seq[np.asarray(deleted, dtype=np.int64)] |= np.uint32(1 << 31)
+    idx = np.zeros(2 * (R_ + 2), dtype="<u8")
+    R.orc().orc_arc_index(R_ + 2, n, _ptr(a), _ptr(idx))
+    return R_ + 2, a, seq, idx

@@ -5,8 +5,9 @@ subprocess (`-p emu_plugin` swaps the library path of the ctypes harness).  This
 kernels' logic (every stage bit-exact against the oracle and the reference library) on the box that has no GPU; it says
 nothing about speed, stream ordering or memory-model behaviour, which only the `-m gpu` run on an MI355X covers.
 
-By default a subset that finishes in about three minutes runs; MA_EMU_FULL=1 runs every GPU test module except the
-BASELINE-scale inputs and the RCCL tests (about 25 minutes on 8 cores)."""
+By default a subset runs; MA_EMU_FULL=1 runs every GPU test module except the BASELINE-scale inputs and the RCCL tests (about 25 minutes
+on 8 cores).  The default `-m "not gpu"` selection of this file took 12 min 46 s of wall time on 8 cores before tests/test_gpu_graph_edges.py was
+added; that module adds about half a minute (15 s in normal order, 16 s reversed with guard pages), so none of its cases is held back for MA_EMU_FULL."""
 import os
 import subprocess
 import sys
@@ -70,12 +71,19 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     env = {"EMU_ORDER": "reverse", "EMU_GUARD": "1", "MA_DEV_POOL": "0"}  # (the pool hands out pieces of bigger allocations: no guard page behind them)
     run_gpu_tests(["tests/test_gpu_parity.py", "-k", "noisy or deep_groups or sort_random", "tests/test_gpu_ingest.py"], 3000, env)
     run_gpu_tests(["tests/test_gpu_fused_hits.py", "-k", "group_size_edges"], 3000, env)  # tier B's global scratch (4097 and 9001 hits) ends at a guard page too
+    run_gpu_tests(["tests/test_gpu_graph_edges.py"], 3000, env)  # the arc sort's rows, the reduction's neighbour lists and the cleanup's tails at their size edges
 
 
 def test_kernels_graph_api_on_cpu(emu_built):
     """tests/test_gpu_graph_api.py, test_gpu_graph_fuzz.py: device cleaners and unitigs after every call, through the per-symbol ABI (pipeline graphs,
     hand-made rings and hubs, random graphs with random scripts)"""
     run_gpu_tests(["tests/test_gpu_graph_api.py", "tests/test_gpu_graph_fuzz.py"] + ([] if FULL else ["-k", "not noisy_big"]), 1800)
+
+
+def test_graph_size_edges_on_cpu(emu_built):
+    """tests/test_gpu_graph_edges.py: the graph kernels at every size edge they branch on (arcs per read, arcs per vertex and per expanded neighbour, arc counts
+    of the cleanup), every one against the oracle and the reference library; a quarter of a minute"""
+    run_gpu_tests(["tests/test_gpu_graph_edges.py"], 1800)
 
 
 def test_tie_filter_on_cpu(emu_built):
