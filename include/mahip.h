@@ -210,6 +210,14 @@ int mahip_asg_pop_bubble(mahip_ctx_t *c, int max_dist, uint32_t *n_pop, uint32_t
 /* how many asg_pop_bubble calls of this context were run as the reference's sequential sweep on one lane (graphs that are not symmetric or not clean:
  * csrc/clean_core.h, ASSUMPTION; MA_BUBBLE_SEQ=1 forces it) */
 uint32_t mahip_bubble_seq_sweeps(mahip_ctx_t *c);
+/* What the LAST mahip_asg_cut_tip / _cut_internal / _cut_biloop / _pop_bubble call of this context did (host bookkeeping, read-only; the tests assert
+ * from it that a case reached the tier, kernel form and sweep count it was built for).  n_iter: sweeps of the fixpoint, the one that found nothing
+ * new included (0: the call returned before its first sweep -- no reads, no arcs, no bubble source).  Bubbles only: max_tier = the highest table
+ * tier launched; n_src[t] = sources handed to tier t, summed over the sweeps; form[t] = the kernel form tier t last ran in (0: never launched);
+ * seq_sweep: the call ended in the reference's sequential sweep on one lane (then the graph is that sweep's, whatever the fixpoint did before). */
+enum { MAHIP_BUBBLE_TIERS = 5, MAHIP_BUBBLE_THREAD = 1, MAHIP_BUBBLE_WAVE_LDS = 2, MAHIP_BUBBLE_WAVE_HBM = 3 };
+typedef struct { uint32_t n_iter, max_tier, seq_sweep, form[MAHIP_BUBBLE_TIERS]; uint64_t n_src[MAHIP_BUBBLE_TIERS]; } mahip_clean_info_t;
+int mahip_clean_last(mahip_ctx_t *c, mahip_clean_info_t *out);
 /* asm.c:121-210 ma_ug_gen on the device (csrc/ug.hip): unitigs of the current graph.  Counts: unitigs, reads on them, arcs
  * between unitig ends.  mahip_ug_download: per unitig {reads, length, start, end} (start == end == 0xffffffff: circular) and the
  * offset of its members; members = vertex << 32 | length to the next read; uarcs = the unitig arcs in push order (the
@@ -224,6 +232,10 @@ int mahip_useq_begin(mahip_ctx_t *c, size_t arena_bytes);          /* arena of a
 int mahip_useq_batch(mahip_ctx_t *c, const char *h_seq, size_t seq_bytes, const mahip_useq_job_t *h_jobs, size_t n_jobs);
 int mahip_useq_end(mahip_ctx_t *c, char *h_arena);                 /* the arena back to the host */
 uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
+/* how many device-wide scans (csrc/scan.hip) of this context, since it was created, took each form: one tile (k_scan_down alone, n <= 2048), the chained
+ * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */
+enum { MAHIP_SCAN_ONE_TILE = 0, MAHIP_SCAN_CHAINED = 1, MAHIP_SCAN_THREE_PHASE = 2 };
+void mahip_scan_forms(mahip_ctx_t *c, uint64_t out[3]);
 /* iterations of the inner loop of asg_arc_del_trans (asg.c:169) in the last reduction this context ran, counted on the device: SURVEY 8(d) prices the
  * reduction at 16 (A + I) bytes (bench.py: roofline.reduce_group) */
 uint64_t mahip_asg_trans_inner(mahip_ctx_t *c);

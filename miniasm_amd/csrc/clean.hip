@@ -207,8 +207,9 @@ __global__ __launch_bounds__(64) void k_clean_bubble_seq(const uint32_t *au, con
 // bubble tables: tier 0 = one small table per thread of the full-width launch; tiers above (16x the slots, 1/16 of the threads: the same
 // bytes) only ever see the sources that overflowed the tier below
 enum { BUB_CAP0 = 16, BUB_THREADS0 = 524288, BUB_TIERS = 5 }; // 16, 1 024, 16 384 .. 4 M slots; 32 B per slot: 256 MiB per tier that is ever needed (tier 1: LDS)
+static_assert(BUB_TIERS == MAHIP_BUBBLE_TIERS, "mahip_clean_info_t holds one entry per tier");
 struct BubTier { DevBuf tabs, aux; bool ready = false; };
-struct CleanBufs { DevBuf st[2], src, ovf[2], seq; BubTier tier[BUB_TIERS]; uint32_t max_tier = 0; uint32_t n_seq_sweeps = 0; }; // st[k]: read stamps [R rounded up] then arc stamps [A]
+struct CleanBufs { DevBuf st[2], src, ovf[2], seq; BubTier tier[BUB_TIERS]; uint32_t max_tier = 0; uint32_t n_seq_sweeps = 0; mahip_clean_info_t last = {}; }; // st[k]: read stamps [R rounded up] then arc stamps [A]; last: what the last cleaner call did (mahip_clean_last)
 
 static CleanBufs *clean_bufs(mahip_ctx *c)
 {
@@ -259,7 +260,7 @@ static int bubble_launch(mahip_ctx *c, CleanBufs *b, int tier, const cl_view_t &
 	const bool lds = wave && cap <= bub_lds_cap();
 	const unsigned threads = lds ? (n_src < 8192u ? n_src : 8192u) : bub_threads(tier, n_src); // = tables = (wave form) blocks
 	const size_t slots = lds ? 0 : (size_t)threads * cap;
-	if (t.tabs.cap < slots * sizeof(cl_binfo_t)) {
+	if (t.tabs.cap < slots * sizeof(cl_binfo_t) || t.aux.cap < slots * 2 * 4) { // (each on its own: the pool may have handed out more than was asked for, and not the same surplus to both)
 		CHK(dev_reserve(c, t.tabs, slots * sizeof(cl_binfo_t)));
 		CHK(dev_reserve(c, t.aux, slots * 2 * 4));
 		t.ready = false;
@@ -273,6 +274,9 @@ static int bubble_launch(mahip_ctx *c, CleanBufs *b, int tier, const cl_view_t &
 	if (wave) hipLaunchKernelGGL(k_clean_bubble_wave, dim3(threads), dim3(64), 0, c->st, g, s, src, n_src, max_dist, (cl_binfo_t*)t.tabs.p, P<uint32_t>(t.aux), cap, lds ? 1 : 0, ovf, P<unsigned long long>(c->ctr));
 	else hipLaunchKernelGGL(k_clean_bubble, dim3((threads + 63) / 64), dim3(64), 0, c->st, g, s, src, n_src, max_dist, (cl_binfo_t*)t.tabs.p, P<uint32_t>(t.aux), cap, threads, ovf, P<unsigned long long>(c->ctr));
 	if ((uint32_t)tier > b->max_tier) b->max_tier = tier;
+	if ((uint32_t)tier > b->last.max_tier) b->last.max_tier = tier;
+	b->last.n_src[tier] += n_src;
+	b->last.form[tier] = !wave ? MAHIP_BUBBLE_THREAD : lds ? MAHIP_BUBBLE_WAVE_LDS : MAHIP_BUBBLE_WAVE_HBM;
 	return 0;
 }
 
@@ -295,12 +299,19 @@ static int bubble_sweep_seq(mahip_ctx *c, CleanBufs *b, uint32_t max_dist, uint3
 	CHK(ctr_fetch(c));
 	HIPCHK(hipGetLastError());
 	++b->n_seq_sweeps;
+	b->last.seq_sweep = 1;
 	if (c->h_ctr[CT_OVF]) { mahip_set_error("asg_pop_bubble: more walks into a vertex than it has arcs in -- the graph is not symmetric, and the reference's assertion (asg.c:391) ends its run here too"); return -1; }
 	*cnt = (uint32_t)c->h_ctr[CT_LIVE]; *cnt2 = (uint32_t)c->h_ctr[CT_REMAIN];
 	if (*cnt) { c->arcs_clean = false; CHK(ctr_zero(c)); CHK(graph_cleanup(c)); } // asg.c:430 (reads were deleted: the cleanup looks at seq.del again)
 	return 0;
 }
 extern "C" uint32_t mahip_bubble_seq_sweeps(mahip_ctx_t *c) { return c->clean ? ((CleanBufs*)c->clean)->n_seq_sweeps : 0; } // tests: did a call take the sequential road?
+extern "C" int mahip_clean_last(mahip_ctx_t *c, mahip_clean_info_t *out) // tests: sweeps, tiers and kernel forms of the last cleaner call (host bookkeeping only)
+{
+	if (!c->clean) { mahip_set_error("mahip_clean_last: no cleaner has run on this context"); return -1; }
+	*out = ((CleanBufs*)c->clean)->last;
+	return 0;
+}
 
 // mode 0..2: the short-unitig rules with param = max_ext; mode 3: bubbles with param = max_dist.
 // *cnt = actions of the sweep (tips cut / internal sequences / bi-loops / bubbles), *cnt2 = tips trimmed by bubble pops.
@@ -311,6 +322,7 @@ static int clean_sweep(mahip_ctx *c, int mode, int param, uint32_t *cnt, uint32_
 	CleanBufs *b = clean_bufs(c);
 	const uint32_t R = graph_nseq(c), V = 2 * R;
 	const size_t A = c->n_arc;
+	b->last = mahip_clean_info_t();
 	*cnt = *cnt2 = 0; if (n_iter) *n_iter = 0;
 	if (V == 0) return 0; // (no arcs at all is still a graph: every read without arcs is a tip, asg.c:238-254)
 	const size_t Rp = ((size_t)R + 63) & ~(size_t)63, W = Rp + A; // words per stamp set
@@ -330,7 +342,7 @@ static int clean_sweep(mahip_ctx *c, int mode, int param, uint32_t *cnt, uint32_
 		n_src = (uint32_t)(c->h_ctr[CT_TOTAL] & 0xffffffffu);
 		if (n_src == 0) return 0;
 		static const bool force_seq = getenv("MA_BUBBLE_SEQ") != nullptr;
-		if (force_seq) { if (n_iter) *n_iter = 1; return bubble_sweep_seq(c, b, (uint32_t)param, cnt, cnt2); }
+		if (force_seq) { b->last.n_iter = 1; if (n_iter) *n_iter = 1; return bubble_sweep_seq(c, b, (uint32_t)param, cnt, cnt2); }
 	}
 	cl_view_t g;
 	const int ag = c->ag;
@@ -375,6 +387,7 @@ static int clean_sweep(mahip_ctx *c, int mode, int param, uint32_t *cnt, uint32_
 		}
 		cur ^= 1;
 		if (n_iter) *n_iter = it + 1;
+		b->last.n_iter = (uint32_t)it + 1;
 		// fixpoint: the stamps did not change.  After the first sweep: no action means no stamp (an action may also be a no-op: counted, asg.c:296-302)
 		if (it == 0 ? c->h_ctr[CT_LIVE] == 0 : c->h_ctr[CT_TOTDP] == 0) {
 			if (mode == 3 && c->h_ctr[CT_OVF2]) // the final view holds a pop that brings a dead read back (clean_core.h: ASSUMPTION): outside the fixpoint's contract --

@@ -175,18 +175,23 @@ int scan_exclusive_u32(mahip_ctx *c, const uint32_t *in, uint32_t *out, size_t n
 	const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
 	if (nb >= 0x40000000ull) { mahip_set_error("scan: input too large"); return -1; }
 	if (nb == 1) { // one tile: nothing to chain
+		++c->scan_forms[MAHIP_SCAN_ONE_TILE];
 		hipLaunchKernelGGL(k_scan_down, dim3(1), dim3(SCAN_THREADS), 0, c->st, in, out, (const uint32_t*)nullptr, n, d_total);
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
 	if (nb > SCAN_CHAIN_MAX) { // a big array: reduce / scan of the tile sums / downsweep
+		++c->scan_forms[MAHIP_SCAN_THREE_PHASE];
 		CHK(scan_rec(c, in, out, n, d_total, 0));
 		HIPCHK(hipGetLastError());
 		return 0;
 	}
 	uint32_t *ticket; unsigned long long *state; uint32_t ticket_base, epoch;
 	CHK(scan_chain_begin(c, nb, &state, &ticket, &ticket_base, &epoch));
+	++c->scan_forms[MAHIP_SCAN_CHAINED];
 	hipLaunchKernelGGL(k_scan_chain, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, c->st, in, out, n, d_total, state, ticket, ticket_base, epoch);
 	HIPCHK(hipGetLastError());
 	return 0;
 }
+
+extern "C" void mahip_scan_forms(mahip_ctx_t *c, uint64_t out[3]) { for (int k = 0; k < 3; ++k) out[k] = c->scan_forms[k]; } // tests: which form did a size take?

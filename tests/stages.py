@@ -895,3 +895,301 @@ def rm_graph(keep, chained):
     idx = np.zeros(2 * (R_ + 2), dtype="<u8")
     R.orc().orc_arc_index(R_ + 2, n, _ptr(a), _ptr(idx))
     return R_ + 2, a, seq, idx
+
+
+# --------------------------------------------------------------------------------------------- cleaners and unitigs at their size edges (tests/test_gpu_clean_edges.py)
+class CleanInfo(C.Structure):  # include/mahip.h: mahip_clean_info_t
+    _fields_ = [("n_iter", C.c_uint32), ("max_tier", C.c_uint32), ("seq_sweep", C.c_uint32), ("form", C.c_uint32 * 5), ("n_src", C.c_uint64 * 5)]
+
+
+FORM_THREAD, FORM_LDS, FORM_HBM = 1, 2, 3  # MAHIP_BUBBLE_THREAD / _WAVE_LDS / _WAVE_HBM
+
+
+def clean_api():
+    """the C ABI entry points of the cleaners and the unitig pass, and the view of what the last cleaner call did"""
+    L = graph_api()
+    vp, u32 = C.c_void_p, C.c_uint32
+    for name in ("mahip_asg_cut_tip", "mahip_asg_cut_internal", "mahip_asg_cut_biloop"):
+        getattr(L, name).argtypes = [vp, C.c_int, C.POINTER(u32)]
+    L.mahip_asg_pop_bubble.argtypes = [vp, C.c_int, C.POINTER(u32), C.POINTER(u32)]
+    L.mahip_asg_del_short.argtypes = [vp, C.c_float, C.POINTER(u32)]
+    L.mahip_clean_last.argtypes = [vp, C.POINTER(CleanInfo)]
+    L.mahip_ug_gen.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
+    L.mahip_ug_download.argtypes = [vp] + [vp] * 7
+    L.mahip_scan_forms.restype = None
+    L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+    return L
+
+
+def clean_last(ctx):
+    """mahip_clean_last as a dict: n_iter, max_tier, seq_sweep, form[5], n_src[5]"""
+    info = CleanInfo()
+    ma._chk(clean_api().mahip_clean_last(ctx.h, C.byref(info)), "clean_last")
+    return dict(n_iter=info.n_iter, max_tier=info.max_tier, seq_sweep=info.seq_sweep, form=list(info.form), n_src=[int(x) for x in info.n_src])
+
+
+def scan_forms(ctx):
+    """mahip_scan_forms: scans of this context so far that took [one tile, the chained launch, reduce / scan / downsweep]"""
+    out = (C.c_uint64 * 3)()
+    clean_api().mahip_scan_forms(ctx.h, C.byref(out))
+    return [int(x) for x in out]
+
+
+def mirror_rows(rows, d_len=3):
+    """with_mirrors on an (n, 4) array: row k and its mirror stand at 2k and 2k + 1"""
+    r = np.asarray(rows, dtype=np.int64).reshape(-1, 4)
+    out = np.empty((2 * len(r), 4), dtype=np.int64)
+    out[0::2] = r
+    out[1::2, 0], out[1::2, 1], out[1::2, 2], out[1::2, 3] = r[:, 1] ^ 1, r[:, 0] ^ 1, r[:, 2] + d_len, r[:, 3]
+    return out
+
+
+class Gb:
+    """a graph under construction: reads are handed out in id order, arcs are given between VERTICES (Gb.v(read), ^ 1 for the other strand);
+    finish() adds the mirrors and returns what asg_symm + asg_cleanup leave: symmetric, sorted, indexed, no multi-arcs (asserted).
+    mixed: every third read is used on its reverse strand."""
+    DEL = 1 << 31
+
+    def __init__(self, mixed=False):
+        self.n, self.rows, self.raw, self.mixed = 0, [], [], mixed
+
+    def reads(self, k):
+        self.n += k
+        return np.arange(self.n - k, self.n, dtype=np.int64)
+
+    def read(self):
+        return int(self.reads(1)[0])
+
+    def v(self, r):
+        r = np.asarray(r, dtype=np.int64)
+        return 2 * r + (r % 3 == 1 if self.mixed else 0)
+
+    def arc(self, u, v, ln, ol=3000, dead=False):
+        u, v, ln, ol = np.broadcast_arrays(np.asarray(u, dtype=np.int64), np.asarray(v, dtype=np.int64), np.asarray(ln, dtype=np.int64), np.asarray(ol, dtype=np.int64))
+        if u.size:
+            self.rows.append(np.stack([u.ravel(), v.ravel(), ln.ravel(), ol.ravel() | (self.DEL if dead else 0)], axis=1))
+
+    def arc2(self, u, v, ln, ln_mirror, ol=3000):
+        """an arc and its mirror with lengths of their own (finish() adds no mirror for these)"""
+        self.raw.append(np.array([[u, v, ln, ol], [v ^ 1, u ^ 1, ln_mirror, ol]], dtype=np.int64))
+
+    def path(self, reads, ln=1, ol=3000):
+        self.arc(self.v(reads[:-1]), self.v(reads[1:]), ln, ol)
+
+    def ring(self, k):
+        """k reads in a ring: nothing about it is a tip, a fork or a bubble"""
+        h = self.reads(k)
+        self.path(np.r_[h, h[:1]], 50)
+        return h
+
+    def finish(self, d_len=3, pad_to=None):
+        if pad_to is not None:
+            assert pad_to >= self.n
+            self.n = pad_to
+        rows = mirror_rows(np.concatenate(self.rows), d_len) if self.rows else np.zeros((0, 4), dtype=np.int64)
+        rows = np.concatenate([rows] + self.raw) if self.raw else rows
+        uv = rows[:, 0] << 32 | rows[:, 1]
+        assert len(np.unique(uv)) == len(uv), "multi-arcs"
+        assert len(rows) == 0 or rows[:, :2].max() < 2 * self.n
+        return (self.n,) + graph_from_rows(self.n, rows)
+
+
+def ladder_bubble(gb, m1, m2, broken=None, tips=0):
+    """source s -> two parallel paths p (m1 reads) and q (m2 reads) -> sink t -> one more read (a sink without arcs would be a tip: asg.c:393-395).
+    The probe from s expands q first (arcs are taken in list order, the work list is LIFO), meets t, then p: its table holds m1 + m2 + 1 + tips entries
+    when it walks its LAST arc, p's last read -> t, and that arc also has the largest d + l of the probe, `far` (p's inner arcs are 3 long, q's 1:
+    asserted) -- so max_dist = far pops with d + l == max_dist on the last arc, max_dist = far - 1 gives up there with the table full.
+    t^1 is a bubble source too (the mirror image, same distances with finish(d_len=0)); s is the smaller vertex and pops, t^1 must see it popped.
+    tips: reads without arcs hanging off q's first reads; the pop trims them (n_tips), and the mirror probe fails (an arc comes in from outside).
+    broken: "cycle": p's last read goes back to s instead of t; "nosink": it goes nowhere (the work list runs empty) -- neither is a bubble, both fill
+    the table first.
+    -> dict(s, t1 = t^1, entries, far)"""
+    assert m1 >= 1 and m2 >= 1 and tips <= m2
+    s, p, q, z, t = gb.read(), gb.reads(m1), gb.reads(m2), gb.read(), gb.read()  # (t last: without tips t^1 can be the graph's last vertex)
+    gb.arc(gb.v(s), gb.v(p[0]), 1)
+    gb.arc(gb.v(s), gb.v(q[0]), 2)
+    gb.path(p, 3)
+    gb.path(q, 1)
+    gb.arc(gb.v(q[-1]), gb.v(t), 2)
+    if broken is None:
+        gb.arc(gb.v(p[-1]), gb.v(t), 1)
+    else:  # t keeps waiting for an arc from a ring the probe never reaches (else t, expanded, would leave p as the last open end: a bubble)
+        assert broken in ("cycle", "nosink")
+        gb.arc(gb.v(gb.ring(4)[1]), gb.v(t), 1)
+        if broken == "cycle":
+            gb.arc(gb.v(p[-1]), gb.v(s), 1)
+    gb.arc(gb.v(t), gb.v(z), 5)
+    if tips:
+        w = gb.reads(tips)
+        gb.arc(gb.v(q[:tips]), gb.v(w), 7)
+    far_p, far_q = 3 * (m1 - 1) + 2, m2 + 3 + (6 if tips else 0)
+    return dict(s=int(gb.v(s)), t1=int(gb.v(t)) ^ 1, entries=m1 + m2 + 1 + tips, far=far_p, far_is_last=far_p > far_q)
+
+
+def ladder_of(entries):
+    """(m1, m2) of the ladder whose probe holds `entries` vertices"""
+    return entries // 2, (entries - 1) // 2
+
+
+def fan_bubble(gb, k, tips=0):
+    """source s -> k middle reads -> sink t -> one more read: the probe's table holds k + 1 + tips entries, s and t^1 have k arcs each (the wave form stages
+    them 64 at a time).  tips: reads without arcs hanging off the first middles.  -> dict(s, t1, entries, far)"""
+    s, m, z, t = gb.read(), gb.reads(k), gb.read(), gb.read()
+    i = np.arange(k)
+    gb.arc(gb.v(s), gb.v(m), 10 + i)
+    gb.arc(gb.v(m), gb.v(t), 10 + i)
+    gb.arc(gb.v(t), gb.v(z), 5)
+    if tips:
+        gb.arc(gb.v(m[:tips]), gb.v(gb.reads(tips)), 4000)
+    return dict(s=int(gb.v(s)), t1=int(gb.v(t)) ^ 1, entries=k + 1 + tips, far=20 + 2 * (k - 1))
+
+
+def hub_bubble(gb, nv, special=None, pos=0, pre=12):
+    """the wave form's staging: source s -> c (a short chain), X, F.  F is expanded first and finds `pre` reads without arcs (13 .. 15 entries: tier 0 is
+    full), then X with exactly nv arcs, then only c is left on the work list: a bubble whose sink is c and whose pop trims the arc-less reads (n_tips).
+    X's arc at list position j is 100 + j long, d(X) = 2.  special at position pos of X's list:
+      "dead"     the arc is flagged deleted (to a read of its own): skipped, one tip fewer;
+      "v0_dead"  the arc goes back to s AND is flagged deleted: the check for the source comes first (asg.c:377-378), no bubble;
+      "far"      the arcs from pos on are all 100 + pos long: max_dist = far pops (d + l == max_dist at pos), far - 1 gives up exactly at pos.
+    -> dict(s, entries, n_tips, far)"""
+    assert nv >= 1 and 0 <= pos < nv
+    s, c, X, F = gb.read(), gb.reads(3), gb.read(), gb.read()
+    gb.arc(gb.v(s), gb.v([c[0], X, F]), [1, 2, 3])
+    gb.path(c, 1)
+    gb.arc(gb.v(F), gb.v(gb.reads(pre)), 1 + np.arange(pre) // 4)
+    j = np.arange(nv)
+    ln = 100 + (np.minimum(j, pos) if special == "far" else j)
+    y = gb.reads(nv)
+    keep = np.ones(nv, dtype=bool)
+    if special in ("dead", "v0_dead"):
+        keep[pos] = False
+        gb.arc(gb.v(X), gb.v(y[pos]) if special == "dead" else gb.v(s), int(ln[pos]), dead=True)
+    gb.arc(gb.v(X), gb.v(y[keep]), ln[keep])
+    n_tips = pre + int(keep.sum())
+    return dict(s=int(gb.v(s)), entries=3 + n_tips, n_tips=0 if special == "v0_dead" else n_tips, far=102 + pos, pops=special != "v0_dead")
+
+
+def tip_comb(depth, order="ascending", mixed=False):
+    """asg_cut_tip, a chain of dependent actions: a_1 -> a_2 -> ... -> a_D, every a_k with a second arc into a ring (so each is a fork: MULTI_OUT ends
+    the walk at once, whatever max_ext).  Only a_1 has nothing coming in; a_k becomes a tip when a_{k-1} is cut.  ascending: a_k's ids grow with k, the
+    reference's one sweep cuts all D, and the fixpoint needs D + 1 sweeps: sweep k is the first whose view holds the stamps of a_1 .. a_{k-1}, so it is the
+    first in which a_k acts, and sweep D + 1 is the first that changes nothing.  descending: the ids fall with k, a_2 never sees a dead a_1 (its stamp is
+    not smaller than a_2), one tip is cut, and the second sweep already changes nothing: 2 sweeps.  -> (graph, actions, sweeps)"""
+    gb = Gb(mixed)
+    h = gb.ring(depth + 3)
+    a = gb.reads(depth)
+    if order == "descending":
+        a = a[::-1]
+    gb.path(a, 10)
+    gb.arc(gb.v(a), gb.v(h[1:depth + 1]), 20)
+    gb.arc(gb.v(a[-1]), gb.v(h[depth + 1]), 30)
+    return gb.finish(), (depth if order == "ascending" else 1), (depth + 1 if order == "ascending" else 2)
+
+
+def internal_comb(depth, order="ascending", mixed=False):
+    """asg_cut_internal(max_ext = 1), the same dependency: v_1 -> v_2 -> ... -> v_D -> a ring, every v_k also entered from a ring vertex h_k (which has two
+    arcs out).  v_k is "internal" when h_k is its only way in (MULTI_NEI behind it) and its one arc leads to a vertex with other ways in (MULTI_NEI ahead):
+    true for v_1 from the start, for v_k once v_{k-1} is gone.  Sweeps as in tip_comb: D + 1 ascending, 2 descending.  -> (graph, actions, sweeps)"""
+    gb = Gb(mixed)
+    h = gb.ring(depth + 3)
+    g2 = gb.ring(4)
+    a = gb.reads(depth)
+    if order == "descending":
+        a = a[::-1]
+    gb.path(a, 10)
+    gb.arc(gb.v(h[1:depth + 1]), gb.v(a), 20)
+    gb.arc(gb.v(a[-1]), gb.v(g2[1]), 30)
+    return gb.finish(), (depth if order == "ascending" else 1), (depth + 1 if order == "ascending" else 2)
+
+
+def bubble_comb(depth, order="ascending", inner=1, big=100000):
+    """asg_pop_bubble, a chain of dependent pops: bubble k is S_k -> {A_k, L_k} -> T_k.  L_k is one read; the arc L_k -> T_k is short, but its mirror T_k^1 -> L_k^1
+    is `big`, longer than any max_dist.  A_1 is a chain of `inner` reads; A_k (k > 1) is a_k -> T_{k-1}^1 -> (the whole of bubble k-1, backwards) -> S_{k-1}^1:
+    while L_{k-1} lives, the probe from S_k meets the big arc out of T_{k-1}^1 and gives up (too far).  The pop from S_{k-1} keeps A (visited second: the shorter
+    arc out of S) and deletes L_{k-1} with the big arc, its mirror; from then on the way through bubble k-1 is a plain path and S_k is a bubble.  Ascending ids:
+    the reference pops all D in one sweep; in the fixpoint S_k pops first in sweep k (the first whose view holds S_{k-1}'s stamps), sweep D + 1 is the first that
+    changes nothing: D + 1 sweeps.  Descending (S_1 has the largest id): S_2 never sees S_1's stamps, one pop, 2 sweeps.  The probe from S_k holds about
+    4k + inner vertices: from some k on it overflows tier 0.  No T_k^1 ever pops (big arc, or one live arc).  -> (graph, pops, sweeps, max_dist)"""
+    gb = Gb()
+    n = inner + 3 + 4 * (depth - 1) + 1
+    ids = iter(np.arange(n) if order == "ascending" else np.arange(n)[::-1])
+    gb.reads(n)
+    rd = lambda: 2 * int(next(ids))
+    prev_s = prev_t = None
+    for k in range(depth):
+        S, L, T = rd(), rd(), rd()
+        if k == 0:
+            A = [rd() for _ in range(inner)]
+            gb.arc(S, A[0], 1)
+            gb.arc(A[:-1], A[1:], 1)
+            gb.arc(A[-1], T, 1)
+        else:
+            a = rd()
+            gb.arc(S, a, 1)
+            gb.arc(a, prev_t ^ 1, 1)
+            gb.arc(prev_s ^ 1, T, 1)
+        gb.arc(S, L, 2)
+        gb.arc2(L, T, 2, big)
+        prev_s, prev_t = S, T
+    gb.arc(prev_t, rd(), 1)
+    return gb.finish(d_len=0), (depth if order == "ascending" else 1), (depth + 1 if order == "ascending" else 2), 1000
+
+
+def stamped_hub(gb, nv, outer=True):
+    """the wave form against arcs that a SMALLER source's pop has stamped dead.  A fan S0 -> nv middles -> X^1; the pop from S0 keeps the way through ONE middle
+    (the second one visited: position nv - 2 of the lists, asserted by the test from the reference's result) and deletes every other arc into X^1 together with
+    its mirror, an arc out of X: X's list then holds nv - 1 arcs that are dead by their stamp alone, at every position but nv - 2.  Then (outer) a larger source s
+    as in hub_bubble: s -> c (a chain), X, F; F's 12 arc-less reads fill tier 0 first, then X is expanded, and its one live arc leads through S0^1 into c's third
+    read, the sink.  -> dict(S0, s, X, n_tips)"""
+    S0, m, Xr = gb.read(), gb.reads(nv), gb.read()
+    i = np.arange(nv)
+    gb.arc(gb.v(S0), gb.v(m), 10 + i)
+    gb.arc(gb.v(m), gb.v(Xr), 10 + i)
+    X = int(gb.v(Xr)) ^ 1
+    if not outer:
+        gb.arc(gb.v(Xr), gb.v(gb.read()), 1)  # (a sink needs an arc out)
+        return dict(S0=int(gb.v(S0)), X=X)
+    s, c, F = gb.read(), gb.reads(4), gb.read()
+    gb.arc(gb.v(s), [int(gb.v(c[0])), X, int(gb.v(F))], [1, 2, 3])
+    gb.path(c, 1)
+    gb.arc(gb.v(F), gb.v(gb.reads(12)), 1 + np.arange(12) // 4)
+    gb.arc(int(gb.v(S0)) ^ 1, gb.v(c[2]), 1)
+    return dict(S0=int(gb.v(S0)), s=int(gb.v(s)), X=X, n_tips=12)
+
+
+END_KINDS = ("TIP", "MULTI_OUT", "MULTI_NEI")
+
+
+def tip_piece(gb, n, end, ring):
+    """a chain of exactly n reads that starts at a dead end and ends in `end`: nothing at all (the whole piece is linear, both ends are tips), a fork
+    (two arcs into the ring) or one arc to a ring vertex, which has another way in.  asg_extend (asg.c:223-236) looks at the ends of at most max_ext
+    reads: the piece goes iff n <= max_ext."""
+    c = gb.reads(n)
+    gb.path(c, 10)
+    if end == "MULTI_OUT":
+        gb.arc(gb.v(c[-1]), gb.v(ring[[1, 3]]), [20, 30])
+    elif end == "MULTI_NEI":
+        gb.arc(gb.v(c[-1]), gb.v(ring[1]), 20)
+    return c
+
+
+def biloop_piece(gb, n, ov, ox, ring):
+    """asg.c:274-306: w -> c_1 -> ... -> c_n, c_n a fork (to w^1 and into the ring), and w -> c_n^1: the walk from v = c_1 ends MULTI_OUT at c_n within
+    max_ext iff n <= max_ext, x = c_n^1, and the arc w -> x goes iff ov (overlap of w -> v) > ox (overlap of w -> x)."""
+    w, c = gb.read(), gb.reads(n)
+    gb.arc(gb.v(w), gb.v(c[0]), 10, ov)
+    gb.path(c, 10)
+    gb.arc(gb.v(w), gb.v(c[-1]) ^ 1, 15, ox)
+    gb.arc(gb.v(c[-1]), gb.v(ring[1]), 20)
+    return w, c
+
+
+def chain_graph(L, ring=False, first=0, mixed=False, gb=None):
+    """L reads in one chain (or ring); position k of the chain holds read (k + first) mod L of the piece, so read 0 -- whose vertex is the smallest with an
+    arc, where the reference discovers the unitig -- stands at position L - first.  With gb=None the chain is the WHOLE graph (V == 2L)."""
+    own = gb is None
+    gb = Gb(mixed) if own else gb
+    r = gb.reads(L)
+    r = np.r_[r[first:], r[:first]] if first else r
+    gb.path(np.r_[r, r[:1]] if ring else r, 700 + np.arange(L - 1 + (1 if ring else 0)) % 50)
+    return gb.finish(d_len=7) if own else r

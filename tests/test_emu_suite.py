@@ -7,7 +7,10 @@ nothing about speed, stream ordering or memory-model behaviour, which only the `
 
 By default a subset runs; MA_EMU_FULL=1 runs every GPU test module except the BASELINE-scale inputs and the RCCL tests (about 25 minutes
 on 8 cores).  The default `-m "not gpu"` selection of this file took 12 min 46 s of wall time on 8 cores before tests/test_gpu_graph_edges.py was
-added; that module adds about half a minute (15 s in normal order, 16 s reversed with guard pages), so none of its cases is held back for MA_EMU_FULL."""
+added; that module adds about half a minute (15 s in normal order, 16 s reversed with guard pages), so none of its cases is held back for MA_EMU_FULL.
+tests/test_gpu_clean_edges.py adds about a minute: 30 s in normal order (its three child processes and the 8 193-bubble input, 2 s, included) and 30 s
+reversed with guard pages.  Its 196 608 / 196 609-entry probes take 63 s alone and are held back for MA_EMU_FULL=1, so by default the CPU build does not reach
+bubble tiers 3 and 4; they run by default under `-m gpu`."""
 import os
 import subprocess
 import sys
@@ -72,6 +75,7 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     run_gpu_tests(["tests/test_gpu_parity.py", "-k", "noisy or deep_groups or sort_random", "tests/test_gpu_ingest.py"], 3000, env)
     run_gpu_tests(["tests/test_gpu_fused_hits.py", "-k", "group_size_edges"], 3000, env)  # tier B's global scratch (4097 and 9001 hits) ends at a guard page too
     run_gpu_tests(["tests/test_gpu_graph_edges.py"], 3000, env)  # the arc sort's rows, the reduction's neighbour lists and the cleanup's tails at their size edges
+    run_gpu_tests(["tests/test_gpu_clean_edges.py"] + CLEAN_EDGES_SEL, 3000, env)  # the bubble tables, stacks and stamp arrays at their borders; the wave form without lock-step
 
 
 def test_kernels_graph_api_on_cpu(emu_built):
@@ -84,6 +88,15 @@ def test_graph_size_edges_on_cpu(emu_built):
     """tests/test_gpu_graph_edges.py: the graph kernels at every size edge they branch on (arcs per read, arcs per vertex and per expanded neighbour, arc counts
     of the cleanup), every one against the oracle and the reference library; a quarter of a minute"""
     run_gpu_tests(["tests/test_gpu_graph_edges.py"], 1800)
+
+
+CLEAN_EDGES_SEL = [] if FULL else ["-k", "not border[3]"]  # the 196 608 / 196 609-entry probes (tiers 3 and 4): MA_EMU_FULL=1
+
+
+def test_cleaner_and_unitig_size_edges_on_cpu(emu_built):
+    """tests/test_gpu_clean_edges.py: cleaners, unitigs and the scan at every size they branch on, the child-process cases included, every one against the
+    reference library"""
+    run_gpu_tests(["tests/test_gpu_clean_edges.py"] + CLEAN_EDGES_SEL, 3000)
 
 
 def test_tie_filter_on_cpu(emu_built):
