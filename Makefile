@@ -1,5 +1,5 @@
 # Top-level build: HIP kernels (gfx950) + host C -> miniasm_amd/lib/libminiasm_amd.so, the miniasm CLI,
-# the synthetic PAF generator, the CPU oracle (tests only) and the link-level drop-in check.
+# the synthetic PAF and reads-file generators, the CPU oracle (tests only) and the link-level drop-in check.
 #   make            everything
 #   make lib        just the library
 # hipcc cross-compiles gfx950 without a GPU present.
@@ -22,7 +22,7 @@ HIP_OBJ   = $(addprefix $(B)/,$(addsuffix .hip.o,$(HIP_SRC)))
 HOST_OBJ  = $(addprefix $(B)/,$(addsuffix .o,$(HOST_SRC)))
 
 LIB       = $(PKG)/lib/libminiasm_amd.so
-BIN       = $(PKG)/bin/miniasm $(PKG)/bin/pafgen
+BIN       = $(PKG)/bin/miniasm $(PKG)/bin/pafgen $(PKG)/bin/readgen
 CORE_TEST = $(PKG)/lib/libma_core_host.so $(PKG)/lib/libclean_host.so
 
 .PHONY: all lib oracle dropin clean
@@ -47,6 +47,10 @@ $(PKG)/bin/miniasm: $(HOST)/cli.c $(LIB) | $(PKG)/bin
 
 $(PKG)/bin/pafgen: tools/pafgen.c | $(PKG)/bin
 	$(CC) -O2 -Wall -o $@ tools/pafgen.c -lm
+
+# a reads file that matches a PAF (tests and timing of `miniasm -f`)
+$(PKG)/bin/readgen: tools/readgen.c | $(PKG)/bin
+	$(CC) -O2 -Wall -o $@ tools/readgen.c
 
 # ma_core.h compiled for the host: lets the CPU tests check the per-hit arithmetic against the reference
 $(PKG)/lib/libma_core_host.so: tests/core_host.c $(CSRC)/ma_core.h | $(PKG)/lib

@@ -224,13 +224,56 @@ int mahip_clean_last(mahip_ctx_t *c, mahip_clean_info_t *out);
  * reference sorts them with its own sort afterwards, asm.c:208). */
 int mahip_ug_gen(mahip_ctx_t *c, uint32_t *n_utg, uint32_t *n_members, uint32_t *n_uarc);
 int mahip_ug_download(mahip_ctx_t *c, uint32_t *u_n, uint32_t *u_len, uint32_t *u_start, uint32_t *u_end, uint32_t *u_off, uint64_t *members, asg_arc_t *uarcs);
-/* asm.c:216-290 ma_ug_seq as a device byte gather (csrc/useq.hip).  The host reads the sequence file and hands the bases of the
+/* asm.c:216-290 ma_ug_seq as a device byte gather (csrc/useq.hip).  Host reader (gzip, stdin, files outside the regular form below): it reads the sequence file and hands the bases of the
  * reads that sit on a unitig over in batches; a job copies `len` bases from the batch buffer to the unitig arena -- the first `len`
  * bases at src_off (forward) or the reverse complement of the last `len` of the src_len bases there (reverse). */
 typedef struct { uint64_t src_off, dst_off; uint32_t src_len, len; uint32_t rev, pad; } mahip_useq_job_t;
 int mahip_useq_begin(mahip_ctx_t *c, size_t arena_bytes);          /* arena of all unitig strings, filled with 'N' */
 int mahip_useq_batch(mahip_ctx_t *c, const char *h_seq, size_t seq_bytes, const mahip_useq_job_t *h_jobs, size_t n_jobs);
 int mahip_useq_end(mahip_ctx_t *c, char *h_arena);                 /* the arena back to the host */
+/* The reads file read on the device (csrc/useq.hip, replaces kseq.h:192-232 kseq_read + sdict.c sd_get + the copy loops of asm.c:262-284 for files in the
+ * REGULAR FORM): the whole text goes to HBM, a newline census and a scan give every line its start, one pass over the lines checks the form, the wanted reads'
+ * names go into a hash table that every record's name is looked up in, and the bases are copied from the text into the arena of mahip_useq_begin.
+ * Regular form = the line index alone fixes the records, and kseq reads the same ones: no '\r' byte; no NUL byte (the reference's names are C strings, asm.c:266:
+ * a NUL ends one); no line of 16 MiB or more inside a wrapped FASTA record (the placement sums 256 line lengths in 32 bits); first byte '>' (FASTA: every line that begins with '>' is
+ * a header, no other non-empty line begins with '@' or '+', empty lines are skipped, sequences may be wrapped) or '@' (FASTQ: four lines a record -- '@' header,
+ * a sequence line beginning with none of '>' '@' '+', a '+' line, a quality line of exactly the sequence's length); at most 2^32 - 1 lines.  Anything else comes
+ * back as regular = 0 with a reason; that is not an error: the caller keeps its host reader (host/unitig_gfa.c). */
+enum { MAHIP_FASTX_OK = 0, MAHIP_FASTX_CR, MAHIP_FASTX_FIRST_BYTE, MAHIP_FASTX_FASTA_LINE_START, MAHIP_FASTX_FASTQ_SHAPE, MAHIP_FASTX_FASTQ_QUAL_LEN, MAHIP_FASTX_TOO_MANY_LINES,
+       MAHIP_FASTX_NOMEM, MAHIP_FASTX_SHORT_READ, MAHIP_FASTX_NOT_PLAIN, MAHIP_FASTX_FORCED, MAHIP_FASTX_NUL_BYTE, MAHIP_FASTX_LONG_LINE };
+enum { MAHIP_FASTX_FASTA = 1, MAHIP_FASTX_FASTQ = 2 };
+typedef struct {
+	int format;               /* MAHIP_FASTX_FASTA / _FASTQ by the first byte, 0: neither */
+	uint64_t n_lines;         /* a last line without '\n' counts */
+	uint64_t n_records;       /* FASTA: header lines; FASTQ: n_lines / 4 */
+	uint64_t n_cr;            /* '\r' bytes */
+	int regular, reason;      /* regular = 1 <=> reason == MAHIP_FASTX_OK */
+} mahip_fastx_info_t;
+int mahip_fastx_load_mem(mahip_ctx_t *c, const void *text, size_t nbytes);  /* nbytes > 0 */
+int mahip_fastx_load_fd(mahip_ctx_t *c, int fd, size_t nbytes);             /* bytes [0,nbytes) of an open plain file; 1: no device memory for it, -1: error */
+int mahip_fastx_index(mahip_ctx_t *c, mahip_fastx_info_t *info);            /* returns 0 with reason _NOMEM when the index does not fit */
+int mahip_fastx_release(mahip_ctx_t *c);                                    /* the text, the index and the lookup tables go back to the pool */
+const char *mahip_fastx_reason_name(int reason);
+/* for stage tests: out[0 .. n_lines] = offset of the first byte of every line, out[n_lines] = nbytes (+ 1 when the last line has no '\n'): line i is bytes
+ * [out[i], out[i+1] - 1); and, for a regular text, where every record's name stands in it (n_records entries each) */
+int mahip_fastx_line_starts(mahip_ctx_t *c, uint64_t *out);
+int mahip_fastx_name_spans(mahip_ctx_t *c, uint64_t *off, uint32_t *len);
+/* A read that sits on a unitig: its name (bytes [name_off, name_off + name_len) of `names`, exact byte string as sd_get compares it, sdict.c), where its
+ * `len` bases go, the strand, and the kept interval [s, e) of the read they are taken from (whole = 1: the whole record, as ma_ug_seq without `sub`).
+ * Forward: the first len bases of the interval; reverse: the reverse complement of its last len (asm.c:275-283). */
+typedef struct { uint64_t dst_off, name_off; uint32_t name_len, len, s, e, rev, whole; } mahip_useq_want_t;
+/* between mahip_useq_begin and mahip_useq_end, on a regular text: looks every record's name up (names are distinct; a name the file carries more than once
+ * takes its LAST record, as the reference's loop does) and copies.  n_matched = wanted reads found, n_dup = matching records beyond the first of a name, n_short =
+ * matching records with fewer bases than the placement needs (e, or len with whole).  n_short > 0: NOTHING is placed -- the caller falls back to its host reader,
+ * which keeps the reference's behaviour for such files.  laps_ms (optional): wall time of lookup and placement (the latter costs a stream sync). */
+int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes,
+                          uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms);
+/* What the LAST ma_ug_seq of this context did (host bookkeeping, noted by host/unitig_gfa.c through mahip_useq_note; the tests assert from it that an input reached
+ * the reader it was built for): reader 1 = host, 2 = device; reason: why the host reader ran (MAHIP_FASTX_*). */
+enum { MAHIP_USEQ_HOST = 1, MAHIP_USEQ_DEVICE = 2 };
+typedef struct { int reader, reason, format; uint64_t n_records, n_matched, n_dup, n_short; } mahip_useq_info_t;
+void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in);
+int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out);
 uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
 /* how many device-wide scans (csrc/scan.hip) of this context, since it was created, took each form: one tile (k_scan_down alone, n <= 2048), the chained
  * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */

@@ -69,6 +69,26 @@ class TieInfo(C.Structure):  # include/mahip.h: mahip_tie_info_t
                 ("arc_walk", C.c_int), ("hit_walk", C.c_int), ("unrepaired", C.c_int), ("push_conflicts_seen", C.c_uint64), ("hit_walk_reads", C.c_uint64)]
 
 
+class FastxInfo(C.Structure):  # include/mahip.h: mahip_fastx_info_t
+    _fields_ = [("format", C.c_int), ("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("n_cr", C.c_uint64), ("regular", C.c_int), ("reason", C.c_int)]
+
+
+class UseqWant(C.Structure):  # include/mahip.h: mahip_useq_want_t
+    _fields_ = [("dst_off", C.c_uint64), ("name_off", C.c_uint64), ("name_len", C.c_uint32), ("len", C.c_uint32), ("s", C.c_uint32), ("e", C.c_uint32),
+                ("rev", C.c_uint32), ("whole", C.c_uint32)]
+
+
+class UseqInfo(C.Structure):  # include/mahip.h: mahip_useq_info_t
+    _fields_ = [("reader", C.c_int), ("reason", C.c_int), ("format", C.c_int), ("n_records", C.c_uint64), ("n_matched", C.c_uint64), ("n_dup", C.c_uint64),
+                ("n_short", C.c_uint64)]
+
+
+# include/mahip.h: MAHIP_FASTX_* reasons, formats, MAHIP_USEQ_* readers
+FASTX_REASONS = ["OK", "CR", "FIRST_BYTE", "FASTA_LINE_START", "FASTQ_SHAPE", "FASTQ_QUAL_LEN", "TOO_MANY_LINES", "NOMEM", "SHORT_READ", "NOT_PLAIN", "FORCED", "NUL_BYTE", "LONG_LINE"]
+FASTX_FORMATS = {0: None, 1: "fasta", 2: "fastq"}
+USEQ_READERS = {0: None, 1: "host", 2: "device"}
+
+
 class ProfRec(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -145,6 +165,18 @@ def lib():
         L.mahip_prof_get.argtypes = [vp, C.POINTER(ProfRec), i32]
         L.mahip_mem_bytes.restype = sz
         L.mahip_mem_bytes.argtypes = [vp]
+        L.mahip_fastx_load_mem.argtypes = [vp, vp, sz]
+        L.mahip_fastx_load_fd.argtypes = [vp, i32, sz]
+        L.mahip_fastx_index.argtypes = [vp, C.POINTER(FastxInfo)]
+        L.mahip_fastx_release.argtypes = [vp]
+        L.mahip_fastx_line_starts.argtypes = [vp, vp]
+        L.mahip_fastx_name_spans.argtypes = [vp, vp, vp]
+        L.mahip_useq_begin.argtypes = [vp, sz]
+        L.mahip_useq_end.argtypes = [vp, vp]
+        L.mahip_useq_place_text.argtypes = [vp, vp, sz, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+        L.mahip_useq_last.argtypes = [vp, C.POINTER(UseqInfo)]
+        L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
+        L.mahip_scan_forms.restype = None
         L.ma_opt_init.argtypes = [C.POINTER(MaOpt)]
         L.sd_init.restype = C.POINTER(Sdict)
         L.sd_destroy.argtypes = [C.POINTER(Sdict)]
@@ -328,6 +360,59 @@ class Ctx:
         for p in (g.arc, g.seq, g.idx):
             lib().free_buf(p)
         return arcs, seq, idx
+
+    # ---- the reads file as text (csrc/useq.hip): for stage tests
+    def fastx_load(self, text):
+        """a FASTA/FASTQ text (bytes) into HBM"""
+        _chk(lib().mahip_fastx_load_mem(self.h, text, len(text)), "fastx_load_mem")
+
+    def fastx_index(self):
+        """line index + form check -> dict(format, n_lines, n_records, n_cr, regular, reason) with format / reason as names"""
+        fi = FastxInfo()
+        _chk(lib().mahip_fastx_index(self.h, C.byref(fi)), "fastx_index")
+        return dict(format=FASTX_FORMATS[fi.format], n_lines=fi.n_lines, n_records=fi.n_records, n_cr=fi.n_cr, regular=bool(fi.regular), reason=FASTX_REASONS[fi.reason])
+
+    def fastx_line_starts(self, n_lines):
+        out = np.zeros(n_lines + 1, dtype=np.uint64)
+        _chk(lib().mahip_fastx_line_starts(self.h, out.ctypes.data), "fastx_line_starts")
+        return out
+
+    def fastx_names(self, text, n_records):
+        """the records' names as the device delimits them, cut out of `text` (the bytes that were loaded)"""
+        off, ln = np.zeros(max(n_records, 1), dtype=np.uint64), np.zeros(max(n_records, 1), dtype=np.uint32)
+        _chk(lib().mahip_fastx_name_spans(self.h, off.ctypes.data, ln.ctypes.data), "fastx_name_spans")
+        return [text[int(o):int(o) + int(l)] for o, l in zip(off[:n_records], ln[:n_records])]
+
+    def fastx_release(self):
+        _chk(lib().mahip_fastx_release(self.h), "fastx_release")
+
+    def useq_place_text(self, arena_bytes, wanted):
+        """wanted: dicts(name, dst_off, len, rev, s, e) with e = None for the whole record -> (arena bytes, n_matched, n_dup, n_short);
+        the text must be loaded and indexed (regular)"""
+        L = lib()
+        arr = (UseqWant * max(len(wanted), 1))()
+        blob = b""
+        for k, w in enumerate(wanted):
+            arr[k] = UseqWant(w["dst_off"], len(blob), len(w["name"]), w["len"], w.get("s") or 0, w["e"] if w.get("e") is not None else 0, 1 if w["rev"] else 0, 1 if w.get("e") is None else 0)
+            blob += w["name"]
+        _chk(L.mahip_useq_begin(self.h, arena_bytes), "useq_begin")
+        nm, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(L.mahip_useq_place_text(self.h, C.addressof(arr), len(wanted), blob, len(blob), C.byref(nm), C.byref(nd), C.byref(ns), None), "useq_place_text")
+        out = C.create_string_buffer(max(arena_bytes, 1))
+        _chk(L.mahip_useq_end(self.h, out), "useq_end")
+        return out.raw[:arena_bytes], nm.value, nd.value, ns.value
+
+    def useq_last(self):
+        """which reader the context's last ma_ug_seq used, and why"""
+        u = UseqInfo()
+        _chk(lib().mahip_useq_last(self.h, C.byref(u)), "useq_last")
+        return dict(reader=USEQ_READERS[u.reader], reason=FASTX_REASONS[u.reason], format=FASTX_FORMATS[u.format], n_records=u.n_records, n_matched=u.n_matched, n_dup=u.n_dup, n_short=u.n_short)
+
+    def scan_forms(self):
+        """device-wide scans of this context so far by form: (one tile, chained, three-phase)"""
+        out = (C.c_uint64 * 3)()
+        lib().mahip_scan_forms(self.h, C.byref(out))
+        return tuple(out)
 
     # ---- instrumentation
     def prof_enable(self, on=True):

@@ -142,7 +142,7 @@ int dev_reserve(mahip_ctx *c, DevBuf &b, size_t bytes)
 		if (pool_take(c, want, &b.p, &b.cap) != 0) { b.p = nullptr; b.cap = 0; return -1; }
 	} else {
 		hipError_t e = hipMalloc(&b.p, want);
-		if (e != hipSuccess) { b.p = nullptr; mahip_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); return -1; }
+		if (e != hipSuccess) { (void)hipGetLastError(); b.p = nullptr; mahip_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e)); return -1; }
 		b.cap = want;
 	}
 	c->mem_bytes += b.cap;

@@ -1,12 +1,20 @@
 // useq.hip -- unitig sequences on the device (reference asm.c:216-290 ma_ug_seq): every read placed on a unitig contributes the
 // first `len` bases of its kept interval (forward) or the reverse complement of its last `len` bases (reverse strand).
-// The host reads the FASTA/FASTQ records (gzip or plain: a byte stream only one thread can inflate) and hands the bases of the
-// PLACED reads over in batches; the placement itself is a byte gather: one block per read, coalesced 1-byte loads / stores,
+// A plain reads file in the regular form is read here, on the device (second half of this file).  Otherwise the host reads the
+// FASTA/FASTQ records (gzip or stdin: a byte stream only one thread can inflate) and hands the bases of the PLACED reads over in batches; the placement itself is a byte gather: one block per read, coalesced 1-byte loads / stores,
 // complement through a 128-entry table in LDS.  HBM-bound by construction (bytes in = bytes out); the unitig arena stays in
 // HBM until the last batch and comes back once.
 #include "mahip_internal.hpp"
 
-struct UseqBufs { DevBuf arena, seq, jobs; size_t arena_bytes = 0; };
+struct UseqBufs {
+	DevBuf arena, seq, jobs; size_t arena_bytes = 0;
+	// the reads file as text (second half of this file): the text, newline counts of the granules and their scan, line starts, FASTA header flags and their
+	// scan, header line of every record, counters; the wanted reads, their names, hashes, the table over them and the record each of them takes
+	DevBuf fx_text, fx_gcnt, fx_gpos, fx_ls, fx_hdr, fx_hpos, fx_recl, fx_ctr, fx_want, fx_wname, fx_whash, fx_tab, fx_win;
+	size_t fx_n = 0; uint32_t fx_L = 0, fx_R = 0; int fx_format = 0; bool fx_loaded = false, fx_regular = false;
+	mahip_useq_info_t last = {0, 0, 0, 0, 0, 0, 0};
+};
+static void fx_drop(mahip_ctx *c, UseqBufs *b);
 
 static UseqBufs *useq_bufs(mahip_ctx *c)
 {
@@ -19,6 +27,7 @@ void useq_free(mahip_ctx *c)
 	UseqBufs *b = (UseqBufs*)c->useq;
 	if (!b) return;
 	dev_free(c, b->arena); dev_free(c, b->seq); dev_free(c, b->jobs);
+	fx_drop(c, b);
 	delete b;
 	c->useq = nullptr;
 }
@@ -81,3 +90,437 @@ extern "C" int mahip_useq_end(mahip_ctx_t *c, char *h_arena)
 	if (b->arena_bytes) CHK(xfer_copy(c, b->arena.p, h_arena, b->arena_bytes, 0));
 	return 0;
 }
+
+// ================================================================================================ the reads file on the device
+// FASTA/FASTQ text in HBM -> line index -> form check -> name lookup -> placement straight from the text ("reads file").
+// The reference's reader (kseq.h:192-232) is sequential in general: the quality length is defined by the sequence length, and '@', '+', '>' may begin a
+// quality line.  Here the device VERIFIES that the file is in a form where the line index alone fixes the record structure and where kseq reads the same
+// records (the "regular form", see mahip.h); anything else is reported with a reason and the caller keeps its host reader.
+//   FASTA: first byte '>'; every line beginning with '>' is a header (kseq.h:209/214), every other non-empty line is a sequence line (kseq.h:211-212) and
+//          must not begin with '@' or '+' (they end the sequence loop, kseq.h:209); empty lines are skipped (kseq.h:210).
+//   FASTQ: four lines a record: '@' header, a sequence line that begins with none of '>' '@' '+', a '+' line (kseq.h:226 skips it), a quality line of
+//          exactly the sequence's length (kseq.h:228 reads ONE line then and stops; any other length makes kseq_read return -2 at kseq.h:230, or makes it
+//          read on into the next record).
+//   no '\r' anywhere (kseq.h:146 drops one only from lines longer than 1).
+#define FX_GRAN 1024u
+#define FX_LONG_LINE ((uint64_t)1 << 24) // 256 lines shorter than this: their bases sum up in 32 bits (k_fx_place)
+enum { FX_NL = 0, FX_CR, FX_FIRST, FX_LAST, FX_V_FASTA, FX_V_SHAPE, FX_V_QUAL, FX_MATCH, FX_DISTINCT, FX_SHORT, FX_NUL, FX_V_LONG, FX_NCTR = 16 };
+
+struct FxText { const unsigned char *t; const uint64_t *ls; const uint32_t *recl; uint64_t n; uint32_t L, R; int fq; };
+
+// bit 7 of every byte of w that equals the byte repeated in pat
+__device__ __forceinline__ uint32_t fx_eq(uint32_t w, uint32_t pat) { const uint32_t x = w ^ pat; return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
+// 16 bytes at off (a multiple of 16); bytes behind the text read as 0xff (none of the bytes that are counted)
+__device__ __forceinline__ uint4 fx_load16(const unsigned char *__restrict__ t, uint64_t n, uint64_t off)
+{
+	if (off + 16 <= n) return *(const uint4*)(t + off);
+	uint32_t w[4] = {~0u, ~0u, ~0u, ~0u};
+	for (uint32_t k = 0; k < 16 && off + k < n; ++k) w[k >> 2] ^= (uint32_t)(t[off + k] ^ 0xffu) << (8 * (k & 3));
+	return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// one wave per 1 KiB granule: cnt[g] = its newlines; totals of '\n', '\r' and NUL; the first and the last byte of the text
+__global__ __launch_bounds__(256) void k_fx_census(const unsigned char *__restrict__ t, uint64_t n, uint32_t n_gran, uint32_t *__restrict__ cnt, unsigned long long *__restrict__ ctr)
+{
+	const uint32_t lane = threadIdx.x & 63, n_waves = gridDim.x * 4u;
+	uint64_t nl = 0, cr = 0, nul = 0;
+	for (uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6); g < n_gran; g += n_waves) { // the whole wave
+		const uint4 v = fx_load16(t, n, (uint64_t)g * FX_GRAN + lane * 16u);
+		const uint32_t a = (uint32_t)(__popc(fx_eq(v.x, 0x0a0a0a0au)) + __popc(fx_eq(v.y, 0x0a0a0a0au)) + __popc(fx_eq(v.z, 0x0a0a0a0au)) + __popc(fx_eq(v.w, 0x0a0a0a0au)));
+		cr += (uint32_t)(__popc(fx_eq(v.x, 0x0d0d0d0du)) + __popc(fx_eq(v.y, 0x0d0d0d0du)) + __popc(fx_eq(v.z, 0x0d0d0d0du)) + __popc(fx_eq(v.w, 0x0d0d0d0du)));
+		nul += (uint32_t)(__popc(fx_eq(v.x, 0u)) + __popc(fx_eq(v.y, 0u)) + __popc(fx_eq(v.z, 0u)) + __popc(fx_eq(v.w, 0u)));
+		const uint32_t s = wv_sum_u32(a);
+		if (lane == 0) cnt[g] = s;
+		nl += a;
+	}
+	blk_add_u64(ctr + FX_NL, nl);
+	blk_add_u64(ctr + FX_CR, cr);
+	blk_add_u64(ctr + FX_NUL, nul);
+	if (blockIdx.x == 0 && threadIdx.x == 0) { ctr[FX_FIRST] = t[0]; ctr[FX_LAST] = t[n - 1]; }
+}
+
+// ls[i] = offset of the first byte of line i; line i is bytes [ls[i], ls[i + 1] - 1).  ls[L] = n behind a final newline, n + 1 without one.
+__global__ __launch_bounds__(256) void k_fx_lines(const unsigned char *__restrict__ t, uint64_t n, uint32_t n_gran, const uint32_t *__restrict__ gpos, uint32_t L, uint64_t *__restrict__ ls)
+{
+	const uint32_t lane = threadIdx.x & 63, n_waves = gridDim.x * 4u;
+	for (uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6); g < n_gran; g += n_waves) { // the whole wave
+		const uint64_t off = (uint64_t)g * FX_GRAN + lane * 16u;
+		const uint4 v = fx_load16(t, n, off);
+		const uint32_t m[4] = {fx_eq(v.x, 0x0a0a0a0au), fx_eq(v.y, 0x0a0a0a0au), fx_eq(v.z, 0x0a0a0a0au), fx_eq(v.w, 0x0a0a0a0au)};
+		const uint32_t a = (uint32_t)(__popc(m[0]) + __popc(m[1]) + __popc(m[2]) + __popc(m[3]));
+		uint32_t at = gpos[g] + (uint32_t)wv_scan_incl_i32((int)a, lane) - a + 1u; // line that starts behind this lane's first newline
+		if (a) for (uint32_t k = 0; k < 16; ++k) if (m[k >> 2] >> (8 * (k & 3) + 7) & 1u) ls[at++] = off + k + 1;
+	}
+	if (blockIdx.x == 0 && threadIdx.x == 0) { ls[0] = 0; if (t[n - 1] != '\n') ls[L] = n + 1; }
+}
+
+__device__ __forceinline__ uint32_t fx_first(const FxText &x, uint32_t i) { const uint64_t b = x.ls[i]; return x.ls[i + 1] - 1 > b ? x.t[b] : 0u; } // 0: an empty line
+
+// FASTA: header flags, the lines that may not be there, and lines of FX_LONG_LINE bytes or more in a record of several lines
+__global__ __launch_bounds__(256) void k_fx_form_fasta(const FxText x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr)
+{
+	uint64_t bad = 0, lng = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < x.L; i += (uint64_t)gridDim.x * 256u) {
+		const uint32_t ch = fx_first(x, (uint32_t)i);
+		hdr[i] = ch == '>';
+		bad += ch == '@' || ch == '+';
+		if (ch != '>' && x.ls[i + 1] - 1 - x.ls[i] >= FX_LONG_LINE) // (line 0 is a header) fine as the only line of its record: that one is copied without a scan
+			lng += fx_first(x, (uint32_t)i - 1) != '>' || (i + 1 < x.L && fx_first(x, (uint32_t)i + 1) != '>');
+	}
+	blk_add_u64(ctr + FX_V_FASTA, bad);
+	blk_add_u64(ctr + FX_V_LONG, lng);
+}
+// recl[r] = header line of record r, recl[R] = L
+__global__ __launch_bounds__(256) void k_fx_rec_lines(const uint32_t *__restrict__ hdr, const uint32_t *__restrict__ hpos, uint32_t L, uint32_t *__restrict__ recl)
+{
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < L; i += (uint64_t)gridDim.x * 256u) if (hdr[i]) recl[hpos[i]] = (uint32_t)i;
+	if (blockIdx.x == 0 && threadIdx.x == 0) recl[hpos[L]] = L;
+}
+// FASTQ: record r = lines 4r .. 4r + 3 (L is a multiple of 4)
+__global__ __launch_bounds__(256) void k_fx_form_fastq(const FxText x, unsigned long long *__restrict__ ctr)
+{
+	uint64_t shape = 0, qual = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < x.R; r += (uint64_t)gridDim.x * 256u) {
+		const uint32_t i = (uint32_t)r * 4u, c0 = fx_first(x, i), c1 = fx_first(x, i + 1), c2 = fx_first(x, i + 2);
+		shape += c0 != '@' || c1 == '>' || c1 == '@' || c1 == '+' || c2 != '+';
+		qual += x.ls[i + 2] - x.ls[i + 1] != x.ls[i + 4] - x.ls[i + 3];
+	}
+	blk_add_u64(ctr + FX_V_SHAPE, shape);
+	blk_add_u64(ctr + FX_V_QUAL, qual);
+}
+
+// record r: its header line, its sequence lines [*j0, *j1) and the bases they hold (every line of the stretch ends with one byte that is not a base)
+__device__ __forceinline__ uint32_t fx_record(const FxText &x, uint32_t r, uint32_t *j0, uint32_t *j1, uint64_t *nb)
+{
+	const uint32_t h = x.fq ? r * 4u : x.recl[r];
+	*j0 = h + 1; *j1 = x.fq ? h + 2 : x.recl[r + 1];
+	*nb = x.ls[*j1] - x.ls[*j0] - (*j1 - *j0);
+	return h;
+}
+// the name: the header's bytes behind the marker up to the first white space (kseq.h:203, isspace without '\r' and with the line end as the limit)
+__device__ __forceinline__ uint32_t fx_name(const FxText &x, uint32_t h, uint64_t *off)
+{
+	const uint64_t b = x.ls[h] + 1, e = x.ls[h + 1] - 1;
+	uint64_t p = b;
+	for (; p < e; ++p) { const unsigned ch = x.t[p]; if (ch == ' ' || ch == '\t' || ch == '\v' || ch == '\f') break; }
+	*off = b;
+	return (uint32_t)(p - b);
+}
+__device__ __forceinline__ uint64_t fx_hash(const unsigned char *s, uint32_t l)
+{ // FNV-1a, 64 bits
+	uint64_t h = 0xcbf29ce484222325ull;
+	for (uint32_t k = 0; k < l; ++k) h = (h ^ s[k]) * 0x100000001b3ull;
+	return h;
+}
+__global__ __launch_bounds__(256) void k_fx_name_spans(const FxText x, uint64_t *__restrict__ off, uint32_t *__restrict__ len)
+{
+	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < x.R; r += (uint64_t)gridDim.x * 256u) {
+		uint32_t j0, j1; uint64_t nb;
+		len[r] = fx_name(x, fx_record(x, (uint32_t)r, &j0, &j1, &nb), &off[r]);
+	}
+}
+
+// the wanted reads (distinct names) into an open-addressing table: tab[slot] = index + 1, linear probing
+__global__ __launch_bounds__(256) void k_fx_tab_build(const mahip_useq_want_t *__restrict__ want, const unsigned char *__restrict__ wname, uint32_t n_want, uint64_t *__restrict__ whash,
+                                                      uint32_t *__restrict__ tab, uint32_t mask)
+{
+	for (uint32_t w = blockIdx.x * 256u + threadIdx.x; w < n_want; w += gridDim.x * 256u) {
+		const uint64_t h = fx_hash(wname + want[w].name_off, want[w].name_len);
+		whash[w] = h;
+		uint32_t s = (uint32_t)h & mask;
+		while (atomicCAS(&tab[s], 0u, w + 1u) != 0u) s = (s + 1u) & mask;
+	}
+}
+// every record's name against the table; a wanted read keeps the LAST record that carries its name (the reference's loop overwrites, asm.c:262-284)
+__global__ __launch_bounds__(256) void k_fx_probe(const FxText x, const mahip_useq_want_t *__restrict__ want, const unsigned char *__restrict__ wname, const uint64_t *__restrict__ whash,
+                                                  const uint32_t *__restrict__ tab, uint32_t mask, uint32_t *__restrict__ win, unsigned long long *__restrict__ ctr)
+{
+	uint64_t n_match = 0, n_distinct = 0, n_short = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < x.R; r += (uint64_t)gridDim.x * 256u) {
+		uint32_t j0, j1; uint64_t nb, off;
+		const uint32_t l = fx_name(x, fx_record(x, (uint32_t)r, &j0, &j1, &nb), &off);
+		if (l == 0) continue; // an empty name matches nothing
+		const unsigned char *s = x.t + off;
+		const uint64_t h = fx_hash(s, l);
+		for (uint32_t p = (uint32_t)h & mask;; p = (p + 1u) & mask) {
+			const uint32_t e = tab[p];
+			if (e == 0) break;
+			const mahip_useq_want_t wt = want[e - 1];
+			if (whash[e - 1] != h || wt.name_len != l) continue;
+			const unsigned char *q = wname + wt.name_off;
+			uint32_t k = 0;
+			while (k < l && q[k] == s[k]) ++k;
+			if (k < l) continue;
+			++n_match;
+			n_distinct += atomicMax(&win[e - 1], (uint32_t)r + 1u) == 0u;
+			n_short += nb < (uint64_t)(wt.whole ? wt.len : wt.e);
+			break;
+		}
+	}
+	blk_add_u64(ctr + FX_MATCH, n_match);
+	blk_add_u64(ctr + FX_DISTINCT, n_distinct);
+	blk_add_u64(ctr + FX_SHORT, n_short);
+}
+
+// one block per wanted read: its bases from the text into the arena, forward or reverse complement as k_useq_gather does it.  A sequence on one line
+// (FASTQ, unwrapped FASTA) is a straight coalesced copy; a wrapped one goes through 256 lines at a time: their lengths are scanned into base offsets in
+// LDS and every base finds its line by a binary search there (8 steps), so consecutive lanes still read consecutive bytes except at the line ends.
+__global__ __launch_bounds__(256) void k_fx_place(const FxText x, const mahip_useq_want_t *__restrict__ want, uint32_t n_want, const uint32_t *__restrict__ win, unsigned char *__restrict__ arena)
+{
+	__shared__ unsigned char s_comp[128];
+	__shared__ uint64_t s_start[256];
+	__shared__ uint32_t s_off[256], s_wave[4];
+	if (threadIdx.x < 128) s_comp[threadIdx.x] = comp_of(threadIdx.x);
+	__syncthreads();
+	for (uint32_t w = blockIdx.x; w < n_want; w += gridDim.x) { // the whole block
+		const uint32_t rec = win[w];
+		if (rec == 0) continue; // not in the file: its positions stay 'N'
+		const mahip_useq_want_t wt = want[w];
+		uint32_t j0, j1; uint64_t nb;
+		fx_record(x, rec - 1, &j0, &j1, &nb);
+		const uint64_t s = wt.whole ? 0 : wt.s, e = wt.whole ? nb : wt.e; // the kept interval [s, e) of the read's bases (the caller made sure that nb >= e)
+		const uint64_t len = wt.len < e - s ? wt.len : e - s;
+		const uint64_t lo = wt.rev ? e - len : s, hi = lo + len;          // the bases that are placed
+		unsigned char *dst = arena + wt.dst_off;
+		if (j1 - j0 == 1) {
+			const unsigned char *src = x.t + x.ls[j0];
+			if (!wt.rev) for (uint64_t i = threadIdx.x; i < len; i += 256) dst[i] = src[s + i];
+			else for (uint64_t i = threadIdx.x; i < len; i += 256) { const unsigned ch = src[e - 1 - i]; dst[i] = ch >= 128 ? 'N' : s_comp[ch]; } // asm.c:280-281
+			continue;
+		}
+		uint64_t run = 0; // bases in front of the chunk
+		for (uint32_t cj = j0; cj < j1 && run < hi; cj += 256) {
+			const uint32_t cnt = j1 - cj < 256u ? j1 - cj : 256u, j = cj + threadIdx.x;
+			uint32_t tot;
+			const uint32_t ll = threadIdx.x < cnt ? (uint32_t)(x.ls[j + 1] - x.ls[j] - 1) : 0u;
+			const uint32_t ex = block_excl_scan_256(ll, s_wave, &tot);
+			if (threadIdx.x < cnt) { s_start[threadIdx.x] = x.ls[j]; s_off[threadIdx.x] = ex; }
+			__syncthreads();
+			const uint64_t b0 = lo > run ? lo : run, b1 = hi < run + tot ? hi : run + tot;
+			for (uint64_t b = b0 + threadIdx.x; b < b1; b += 256) {
+				const uint32_t rel = (uint32_t)(b - run);
+				uint32_t ka = 0, kb = cnt; // the last line of the chunk that starts at or in front of the base
+				while (kb - ka > 1) { const uint32_t mid = (ka + kb) >> 1; if (s_off[mid] <= rel) ka = mid; else kb = mid; }
+				const unsigned ch = x.t[s_start[ka] + (rel - s_off[ka])];
+				if (!wt.rev) dst[b - s] = (unsigned char)ch;
+				else dst[e - 1 - b] = ch >= 128 ? 'N' : s_comp[ch];
+			}
+			run += tot;
+			__syncthreads();
+		}
+	}
+}
+
+static void fx_drop(mahip_ctx *c, UseqBufs *b)
+{
+	DevBuf *all[] = {&b->fx_text, &b->fx_gcnt, &b->fx_gpos, &b->fx_ls, &b->fx_hdr, &b->fx_hpos, &b->fx_recl, &b->fx_ctr, &b->fx_want, &b->fx_wname, &b->fx_whash, &b->fx_tab, &b->fx_win};
+	for (DevBuf *d : all) dev_free(c, *d);
+	b->fx_n = 0; b->fx_loaded = b->fx_regular = false;
+}
+
+static int fx_reserve_text(mahip_ctx *c, size_t nbytes)
+{
+	UseqBufs *b = useq_bufs(c);
+	b->fx_loaded = b->fx_regular = false;
+	if (nbytes == 0) { mahip_set_error("mahip_fastx_load: empty text"); return -1; }
+	CHK(dev_reserve(c, b->fx_text, nbytes + 64));
+	b->fx_n = nbytes;
+	return 0;
+}
+extern "C" int mahip_fastx_load_mem(mahip_ctx_t *c, const void *text, size_t nbytes)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	CHK(fx_reserve_text(c, nbytes));
+	CHK(xfer_copy(c, useq_bufs(c)->fx_text.p, (void*)text, nbytes, 1));
+	useq_bufs(c)->fx_loaded = true;
+	return 0;
+}
+extern "C" int mahip_fastx_load_fd(mahip_ctx_t *c, int fd, size_t nbytes)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (nbytes == 0) { mahip_set_error("mahip_fastx_load_fd: empty file"); return -1; }
+	if (fx_reserve_text(c, nbytes) != 0) return 1; // no room for the text: the caller may read the file itself
+	CHK(xfer_from_fd(c, useq_bufs(c)->fx_text.p, fd, nbytes));
+	useq_bufs(c)->fx_loaded = true;
+	return 0;
+}
+extern "C" int mahip_fastx_release(mahip_ctx_t *c)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (c->useq) { HIPCHK(hipStreamSynchronize(c->st)); fx_drop(c, (UseqBufs*)c->useq); }
+	return 0;
+}
+extern "C" const char *mahip_fastx_reason_name(int reason)
+{
+	static const char *const nm[] = {"ok", "carriage returns in the file", "first byte is neither '>' nor '@'", "a FASTA sequence line begins with '@' or '+'", "FASTQ records are not four lines each",
+	                                 "a FASTQ quality line differs in length from its sequence", "more than 2^32 - 1 lines", "not enough device memory", "a wanted read is shorter than its placement",
+	                                 "not a plain file", "MA_FASTX_HOST is set", "NUL bytes in the file", "a line of 16 MiB or more in a wrapped FASTA record"};
+	return reason >= 0 && reason < (int)(sizeof(nm) / sizeof(nm[0])) ? nm[reason] : "?";
+}
+
+static int fx_counters(mahip_ctx *c, UseqBufs *b, unsigned long long *h)
+{
+	HIPCHK(hipMemcpyAsync(h, b->fx_ctr.p, FX_NCTR * 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+static FxText fx_view(UseqBufs *b)
+{
+	FxText x = {(const unsigned char*)b->fx_text.p, (const uint64_t*)b->fx_ls.p, (const uint32_t*)b->fx_recl.p, (uint64_t)b->fx_n, b->fx_L, b->fx_R, b->fx_format == MAHIP_FASTX_FASTQ};
+	return x;
+}
+
+#define FX_RESERVE(buf, bytes) do { if (dev_reserve(c, (buf), (bytes)) != 0) { info->reason = MAHIP_FASTX_NOMEM; return 0; } } while (0)
+extern "C" int mahip_fastx_index(mahip_ctx_t *c, mahip_fastx_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	memset(info, 0, sizeof(*info));
+	if (!b->fx_loaded) { mahip_set_error("mahip_fastx_index: no text loaded"); return -1; }
+	b->fx_regular = false;
+	const uint64_t n = b->fx_n;
+	const uint32_t n_gran = (uint32_t)((n + FX_GRAN - 1) / FX_GRAN);
+	if ((n + FX_GRAN - 1) / FX_GRAN > 0xffffffffull) { info->reason = MAHIP_FASTX_TOO_MANY_LINES; return 0; }
+	unsigned long long h[FX_NCTR];
+	FX_RESERVE(b->fx_ctr, FX_NCTR * 8); FX_RESERVE(b->fx_gcnt, (size_t)n_gran * 4); FX_RESERVE(b->fx_gpos, (size_t)n_gran * 4 + 4);
+	HIPCHK(hipMemsetAsync(b->fx_ctr.p, 0, FX_NCTR * 8, c->st));
+	{
+		ProfScope ps(c, "k_fx_census", (double)n);
+		hipLaunchKernelGGL(k_fx_census, dim3(grid_for(n_gran, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const unsigned char*)b->fx_text.p, n, n_gran, P<uint32_t>(b->fx_gcnt), P<unsigned long long>(b->fx_ctr));
+		HIPCHK(hipGetLastError());
+	}
+	CHK(fx_counters(c, b, h));
+	const uint64_t L = h[FX_NL] + (h[FX_LAST] != '\n');
+	info->n_lines = L; info->n_cr = h[FX_CR];
+	info->format = h[FX_FIRST] == '>' ? MAHIP_FASTX_FASTA : h[FX_FIRST] == '@' ? MAHIP_FASTX_FASTQ : 0;
+	b->fx_format = info->format;
+	if (info->n_cr) { info->reason = MAHIP_FASTX_CR; return 0; }
+	if (h[FX_NUL]) { info->reason = MAHIP_FASTX_NUL_BYTE; return 0; } // the reference's names are C strings (asm.c:266): a name ends at a NUL for it
+	if (info->format == 0) { info->reason = MAHIP_FASTX_FIRST_BYTE; return 0; }
+	if (L > 0xffffffffull) { info->reason = MAHIP_FASTX_TOO_MANY_LINES; return 0; }
+	b->fx_L = (uint32_t)L;
+	FX_RESERVE(b->fx_ls, (size_t)(L + 2) * 8);
+	CHK(scan_exclusive_u32(c, P<uint32_t>(b->fx_gcnt), P<uint32_t>(b->fx_gpos), n_gran, nullptr));
+	{
+		ProfScope ps(c, "k_fx_lines", (double)n + 8.0 * (double)L);
+		hipLaunchKernelGGL(k_fx_lines, dim3(grid_for(n_gran, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const unsigned char*)b->fx_text.p, n, n_gran, P<uint32_t>(b->fx_gpos), (uint32_t)L, P<uint64_t>(b->fx_ls));
+		HIPCHK(hipGetLastError());
+	}
+	if (info->format == MAHIP_FASTX_FASTQ) {
+		b->fx_R = (uint32_t)(L / 4);
+		info->n_records = L / 4;
+		if (L % 4) { info->reason = MAHIP_FASTX_FASTQ_SHAPE; return 0; }
+		ProfScope ps(c, "k_fx_form_fastq", 40.0 * (double)b->fx_R);
+		hipLaunchKernelGGL(k_fx_form_fastq, dim3(grid_for(b->fx_R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, fx_view(b), P<unsigned long long>(b->fx_ctr));
+		HIPCHK(hipGetLastError());
+	} else {
+		FX_RESERVE(b->fx_hdr, (size_t)L * 4); FX_RESERVE(b->fx_hpos, (size_t)(L + 1) * 4);
+		{
+			ProfScope ps(c, "k_fx_form_fasta", 20.0 * (double)L);
+			hipLaunchKernelGGL(k_fx_form_fasta, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, fx_view(b), P<uint32_t>(b->fx_hdr), P<unsigned long long>(b->fx_ctr));
+			HIPCHK(hipGetLastError());
+		}
+		CHK(scan_exclusive_u32(c, P<uint32_t>(b->fx_hdr), P<uint32_t>(b->fx_hpos), L, P<uint32_t>(b->fx_hpos) + L));
+		uint32_t R = 0;
+		HIPCHK(hipMemcpyAsync(&R, P<uint32_t>(b->fx_hpos) + L, 4, hipMemcpyDeviceToHost, c->st));
+		HIPCHK(hipStreamSynchronize(c->st));
+		b->fx_R = R; info->n_records = R;
+		FX_RESERVE(b->fx_recl, (size_t)(R + 1) * 4);
+		ProfScope ps(c, "k_fx_rec_lines", 8.0 * (double)L);
+		hipLaunchKernelGGL(k_fx_rec_lines, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, P<uint32_t>(b->fx_hdr), P<uint32_t>(b->fx_hpos), (uint32_t)L, P<uint32_t>(b->fx_recl));
+		HIPCHK(hipGetLastError());
+	}
+	CHK(fx_counters(c, b, h));
+	if (h[FX_V_FASTA]) info->reason = MAHIP_FASTX_FASTA_LINE_START;
+	else if (h[FX_V_SHAPE]) info->reason = MAHIP_FASTX_FASTQ_SHAPE;
+	else if (h[FX_V_QUAL]) info->reason = MAHIP_FASTX_FASTQ_QUAL_LEN;
+	else if (h[FX_V_LONG]) info->reason = MAHIP_FASTX_LONG_LINE;
+	else { info->regular = 1; b->fx_regular = true; }
+	return 0;
+}
+#undef FX_RESERVE
+
+extern "C" int mahip_fastx_line_starts(mahip_ctx_t *c, uint64_t *out)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fx_loaded || !b->fx_ls.p) { mahip_set_error("mahip_fastx_line_starts: no line index"); return -1; }
+	HIPCHK(hipMemcpyAsync(out, b->fx_ls.p, ((size_t)b->fx_L + 1) * 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+extern "C" int mahip_fastx_name_spans(mahip_ctx_t *c, uint64_t *off, uint32_t *len)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fx_regular) { mahip_set_error("mahip_fastx_name_spans: the text is not in the regular form"); return -1; }
+	const size_t R = b->fx_R;
+	if (R == 0) return 0;
+	DevBuf d_off, d_len;
+	int rc = dev_reserve(c, d_off, R * 8) || dev_reserve(c, d_len, R * 4);
+	if (rc == 0) {
+		hipLaunchKernelGGL(k_fx_name_spans, dim3(grid_for(R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, fx_view(b), P<uint64_t>(d_off), P<uint32_t>(d_len));
+		rc = hipGetLastError() != hipSuccess || hipMemcpyAsync(off, d_off.p, R * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess ||
+		     hipMemcpyAsync(len, d_len.p, R * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess;
+		if (hipStreamSynchronize(c->st) != hipSuccess) rc = 1;
+		if (rc) mahip_set_error("mahip_fastx_name_spans: launch or copy failed");
+	}
+	dev_free(c, d_off); dev_free(c, d_len);
+	return rc ? -1 : 0;
+}
+
+static double fx_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; }
+
+extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes,
+                                     uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fx_regular) { mahip_set_error("mahip_useq_place_text: no text in the regular form (mahip_fastx_index)"); return -1; }
+	if (n_wanted >= 0x40000000ull) { mahip_set_error("mahip_useq_place_text: too many wanted reads"); return -1; }
+	*n_matched = *n_dup = *n_short = 0;
+	if (laps_ms) laps_ms[0] = laps_ms[1] = 0;
+	if (n_wanted == 0 || b->fx_R == 0) return 0;
+	for (size_t w = 0; w < n_wanted; ++w) // the kernels trust these
+		if (wanted[w].name_off + wanted[w].name_len > name_bytes || wanted[w].dst_off + wanted[w].len > b->arena_bytes || (!wanted[w].whole && wanted[w].s > wanted[w].e)) {
+			mahip_set_error("mahip_useq_place_text: wanted read %zu reaches outside the names or the arena", w); return -1;
+		}
+	const double t0 = fx_now();
+	uint32_t cap = 64; while (cap < 2 * n_wanted) cap <<= 1;
+	CHK(dev_reserve(c, b->fx_want, n_wanted * sizeof(mahip_useq_want_t))); CHK(dev_reserve(c, b->fx_wname, name_bytes + 64)); CHK(dev_reserve(c, b->fx_whash, n_wanted * 8));
+	CHK(dev_reserve(c, b->fx_tab, (size_t)cap * 4)); CHK(dev_reserve(c, b->fx_win, n_wanted * 4));
+	HIPCHK(hipMemcpyAsync(b->fx_want.p, wanted, n_wanted * sizeof(mahip_useq_want_t), hipMemcpyHostToDevice, c->st));
+	HIPCHK(hipMemcpyAsync(b->fx_wname.p, names, name_bytes, hipMemcpyHostToDevice, c->st));
+	HIPCHK(hipMemsetAsync(b->fx_tab.p, 0, (size_t)cap * 4, c->st));
+	HIPCHK(hipMemsetAsync(b->fx_win.p, 0, n_wanted * 4, c->st));
+	HIPCHK(hipMemsetAsync(b->fx_ctr.p, 0, FX_NCTR * 8, c->st));
+	const FxText x = fx_view(b);
+	{
+		ProfScope ps(c, "k_fx_tab_build", 0);
+		hipLaunchKernelGGL(k_fx_tab_build, dim3(grid_for(n_wanted, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (uint32_t)n_wanted,
+		                   P<uint64_t>(b->fx_whash), P<uint32_t>(b->fx_tab), cap - 1);
+		HIPCHK(hipGetLastError());
+	}
+	{
+		ProfScope ps(c, "k_fx_probe", 0);
+		hipLaunchKernelGGL(k_fx_probe, dim3(grid_for(b->fx_R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (const uint64_t*)b->fx_whash.p,
+		                   (const uint32_t*)b->fx_tab.p, cap - 1, P<uint32_t>(b->fx_win), P<unsigned long long>(b->fx_ctr));
+		HIPCHK(hipGetLastError());
+	}
+	unsigned long long h[FX_NCTR];
+	CHK(fx_counters(c, b, h)); // (waits for the uploads too: the caller may reuse wanted / names)
+	*n_matched = h[FX_DISTINCT]; *n_dup = h[FX_MATCH] - h[FX_DISTINCT]; *n_short = h[FX_SHORT];
+	const double t1 = fx_now();
+	if (laps_ms) laps_ms[0] = (t1 - t0) * 1e3;
+	if (h[FX_SHORT]) return 0; // the caller falls back: nothing has touched the arena
+	{
+		ProfScope ps(c, "k_fx_place", 0);
+		hipLaunchKernelGGL(k_fx_place, dim3(grid_for(n_wanted, 1, 65536)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (uint32_t)n_wanted, (const uint32_t*)b->fx_win.p, (unsigned char*)b->arena.p);
+		HIPCHK(hipGetLastError());
+	}
+	if (laps_ms) { HIPCHK(hipStreamSynchronize(c->st)); laps_ms[1] = (fx_now() - t1) * 1e3; }
+	return 0;
+}
+
+extern "C" void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in) { useq_bufs(c)->last = *in; }
+extern "C" int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out) { *out = useq_bufs(c)->last; return 0; }

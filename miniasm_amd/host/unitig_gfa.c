@@ -340,6 +340,9 @@ void ma_ug_print_mem(const ma_ug_t *ug, const sdict_t *d, const ma_sub_t *sub, c
 #include <zlib.h>
 #include <ctype.h>
 #include <assert.h>
+#include <fcntl.h>
+#include <unistd.h>
+#include <sys/stat.h>
 
 typedef struct { gzFile fp; unsigned char *buf; int beg, end, eof; } fq_stream_t;
 #define FQ_BUF (1 << 18)
@@ -371,7 +374,7 @@ static int fq_line(fq_stream_t *f, fq_str_t *t)
 	return c;
 }
 
-/* next record: name and sequence (qualities are skipped); *last is the look-ahead marker; returns <0 at end */
+/* next record: name and sequence (qualities are skipped); *last is the look-ahead marker; returns <0 at end (-2: quality string of another length than the sequence) */
 static int fq_read(fq_stream_t *f, int *last, fq_str_t *name, fq_str_t *seq)
 {
 	int c;
@@ -393,18 +396,81 @@ static int fq_read(fq_stream_t *f, int *last, fq_str_t *name, fq_str_t *seq)
 		fq_line(f, seq);
 	}
 	if (c == '>' || c == '@') *last = c; else *last = 0;
-	if (c == '+') { /* FASTQ: skip the '+' line and as many quality characters as there are bases */
+	if (c == '+') { /* FASTQ: skip the '+' line, then whole quality LINES until they hold as many characters as there are bases (kseq.h:226-230) */
 		size_t ql = 0;
+		int tail = 0; /* last quality character kept so far */
 		while ((c = fq_getc(f)) != -1 && c != '\n');
-		while (ql < seq->l && (c = fq_getc(f)) != -1) if (c != '\n' && c != '\r') ++ql; else if (c == '\r') { /* CR inside qualities: kseq keeps line semantics */ }
+		if (c == -1) return -2; /* no quality string */
+		do {
+			if ((c = fq_getc(f)) == -1) break; /* nothing left to read */
+			for (; c != -1 && c != '\n'; c = fq_getc(f)) ++ql, tail = c;
+			if (ql > 1 && tail == '\r') --ql, tail = 0; /* kseq.h:146 */
+		} while (ql < seq->l);
 		*last = 0;
+		if (ql != seq->l) return -2; /* the reference's loop (asm.c:262) stops reading the file here */
 	}
 	return (int)seq->l;
 }
 
 typedef struct { uint32_t utg:31, ori:1, start, len; } utg_place_t;
 
-/* The file is read here (one inflate stream, the reference's record rules); the bases of every read that sits on a unitig go to
+/* The reads file on the device (csrc/useq.hip): a plain file goes to HBM as it is; the device checks that it is in the regular form (include/mahip.h), looks
+ * the names of the reads that sit on a unitig up among its records and copies their bases into the arena.  Returns 1 when the arena is filled, 0 with
+ * ui->reason when the host reader has to run (the arena is untouched then), -1 on an error. */
+enum { LAP_LOAD, LAP_INDEX, LAP_LOOKUP, LAP_PLACE, LAP_DOWNLOAD, N_LAPS };
+static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, const char *fn, const utg_place_t *pl, const uint64_t *uoff, mahip_useq_info_t *ui, double *laps)
+{
+	const char *e = getenv("MA_FASTX_HOST");
+	struct stat st;
+	unsigned char magic[2] = {0, 0};
+	mahip_fastx_info_t fi;
+	mahip_useq_want_t *want;
+	char *names;
+	size_t n_want = 0, name_bytes = 0;
+	uint32_t i;
+	double t0, pl_laps[2];
+	int fd, rc;
+	if (e && atoi(e) != 0) { ui->reason = MAHIP_FASTX_FORCED; return 0; }
+	ui->reason = MAHIP_FASTX_NOT_PLAIN;
+	if (fn == 0 || strcmp(fn, "-") == 0) return 0;
+	if ((fd = open(fn, O_RDONLY)) < 0) return 0; /* the host reader reports it */
+	if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0 || pread(fd, magic, 2, 0) < 1 || (magic[0] == 0x1f && magic[1] == 0x8b)) { close(fd); return 0; }
+	t0 = sys_realtime();
+	mahip_mem_trim(c, 0); /* what the passes before left idle in the pool: the text may need it */
+	rc = mahip_fastx_load_fd(c, fd, (size_t)st.st_size);
+	close(fd);
+	if (rc < 0) { mahip_fastx_release(c); return -1; } /* a read error, a HIP error */
+	if (rc > 0) { ui->reason = MAHIP_FASTX_NOMEM; mahip_fastx_release(c); return 0; } /* no room for the text */
+	laps[LAP_LOAD] = (sys_realtime() - t0) * 1e3; t0 = sys_realtime();
+	if (mahip_fastx_index(c, &fi) != 0) { mahip_fastx_release(c); return -1; }
+	laps[LAP_INDEX] = (sys_realtime() - t0) * 1e3;
+	ui->format = fi.format; ui->n_records = fi.n_records;
+	if (!fi.regular) { ui->reason = fi.reason; mahip_fastx_release(c); return 0; }
+	for (i = 0; i < d->n_seq; ++i) if (pl[i].len) ++n_want, name_bytes += strlen(d->seq[i].name);
+	want = (mahip_useq_want_t*)malloc((n_want ? n_want : 1) * sizeof(mahip_useq_want_t));
+	names = (char*)malloc(name_bytes ? name_bytes : 1);
+	n_want = name_bytes = 0;
+	for (i = 0; i < d->n_seq; ++i) {
+		const utg_place_t *t = &pl[i];
+		mahip_useq_want_t *w = &want[n_want];
+		const size_t l = strlen(d->seq[i].name);
+		if (t->len == 0 || l == 0) continue; /* (no record has an empty name that matches) */
+		memcpy(names + name_bytes, d->seq[i].name, l);
+		w->dst_off = uoff[t->utg] + t->start; w->name_off = name_bytes; w->name_len = (uint32_t)l;
+		w->len = t->len; w->rev = t->ori; w->whole = sub == 0;
+		w->s = sub ? sub[i].s : 0; w->e = sub ? sub[i].e : 0;
+		++n_want; name_bytes += l;
+	}
+	rc = mahip_useq_place_text(c, want, n_want, names, name_bytes, &ui->n_matched, &ui->n_dup, &ui->n_short, pl_laps);
+	free(want); free(names);
+	laps[LAP_LOOKUP] = pl_laps[0]; laps[LAP_PLACE] = pl_laps[1];
+	if (mahip_fastx_release(c) != 0 || rc != 0) return -1;
+	if (ui->n_short) { ui->reason = MAHIP_FASTX_SHORT_READ; return 0; }
+	ui->reason = MAHIP_FASTX_OK;
+	return 1;
+}
+
+/* Host reader (the fallback: gzip, stdin, files outside the regular form): the file is read here (one inflate stream, the reference's record rules); the bases of every read that sits on a unitig go to
  * the device in batches and a byte-gather kernel places them (forward copy / reverse complement, csrc/useq.hip); the unitig
  * strings come back once, at the end. */
 #define USEQ_BATCH_BYTES ((size_t)256 << 20)
@@ -419,12 +485,16 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 	mahip_useq_job_t *jobs;
 	size_t n_jobs = 0, m_jobs = 1 << 16, n_batch = 0, m_batch = USEQ_BATCH_BYTES;
 	uint32_t i, j;
-	int last = 0;
+	int last = 0, on_device;
+	uint32_t *in_batch, batch_no = 1; /* host reader: the batch that holds a job of the read */
+	mahip_useq_info_t ui;
+	double laps[N_LAPS] = {0, 0, 0, 0, 0}, t_dl;
+	static const char *const fmt_name[] = {"?", "fasta", "fastq"};
 	memset(&f, 0, sizeof(f));
-	f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r");
-	if (f.fp == 0) return -1;
+	memset(&ui, 0, sizeof(ui));
+	f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
+	if (f.fp == 0) return -1;                                                      /*  nothing is read through it unless the host reader runs) */
 	c = ma_gpu();
-	f.buf = (unsigned char*)malloc(FQ_BUF);
 	pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
 	uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
 	for (i = 0; i < g->u.n; ++i) { /* where every read lands; unitig strings back to back, each with its terminator */
@@ -440,9 +510,18 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 		}
 	}
 	GPU(mahip_useq_begin(c, (size_t)tot));
-	batch = (char*)malloc(m_batch);
-	jobs = (mahip_useq_job_t*)malloc(m_jobs * sizeof(mahip_useq_job_t));
-	while (fq_read(&f, &last, &name, &seq) >= 0) {
+	on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &ui, laps);
+	if (on_device < 0) ma_gpu_fail(__func__);
+	ui.reader = on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
+	mahip_useq_note(c, &ui);
+	if (!on_device) {
+		fprintf(stderr, "[W::%s] reads file read on the host: %s\n", __func__, mahip_fastx_reason_name(ui.reason));
+		f.buf = (unsigned char*)malloc(FQ_BUF);
+	}
+	batch = on_device ? 0 : (char*)malloc(m_batch);
+	jobs = on_device ? 0 : (mahip_useq_job_t*)malloc(m_jobs * sizeof(mahip_useq_job_t));
+	in_batch = on_device ? 0 : (uint32_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(uint32_t));
+	while (!on_device && fq_read(&f, &last, &name, &seq) >= 0) {
 		int32_t id = name.s ? sd_get(d, name.s) : -1;
 		const utg_place_t *t;
 		const char *rs = seq.s;
@@ -453,27 +532,36 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 			assert(sub[id].e - sub[id].s <= rl);
 			rs += sub[id].s; rl = sub[id].e - sub[id].s;
 		}
-		if (n_batch + rl > m_batch || n_jobs == m_jobs) { /* batch full: place what is there */
+		if (n_batch + rl > m_batch || n_jobs == m_jobs || in_batch[id] == batch_no) { /* batch full: place what is there.  A name the file carries twice: the later record has to win
+		                                                                                 * (asm.c:262-284 overwrites), and the jobs of ONE batch run side by side -- it goes into the next */
 			GPU(mahip_useq_batch(c, batch, n_batch, jobs, n_jobs));
-			n_batch = 0; n_jobs = 0;
+			n_batch = 0; n_jobs = 0; ++batch_no;
 			if (rl > m_batch) { m_batch = rl; batch = (char*)realloc(batch, m_batch); }
 		}
+		in_batch[id] = batch_no;
 		memcpy(batch + n_batch, rs, rl);
 		jobs[n_jobs].src_off = n_batch; jobs[n_jobs].dst_off = uoff[t->utg] + t->start;
 		jobs[n_jobs].src_len = (uint32_t)rl; jobs[n_jobs].len = t->len; jobs[n_jobs].rev = t->ori; jobs[n_jobs].pad = 0;
 		++n_jobs; n_batch += rl;
 	}
-	GPU(mahip_useq_batch(c, batch, n_batch, jobs, n_jobs));
+	if (!on_device) GPU(mahip_useq_batch(c, batch, n_batch, jobs, n_jobs));
 	arena = (char*)malloc(tot ? tot : 1);
+	t_dl = sys_realtime();
 	GPU(mahip_useq_end(c, arena));
+	laps[LAP_DOWNLOAD] = (sys_realtime() - t_dl) * 1e3;
+	if (ma_timing_level() >= 1) {
+		if (on_device) fprintf(stderr, "[T::ug_seq] reader=device format=%s records=%llu matched=%llu dup=%llu : load %.3f index %.3f lookup %.3f place %.3f download %.3f ms\n", fmt_name[ui.format],
+		                       (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, laps[LAP_LOAD], laps[LAP_INDEX], laps[LAP_LOOKUP], laps[LAP_PLACE], laps[LAP_DOWNLOAD]);
+		else fprintf(stderr, "[T::ug_seq] reader=host reason=%d format=%s records=%llu : download %.3f ms\n", ui.reason, fmt_name[ui.format], (unsigned long long)ui.n_records, laps[LAP_DOWNLOAD]);
+	}
 	for (i = 0; i < g->u.n; ++i) { /* ma_ug_destroy frees every string on its own */
 		ma_utg_t *u = &g->u.a[i];
 		u->s = (char*)malloc((size_t)u->len + 1);
 		memcpy(u->s, arena + uoff[i], u->len);
 		u->s[u->len] = 0;
 	}
-	free(arena); free(batch); free(jobs); free(uoff);
+	free(arena); free(batch); free(jobs); free(uoff); free(in_batch);
 	free(pl); free(name.s); free(seq.s); free(f.buf);
-	gzclose(f.fp);
+	if (f.fp) gzclose(f.fp);
 	return 0;
 }

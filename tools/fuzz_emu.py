@@ -4,9 +4,11 @@ command-line options, the unmodified reference binary (oracle/_ref/miniasm_ref) 
 (tests/emu/_build/miniasm), every dump format, bytes compared.  Test tooling: `python tools/fuzz_emu.py --cases 200 --seed 1`.
 With --ranks the same case is also run as MA_GPUS=N over the shared-memory double."""
 import argparse
+import gzip
 import hashlib
 import os
 import random
+import re
 import subprocess
 import sys
 import tempfile
@@ -172,6 +174,16 @@ def write_reads(rng, paf, path):
                 out.write(b">" + hdr + b"\n" + b"\n".join(seq[k:k + wrap] for k in range(0, n, wrap)) + b"\n")
             else:
                 out.write(b">" + hdr + b"\n" + seq + b"\n")
+    how = rng.random()  # one file in five is outside the regular form of the device reader: CR line ends, a leading blank line, gzip
+    if how < 0.2:
+        data = open(path, "rb").read()
+        if how < 0.07:
+            data = data.replace(b"\n", b"\r\n")
+        elif how < 0.14:
+            data = b"\n" + data
+        else:
+            data = gzip.compress(data, 1)
+        open(path, "wb").write(data)
 
 
 def main():
@@ -199,7 +211,7 @@ def main():
     tmp = tempfile.mkdtemp(prefix="ma_fuzz_")
     paf = os.path.join(tmp, "f.paf")
     bad = skipped = 0
-    paths = {}
+    paths, readers = {}, {}
     for k in range(a.cases):
         gen, args = rand_case(rng)
         r = subprocess.run([PAFGEN] + gen + ["-o", paf], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
@@ -219,6 +231,8 @@ def main():
             skipped += 1
             continue
         runs = [("emu", {})]
+        if a.seq:  # the same case with the host reader of the reads file: both must equal the reference
+            runs.append(("emu host reader", {"MA_FASTX_HOST": "1"}))
         if a.ranks > 1:  # requests the sharded head does not serve fall back to one GPU: the bytes must be the same either way
             runs.append(("emu x%d" % a.ranks, {"MA_GPUS": str(a.ranks), "MA_COMM": "shm"}))
         for name, env in runs:
@@ -226,8 +240,11 @@ def main():
             env.update(kv.split("=", 1) for kv in a.env)
             rc1, out1, err1 = run(EMU, args, paf, env)
             for ln in err1.decode(errors="replace").splitlines():
+                if ln.startswith("[T::ug_seq]") and name == "emu":  # which reader the reads file took (and why the host reader ran)
+                    mm = re.search(r"reader=(\w+)(?: reason=(\d+))?", ln)
+                    key = "reads file: %s%s" % (mm.group(1), " (reason %s)" % mm.group(2) if mm.group(2) else "")
+                    readers[key] = readers.get(key, 0) + 1
                 if ln.startswith("[T::ties]") and "arc tie groups" in ln:
-                    import re
                     mm = re.search(r"(\d+) arc tie groups .*?, (\d+) push conflicts \((\d+) of them in sight", ln)
                     if not mm:
                         continue
@@ -246,6 +263,8 @@ def main():
         if (k + 1) % 20 == 0:
             print("%d cases, %d mismatches" % (k + 1, bad), flush=True)
     print("tie paths taken:", paths)
+    if a.seq:
+        print("reads-file readers taken:", readers)
     print("done: %d cases, %d mismatches, %d skipped (reference crashed)" % (a.cases, bad, skipped))
     sys.exit(1 if bad else 0)
 
