@@ -101,6 +101,20 @@ int mahip_set_hints(mahip_ctx_t *c, uint32_t max_qs);
  * upload/adopt, like the other hints. */
 int mahip_set_run_stride(mahip_ctx_t *c, int stride);
 uint64_t mahip_hits_sorted_runs(mahip_ctx_t *c); /* elements of the last mahip_hits_sort if it sorted runs, else 0 */
+/* What the LAST mahip_hits_sort of this context did (host bookkeeping, read-only; the tests assert from it that a case reached the path and the digit plan it
+ * was built for).  path: what the sort's elements were and who counted the first digit (0: no sort yet, or no record to sort).  fallback: a run stride was set
+ * and the records were sorted all the same -- NOT_TRIED: a shard, or no dictionary size (n_seq = 0); FIELD_WIDTH: id, position and length do not fit one word;
+ * ID_RANGE: an id >= n_seq in the input; FEW_RUNS: more than three runs per four records; INTERLEAVED: two runs of one read overlap (k_runs_expand).
+ * n_elem: sorted elements (runs, or this context's records); n_runs_seen: runs k_hit_keys_runs counted (0: not run).  n_pass radix passes over the id bits,
+ * pass p on `bits[p]` bits from bit `shift[p]`; fixed7 bit p: the pass ran the scatter with its 7-bit width at compile time; groups: the last pass wrote the
+ * group starts (else k_runs_expand or k_hit_goff made them). */
+enum { MAHIP_SORT_NONE = 0, MAHIP_SORT_RUNS = 1, MAHIP_SORT_RECORDS_FUSED_HIST = 2, MAHIP_SORT_RECORDS_PLAIN = 3 };
+enum { MAHIP_RUNS_NO_FALLBACK = 0, MAHIP_RUNS_NOT_TRIED = 1, MAHIP_RUNS_FEW_RUNS = 2, MAHIP_RUNS_ID_RANGE = 3, MAHIP_RUNS_INTERLEAVED = 4, MAHIP_RUNS_FIELD_WIDTH = 5 };
+typedef struct { int path, fallback; uint64_t n_elem, n_runs_seen; int n_pass, bits[8], shift[8]; uint32_t fixed7; int groups; } mahip_sort_info_t;
+int mahip_sort_last(mahip_ctx_t *c, mahip_sort_info_t *out);
+/* for stage tests: the resident layout the sort leaves (the pending gather is run first): sidx[n_hits] = input position of the record in every slot,
+ * goff[n_seq + 1] = first slot of every read's group.  Only after mahip_hits_sort. */
+int mahip_hits_layout_download(mahip_ctx_t *c, uint32_t *sidx, uint32_t *goff);
 /* Bulk copies between pageable host memory and device memory at PCIe speed: worker threads stage slices through
  * pinned slots while their DMAs run (a plain hipMemcpy of pageable memory is staged by one runtime thread).
  * Synchronous; ordered after the work already queued on the context's stream.  MA_XFER_THREADS sets the workers. */

@@ -1299,6 +1299,13 @@ extern "C" int mahip_set_run_stride(mahip_ctx_t *c, int stride)
 // elements of the last mahip_hits_sort when it sorted RUNS of records (0: it sorted records)
 extern "C" uint64_t mahip_hits_sorted_runs(mahip_ctx_t *c) { return c->gk_runs ? (uint64_t)c->n_runs : 0; }
 
+// tests: path, fallback reason and digit plan of the last mahip_hits_sort (host bookkeeping only)
+extern "C" int mahip_sort_last(mahip_ctx_t *c, mahip_sort_info_t *out)
+{
+	if (out) *out = c->sort_last;
+	return 0;
+}
+
 extern "C" int mahip_set_exact_ties(mahip_ctx_t *c, int mode)
 {
 	c->tie_mode = mode < 0 || mode > 2 ? 2 : mode;
@@ -1534,6 +1541,8 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 { // groups the hits by query id (input order inside a group); see the note at the top of the sort section
 	HIPCHK(hipSetDevice(c->dev));
 	size_t n = c->n_hits;
+	mahip_sort_info_t &sl = c->sort_last; // (mahip_sort_last)
+	sl = mahip_sort_info_t();
 	if (n == 0) {
 		HIPCHK(hipMemsetAsync(c->goff.p, 0, ((size_t)c->n_seq + 1) * 4, c->st));
 		c->soa_ready = true; c->n_live = 0;
@@ -1564,6 +1573,7 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 	// (mahip_set_run_stride: 2 with mirrored records, 1 without), the ids are dense and the three fields fit a word.  Falls back to sorting records when the
 	// input has few runs, or two runs of one read interleave.
 	const int bl_runs = 64 - bq - bi;
+	if (c->run_stride) sl.fallback = sharded || !c->n_seq ? MAHIP_RUNS_NOT_TRIED : MAHIP_RUNS_FIELD_WIDTH; // (tried: said again below)
 	if (!sharded && c->run_stride && c->n_seq && bl_runs >= RUN_MIN_LEN_BITS && bi <= 32) {
 		const int bl = bl_runs > 16 ? 16 : bl_runs;
 		const size_t nb1 = (n + RUN_TILE - 1) / RUN_TILE;
@@ -1576,6 +1586,7 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 		}
 		CHK(ctr_fetch(c));
 		const size_t n_runs = (size_t)c->h_ctr[CT_TOTAL];
+		sl.n_runs_seen = n_runs; sl.fallback = c->h_ctr[CT_OVF] ? MAHIP_RUNS_ID_RANGE : MAHIP_RUNS_FEW_RUNS;
 		if (n_runs && n_runs * 4 <= n * 3 && c->h_ctr[CT_OVF] == 0) { // worth it (else: the keys of all records below, as if nothing had happened)
 			int g2 = 0;
 			CHK(radix_sort_keys(c, n_runs, bi + bl, bi + bl + bq, &g2, false));
@@ -1596,6 +1607,7 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 			CHK(ctr_fetch(c));
 			runs_done = c->h_ctr[CT_OVF2] == 0; // interleaved runs of one read (or an id outside the dictionary): sort the records instead
 			c->n_runs = runs_done ? n_runs : 0;
+			sl.fallback = runs_done ? MAHIP_RUNS_NO_FALLBACK : MAHIP_RUNS_INTERLEAVED;
 		}
 		CHK(ctr_zero(c));
 	}
@@ -1638,6 +1650,7 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 		c->soa_ready = true;
 		return 0;
 	}
+	sl.path = runs_done ? MAHIP_SORT_RUNS : first_hist ? MAHIP_SORT_RECORDS_FUSED_HIST : MAHIP_SORT_RECORDS_PLAIN; sl.n_elem = runs_done ? c->n_runs : n;
 	if (runs_done) first_hist = true; // (nothing below needs keys)
 	if (runs_done) { /* sorted as runs above: sidx and goff are made */ }
 	else if (!sharded && c->n_seq) { // the group offsets come out of the sort's last pass (ids are < n_seq by contract, checked by the kernel)
@@ -1653,6 +1666,8 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 	}
 	}
 	HIPCHK(hipGetLastError());
+	sl.n_pass = c->rs_last.n_pass < 8 ? c->rs_last.n_pass : 8; sl.fixed7 = c->rs_last.fixed7; sl.groups = c->rs_last.groups; // the radix sort that made the layout: of the runs, or of the records
+	for (int p = 0; p < sl.n_pass; ++p) sl.bits[p] = c->rs_last.bits[p], sl.shift[p] = c->rs_last.shift[p];
 	c->gather_pending = true; c->gk_gen = gen; c->gk_bi = bi; c->gk_runs = runs_done;
 	c->soa_ready = true;
 	return 0;
@@ -2058,6 +2073,18 @@ extern "C" int mahip_survivors_download(mahip_ctx_t *c, uint32_t *old_ids)
 	HIPCHK(hipSetDevice(c->dev));
 	if (!c->has_map && !c->surv_ready) { mahip_set_error("mahip_survivors_download: no squeeze map"); return -1; }
 	if (c->n_seq_new) HIPCHK(hipMemcpyAsync(old_ids, c->surv.p, (size_t)c->n_seq_new * 4, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+
+// tests: the layout mahip_hits_sort leaves, as it stands (mahip_hits_download shows it through a second sort)
+extern "C" int mahip_hits_layout_download(mahip_ctx_t *c, uint32_t *sidx, uint32_t *goff)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (!c->sorted_here) { mahip_set_error("mahip_hits_layout_download: the hits were not sorted by mahip_hits_sort"); return -1; }
+	CHK(hits_need_cols(c, "mahip_hits_layout_download"));
+	if (c->n_hits) HIPCHK(hipMemcpyAsync(sidx, c->sidx.p, c->n_hits * 4, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipMemcpyAsync(goff, c->goff.p, ((size_t)c->n_seq + 1) * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(hipStreamSynchronize(c->st));
 	return 0;
 }

@@ -129,6 +129,8 @@ struct mahip_ctx {
 	hipEvent_t mark_ev[64] = {}; // phase marks (mahip_mark)
 	hipStream_t sub_side[2] = {}; hipEvent_t sub_ev[3] = {}; // side streams of the coverage passes' size classes (hits.hip: SubFork)
 	uint64_t scan_forms[3] = {0, 0, 0};                     // scan_exclusive_u32 calls that took: one tile / the chained launch / reduce-scan-downsweep (mahip_scan_forms)
+	mahip_sort_info_t sort_last = {};                       // what the last mahip_hits_sort did (mahip_sort_last)
+	struct { int n_pass, bits[16], shift[16]; uint32_t fixed7; int groups; } rs_last = {}; // the digit plan of the last radix sort of any kind (radix_sort_impl), copied into sort_last by the hit sort
 	uint64_t tr_inner = 0;                                  // iterations of asg.c:169's loop in the last reduction (mahip_asg_trans_inner)
 	bool arcs_clean = false;                                // no arc touches a read with seq.del set (checked when the arcs were made / last cleaned, no read deleted since): asg_arc_rm need not look
 	bool radix_arcs = false;                                // the radix passes running now sort arcs (profile names)

@@ -325,6 +325,7 @@ int radix_group_starts_finish(mahip_ctx *c, uint32_t *start, uint32_t n_id)
 static int radix_sort_impl(mahip_ctx *c, size_t n, int lo0, int hi0, int lo1, int hi1, int *gen, bool has_val, bool first_hist_ready = false, const RadixGroups *groups = nullptr)
 {
 	int g = *gen, shift[16], bits[16], np;
+	c->rs_last.n_pass = 0; c->rs_last.fixed7 = 0; c->rs_last.groups = 0;
 	if (n == 0) return 0;
 	if (n >= 0xffffffffull) { mahip_set_error("radix sort: too many records"); return -1; }
 	np = plan_digits(lo0, hi0, shift, bits);
@@ -333,6 +334,7 @@ static int radix_sort_impl(mahip_ctx *c, size_t n, int lo0, int hi0, int lo1, in
 	CHK(dev_reserve(c, c->hist, radix_hist_words(nb) * 4));
 	for (int p = 0; p < np; ++p) {
 		unsigned mask = (1u << bits[p]) - 1;
+		const bool w7 = bits[p] == 7; // the scatter with the digit's width at compile time
 		uint64_t *kin = P<uint64_t>(c->key[g]), *kout = P<uint64_t>(c->key[g ^ 1]);
 		uint32_t *vin = P<uint32_t>(c->val[g]), *vout = P<uint32_t>(c->val[g ^ 1]);
 		uint32_t *hist, *hpre, *htot;
@@ -348,14 +350,16 @@ static int radix_sort_impl(mahip_ctx *c, size_t n, int lo0, int hi0, int lo1, in
 			const RsGroups nog = {nullptr, 0, 0};
 			if (groups && p == np - 1) { // the last pass notes the group starts
 				const RsGroups gg = {groups->start, groups->lo, groups->n_id};
-				if (bits[p] == 7) hipLaunchKernelGGL((k_radix_scatter<false, 7, true>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], gg);
+				c->rs_last.groups = 1;
+				if (w7) hipLaunchKernelGGL((k_radix_scatter<false, 7, true>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], gg);
 				else hipLaunchKernelGGL((k_radix_scatter<false, 0, true>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], gg);
 			}
-			else if (has_val && bits[p] == 7) hipLaunchKernelGGL((k_radix_scatter<true, 7>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
+			else if (has_val && w7) hipLaunchKernelGGL((k_radix_scatter<true, 7>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
 			else if (has_val) hipLaunchKernelGGL((k_radix_scatter<true, 0>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
-			else if (bits[p] == 7) hipLaunchKernelGGL((k_radix_scatter<false, 7>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
+			else if (w7) hipLaunchKernelGGL((k_radix_scatter<false, 7>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
 			else hipLaunchKernelGGL((k_radix_scatter<false, 0>), gr, bl, 0, c->st, kin, vin, kout, vout, ro, n, nb, shift[p], mask, bits[p], nog);
 		}
+		c->rs_last.bits[p] = bits[p]; c->rs_last.shift[p] = shift[p]; c->rs_last.fixed7 |= (uint32_t)w7 << p; c->rs_last.n_pass = p + 1;
 		g ^= 1;
 	}
 	HIPCHK(hipGetLastError());

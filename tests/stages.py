@@ -1193,3 +1193,138 @@ def chain_graph(L, ring=False, first=0, mixed=False, gb=None):
     r = np.r_[r[first:], r[:first]] if first else r
     gb.path(np.r_[r, r[:1]] if ring else r, 700 + np.arange(L - 1 + (1 if ring else 0)) % 50)
     return gb.finish(d_len=7) if own else r
+
+
+# --------------------------------------------------------------------------------------------- the hit sort at its size edges (tests/test_gpu_sort_edges.py)
+class SortInfo(C.Structure):  # include/mahip.h: mahip_sort_info_t
+    _fields_ = [("path", C.c_int), ("fallback", C.c_int), ("n_elem", C.c_uint64), ("n_runs_seen", C.c_uint64), ("n_pass", C.c_int), ("bits", C.c_int * 8),
+                ("shift", C.c_int * 8), ("fixed7", C.c_uint32), ("groups", C.c_int)]
+
+
+SORT_PATHS = {0: None, 1: "runs", 2: "records_fused_hist", 3: "records_plain"}  # MAHIP_SORT_*
+RUNS_FALLBACKS = {0: None, 1: "not_tried", 2: "few_runs", 3: "id_range", 4: "interleaved", 5: "field_width"}  # MAHIP_RUNS_*
+RUN_SLAB = 1024  # csrc/hits.hip: a run never crosses a border of 1024 records
+
+
+def sort_api():
+    L = ma.lib()
+    vp = C.c_void_p
+    L.mahip_sort_last.argtypes = [vp, C.POINTER(SortInfo)]
+    L.mahip_hits_layout_download.argtypes = [vp, vp, vp]
+    L.mahip_set_hints.argtypes = [vp, C.c_uint32]
+    L.mahip_set_shard.argtypes = [vp, C.c_uint32, C.c_uint32]
+    return L
+
+
+def sort_last(ctx):
+    """mahip_sort_last as a dict: path and fallback as names, n_elem, n_runs_seen, bits / shift per pass, fixed7 per pass, groups"""
+    s = SortInfo()
+    ma._chk(sort_api().mahip_sort_last(ctx.h, C.byref(s)), "sort_last")
+    return dict(path=SORT_PATHS[s.path], fallback=RUNS_FALLBACKS[s.fallback], n_elem=int(s.n_elem), n_runs_seen=int(s.n_runs_seen), bits=list(s.bits)[:s.n_pass],
+                shift=list(s.shift)[:s.n_pass], fixed7=[bool(s.fixed7 >> p & 1) for p in range(s.n_pass)], groups=bool(s.groups))
+
+
+def layout_download(ctx, n_hits, n_seq):
+    """mahip_hits_layout_download -> (sidx[n_hits], goff[n_seq + 1]): the layout the sort itself made"""
+    sidx, goff = np.zeros(max(n_hits, 1), dtype="<u4"), np.zeros(n_seq + 1, dtype="<u4")
+    ma._chk(sort_api().mahip_hits_layout_download(ctx.h, sidx.ctypes.data, goff.ctypes.data), "hits_layout_download")
+    return sidx[:n_hits], goff
+
+
+def sort_hits(qid, qs=None, seed=0):
+    """records with the given query ids; qe = input position, so no two records are equal and every slot says which record it holds.
+    qs None: every record of a read has the same start (the order inside a group that a dump shows is then the resident order); else the starts given"""
+    qid = np.asarray(qid, dtype=np.uint64)
+    n = len(qid)
+    rng = np.random.default_rng(77 + seed)
+    qs = (qid * np.uint64(7919)) % np.uint64(5000) if qs is None else np.asarray(qs, dtype=np.uint64)
+    h = np.zeros(n, dtype=HIT_DT)
+    h["qns"] = qid << np.uint64(32) | qs
+    h["qe"] = np.arange(n, dtype=np.uint32)
+    h["tn"] = (qid + np.uint64(1)) % (qid.max() + np.uint64(1)) if n else 0  # some id of the input: in the dictionary wherever the query ids are
+    h["ts"] = rng.integers(0, 5000, n); h["te"] = h["ts"] + rng.integers(1, 5000, n).astype(np.uint32)
+    h["bldel"] = 1000; h["mlrev"] = 900
+    return h
+
+
+def run_hits(runs, stride, mirror_ids=None):
+    """[(qid, run length)] -> query ids of a stride-1 array (the runs one behind the other) or a stride-2 array (every record of a run followed by a
+    mirrored single: an id out of mirror_ids, taken in turn -- at least two ids, none a run's id, so that every odd position is a run of one)"""
+    r = np.asarray(runs, dtype=np.int64).reshape(-1, 2)
+    own = np.repeat(r[:, 0], r[:, 1])
+    if stride == 1:
+        return own
+    assert stride == 2 and len(mirror_ids) >= 2 and not set(np.asarray(mirror_ids).tolist()) & set(r[:, 0].tolist())
+    out = np.empty(2 * len(own), dtype=np.int64)
+    out[0::2] = own
+    out[1::2] = np.asarray(mirror_ids, dtype=np.int64)[np.arange(len(own)) % len(mirror_ids)]
+    return out
+
+
+def run_list(qid, stride):
+    """the run model (csrc/hits.hip: k_hit_keys_runs): record p is a head if it stands less than `stride` records behind the start of its slab of 1024, or
+    qid[p - stride] != qid[p]; a run goes on at this stride until the next head of its parity class or the slab's end.  -> (id, first position, length) per run,
+    in input order of the first positions"""
+    qid = np.asarray(qid, dtype=np.int64)
+    n = len(qid)
+    head = (np.arange(n) % RUN_SLAB) < stride
+    head[stride:] |= qid[stride:] != qid[:-stride]
+    pos, ln = [], []
+    for cls in range(stride):
+        sub = head[cls::stride]
+        i = np.flatnonzero(sub)
+        pos.append(i * stride + cls)
+        ln.append(np.diff(np.r_[i, len(sub)]))
+    pos, ln = np.concatenate(pos), np.concatenate(ln)
+    o = np.argsort(pos, kind="stable")
+    assert len(pos) == int(head.sum()) and int(ln.sum()) == n
+    return qid[pos[o]], pos[o], ln[o]
+
+
+def bit_length(x):
+    return max(int(x).bit_length(), 1)
+
+
+def digit_plan(lo, nbits, max_bits=9):
+    """csrc/radix.hip plan_digits: as few passes as possible, each at most 9 bits, widths balanced -> (shift, bits) per pass"""
+    np_ = (nbits + max_bits - 1) // max_bits
+    out, s = [], lo
+    for i in range(np_):
+        w = (nbits - (s - lo) + (np_ - i) - 1) // (np_ - i)
+        out.append((s, w)); s += w
+    return out
+
+
+def sort_model(qid, stride, n_seq):
+    """what mahip_hits_sort must report for an unsharded context: dict(path, fallback, n_elem, bits, shift, groups).  The runs path is taken when a stride is
+    set, the dictionary size is known, id | position | length fit one word with at least 10 length bits, every id is < n_seq, there are at most three runs per
+    four records and no two runs of one read interleave (the later one starts at or in front of the earlier one's last record)"""
+    qid = np.asarray(qid, dtype=np.int64)
+    n = len(qid)
+    bi = bit_length(n - 1)
+    bq = bit_length(n_seq - 1) if n_seq else bit_length(qid.max())
+    M = dict(path="records_fused_hist", fallback=None, n_elem=n, n_runs=0, groups=bool(n_seq))
+    lo = bi
+    if stride:
+        if not n_seq:
+            M["fallback"] = "not_tried"
+        elif 64 - bq - bi < 10:
+            M["fallback"] = "field_width"
+        else:
+            rid, rpos, rlen = run_list(qid, stride)
+            M["n_runs"] = len(rid)
+            o = np.argsort(rid, kind="stable")
+            sid, spos, slen = rid[o], rpos[o], rlen[o]
+            inter = (sid[1:] == sid[:-1]) & (spos[1:] <= spos[:-1] + stride * (slen[:-1] - 1))
+            if (qid >= n_seq).any():
+                M["fallback"] = "id_range"
+            elif len(rid) * 4 > n * 3:
+                M["fallback"] = "few_runs"
+            elif inter.any():
+                M["fallback"] = "interleaved"
+            else:
+                M.update(path="runs", n_elem=len(rid), groups=False)
+                lo = bi + min(16, 64 - bq - bi)
+    plan = digit_plan(lo, bq)
+    M["shift"], M["bits"] = [p[0] for p in plan], [p[1] for p in plan]
+    return M

@@ -10,7 +10,10 @@ on 8 cores).  The default `-m "not gpu"` selection of this file took 12 min 46 s
 added; that module adds about half a minute (15 s in normal order, 16 s reversed with guard pages), so none of its cases is held back for MA_EMU_FULL.
 tests/test_gpu_clean_edges.py adds about a minute: 30 s in normal order (its three child processes and the 8 193-bubble input, 2 s, included) and 30 s
 reversed with guard pages.  Its 196 608 / 196 609-entry probes take 63 s alone and are held back for MA_EMU_FULL=1, so by default the CPU build does not reach
-bubble tiers 3 and 4; they run by default under `-m gpu`."""
+bubble tiers 3 and 4; they run by default under `-m gpu`.
+tests/test_gpu_sort_edges.py adds about three minutes: 62 to 69 s in normal order for its 217 cases (the 526 337-id case takes under a second, so it is not held
+back) and 131 s reversed with guard pages, the latter measured while other builds were using the box.  Its production-form case (67 M records) skips itself on
+the CPU build."""
 import os
 import subprocess
 import sys
@@ -76,6 +79,7 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     run_gpu_tests(["tests/test_gpu_fused_hits.py", "-k", "group_size_edges"], 3000, env)  # tier B's global scratch (4097 and 9001 hits) ends at a guard page too
     run_gpu_tests(["tests/test_gpu_graph_edges.py"], 3000, env)  # the arc sort's rows, the reduction's neighbour lists and the cleanup's tails at their size edges
     run_gpu_tests(["tests/test_gpu_clean_edges.py"] + CLEAN_EDGES_SEL, 3000, env)  # the bubble tables, stacks and stamp arrays at their borders; the wave form without lock-step
+    run_gpu_tests(["tests/test_gpu_sort_edges.py"], 3000, env)  # rkey[r00 - 1], the n + 128 padding of sidx, the rows / chunk sums / totals of the radix histograms and the tile minima of the group starts
 
 
 def test_kernels_graph_api_on_cpu(emu_built):
@@ -88,6 +92,12 @@ def test_graph_size_edges_on_cpu(emu_built):
     """tests/test_gpu_graph_edges.py: the graph kernels at every size edge they branch on (arcs per read, arcs per vertex and per expanded neighbour, arc counts
     of the cleanup), every one against the oracle and the reference library; a quarter of a minute"""
     run_gpu_tests(["tests/test_gpu_graph_edges.py"], 1800)
+
+
+def test_sort_size_edges_on_cpu(emu_built):
+    """tests/test_gpu_sort_edges.py: the hit sort's own result (sidx, goff) and its report at every size the sort branches on, runs path, record paths, shard
+    form and order sort; only the production-form case (67 M records) needs a real device and skips itself here"""
+    run_gpu_tests(["tests/test_gpu_sort_edges.py"], 1800)
 
 
 CLEAN_EDGES_SEL = [] if FULL else ["-k", "not border[3]"]  # the 196 608 / 196 609-entry probes (tiers 3 and 4): MA_EMU_FULL=1
