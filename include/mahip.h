@@ -77,6 +77,31 @@ int mahip_paf_names(mahip_ctx_t *c, char *names, uint32_t *lens);
 /* the same as ready-made sd_seq_t records (sdict.h:6-10) whose name pointers point into `names` (a host block of name_bytes): seqs16[n_seq * 16 bytes] */
 int mahip_paf_seqs(mahip_ctx_t *c, char *names, void *seqs16, uint64_t *tot_len);          /* names[name_bytes], lens[n_seq] = first-seen read lengths */
 int mahip_paf_release(mahip_ctx_t *c);                                      /* free the text and the per-line columns */
+/* For stage tests: what the LAST mahip_paf_parse* of this context decided and counted (host bookkeeping, read-only), and its per-line columns.  Both are valid
+ * from the parse until mahip_paf_release and fail afterwards.  n_gran: KiB granules of the text (the appended newline of an open last line included);
+ * tile_k / n_tiles: granules per tile, tiles; tile_form: KiB of text a block of the tile parser stages / 16 (1 or 2); n_odd: lines the tile parser left to the
+ * byte-wise routine, odd_ran: that kernel was launched; n_long: stored lines with a name that is not 1..8 bytes; dict_form: the short-key or the text-comparing
+ * name table (0: no stored line, no table); the insert pass ran n_attempts times, attempt a on a table of cap[a] slots, and ended as end[a] says (LOAD: more
+ * than cap / 2 distinct names; PROBES: a probe sequence ran out); n_distinct: names the last attempt counted (with -R: before the exclusion); bl_pass: the
+ * pass that hands 10-column lines their stale `bl` ran; n_excl as in mahip_paf_info_t.  After mahip_paf_parse_sharded: this rank's range, bl_pass 0. */
+enum { MAHIP_PAF_DICT_NONE = 0, MAHIP_PAF_DICT_SHORT = 1, MAHIP_PAF_DICT_TEXT = 2 };
+enum { MAHIP_PAF_TAB_OK = 0, MAHIP_PAF_TAB_LOAD = 1, MAHIP_PAF_TAB_PROBES = 2 };
+typedef struct {
+	uint64_t n_lines, n_odd, n_long, n_distinct;
+	uint32_t n_gran, tile_k, n_tiles, n_excl;
+	int tile_form, open_line, odd_ran, dict_form, bl_pass, n_attempts;
+	uint32_t cap[4];
+	int end[4];
+} mahip_paf_report_t;
+int mahip_paf_last(mahip_ctx_t *c, mahip_paf_report_t *out);
+/* host arrays, any of them NULL: flags[n_lines] (bit0 valid, bit1 stored, bit2 has column 11, bit3 rev, 0x10: the query name is that of the stored line in
+ * front of it and the tile parser saw it), odd[n_lines] (1: the line went through the byte-wise routine; needs mahip_paf_keep_odd), nums[8][n_lines] (ql qs qe tl
+ * ts te ml bl), tnoff / qlen / tlen[n_lines] (target-name offset in the line, name lengths), lstart[n_lines + 1], tfirst[n_tiles] (start of the first line
+ * that ends in each tile).  Columns of lines with fewer than 10 columns are unspecified. */
+int mahip_paf_cols_download(mahip_ctx_t *c, uint8_t *flags, uint8_t *odd, uint32_t *nums, uint32_t *tnoff, uint32_t *qlen, uint32_t *tlen, uint64_t *lstart, uint64_t *tfirst);
+/* on: every following parse of this context copies, between the tile parser and the byte-wise kernel, which lines wait for the latter (one D2H copy of the
+ * flags: for tests, not for production runs).  Off by default. */
+int mahip_paf_keep_odd(mahip_ctx_t *c, int on);
 uint32_t mahip_paf_max_qs(mahip_ctx_t *c);                                  /* info.max_qs of the last parse (a sort hint for later mahip_hits_adopt calls) */
 int mahip_hits_raw_download(mahip_ctx_t *c, ma_hit_t *out);                 /* the unsorted records held by the context (n_hits of them) */
 /* device-to-device: the unsorted records whose query id lies in [q_beg,q_end), in input order, into d_dst (NULL: only count

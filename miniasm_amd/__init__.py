@@ -89,6 +89,22 @@ FASTX_FORMATS = {0: None, 1: "fasta", 2: "fastq"}
 USEQ_READERS = {0: None, 1: "host", 2: "device"}
 
 
+class PafInfo(C.Structure):  # include/mahip.h: mahip_paf_info_t
+    _fields_ = [("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("n_stored_lines", C.c_uint64), ("n_hits", C.c_uint64), ("name_bytes", C.c_uint64),
+                ("n_seq", C.c_uint32), ("max_qs", C.c_uint32), ("n_excl", C.c_uint32)]
+
+
+class PafReport(C.Structure):  # include/mahip.h: mahip_paf_report_t
+    _fields_ = [("n_lines", C.c_uint64), ("n_odd", C.c_uint64), ("n_long", C.c_uint64), ("n_distinct", C.c_uint64),
+                ("n_gran", C.c_uint32), ("tile_k", C.c_uint32), ("n_tiles", C.c_uint32), ("n_excl", C.c_uint32),
+                ("tile_form", C.c_int), ("open_line", C.c_int), ("odd_ran", C.c_int), ("dict_form", C.c_int), ("bl_pass", C.c_int), ("n_attempts", C.c_int),
+                ("cap", C.c_uint32 * 4), ("end", C.c_int * 4)]
+
+
+PAF_DICT_FORMS = {0: None, 1: "short", 2: "text"}  # MAHIP_PAF_DICT_*
+PAF_TAB_ENDS = {0: "ok", 1: "load", 2: "probes"}   # MAHIP_PAF_TAB_*
+
+
 class ProfRec(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -136,6 +152,11 @@ def lib():
         L.mahip_paf_load_fd.argtypes = [vp, i32, sz]
         L.mahip_paf_load_mem.argtypes = [vp, vp, sz]
         L.mahip_hits_raw_download.argtypes = [vp, vp]
+        L.mahip_paf_parse_excl.argtypes = [vp, i32, i32, i32, i32, i32, C.c_float, C.POINTER(PafInfo)]
+        L.mahip_paf_names.argtypes = [vp, vp, vp]
+        L.mahip_paf_last.argtypes = [vp, C.POINTER(PafReport)]
+        L.mahip_paf_cols_download.argtypes = [vp] + [vp] * 8
+        L.mahip_paf_keep_odd.argtypes = [vp, i32]
         L.mahip_hits_sort.argtypes = [vp]
         L.mahip_hits_index.argtypes = [vp]
         L.mahip_hits_sub.argtypes = [vp, i32, C.c_float, i32, i32, C.POINTER(sz)]

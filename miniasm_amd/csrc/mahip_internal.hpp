@@ -125,6 +125,7 @@ struct mahip_ctx {
 	uint32_t scan_ticket = 0, scan_epoch = 0; // scan.hip: tickets handed out so far, launch number
 	void *xfer = nullptr;      // staged-copy worker pool (xfer.hip)
 	void *paf = nullptr;       // text-ingest buffers (paf.hip)
+	bool paf_keep_odd = false; // mahip_paf_keep_odd: the next parses keep a host snapshot of the lines left to the byte-wise parser (tests)
 
 	hipEvent_t mark_ev[64] = {}; // phase marks (mahip_mark)
 	hipStream_t sub_side[2] = {}; hipEvent_t sub_ev[3] = {}; // side streams of the coverage passes' size classes (hits.hip: SubFork)

@@ -40,6 +40,10 @@ struct PafBufs {
 	size_t nbytes = 0, name_bytes = 0;
 	uint32_t n_seq = 0;
 	bool loaded = false;
+	// what the last parse decided and counted (mahip_paf_last / mahip_paf_cols_download: host bookkeeping, read-only)
+	bool parsed = false;
+	mahip_paf_report_t rep = {};
+	std::vector<uint8_t> odd_snap; // mahip_paf_keep_odd: per line, flags == PF_ODD between the tile parser and k_paf_parse_odd
 };
 
 struct PafCols {
@@ -1019,6 +1023,8 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	unsigned long long *ctr = P<unsigned long long>(c->ctr);
 	memset(info, 0, sizeof(*info));
 	b->n_seq = 0; b->name_bytes = 0;
+	b->parsed = false; b->rep = {}; b->odd_snap.clear();
+	mahip_paf_report_t &rp = b->rep;
 	// MA_PIPE_TIMING=2: wall-clock laps of this function's parts on stderr (each lap waits for the stream: a diagnostic, it changes what it measures by the waits)
 	const bool laps = ma_timing_level() >= 2;
 	struct timespec lap_t0;
@@ -1113,19 +1119,29 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			const uint32_t reg = (uint32_t)ch * 16384u, lds = reg + 32 + 2 * (reg / 16 + 8) * 2 + 260 * 4;
 			uint32_t per_cu = (160u * 1024u) / (lds + 64u); if (per_cu > 8) per_cu = 8; // blocks a CU holds: the grid is what fits the chip, a block works through tiles (one set of counter atomics per block)
 			const unsigned grid = grid_for(n_tiles, 1, 256u * per_cu);
+			rp.tile_form = ch;
 			if (ch == 1) hipLaunchKernelGGL(k_paf_parse_tile<1>, dim3(grid), dim3(256), lds, c->st, ta, o, P<uint64_t>(b->lstart), ctr);
 			else hipLaunchKernelGGL(k_paf_parse_tile<2>, dim3(grid), dim3(256), lds, c->st, ta, o, P<uint64_t>(b->lstart), ctr);
 		}
 		CHK(ctr_fetch(c));
+		rp.n_odd = c->h_ctr[PC_ODD];
+		if (c->paf_keep_odd) { // tests: which lines the tile parser left to the byte-wise routine (the final flags do not say)
+			b->odd_snap.resize(L);
+			HIPCHK(hipMemcpyAsync(b->odd_snap.data(), o.flags, L, hipMemcpyDeviceToHost, c->st));
+			HIPCHK(hipStreamSynchronize(c->st));
+			for (uint8_t &f : b->odd_snap) f = f == PF_ODD;
+		}
 		if (c->h_ctr[PC_ODD]) { // lines the straight-line parser does not cover: the byte-wise routine on them (the counters add up)
 			ProfScope ps(c, "k_paf_parse_odd", 0.0);
 			hipLaunchKernelGGL(k_paf_parse_odd, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, min_span, min_match, o, ctr);
 			CHK(ctr_fetch(c));
+			rp.odd_ran = 1;
 		}
 		n_valid = (size_t)c->h_ctr[PC_VALID]; n_pass = (size_t)c->h_ctr[PC_PASS]; n_nobl = (size_t)c->h_ctr[PC_NOBL];
 		n_long = (size_t)c->h_ctr[PC_LONG];
 		max_qs = (uint32_t)c->h_ctr[PC_MAXQS];
 		if (n_nobl && !sharded) { // stale bl: rare (PAF writers emit 12+ columns)
+			rp.bl_pass = 1;
 			CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
 			hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
 			CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, nullptr));
@@ -1133,6 +1149,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			hipLaunchKernelGGL(k_paf_bl_fill, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->blv), L, o.bl);
 		}
 	}
+	rp.n_lines = L; rp.n_gran = n_gran; rp.tile_k = tile_k; rp.n_tiles = n_tiles; rp.open_line = open_line; rp.n_long = n_long;
 	lap("fields");
 	uint64_t nobl_total = n_nobl;
 	if (sharded) { // what the ranges have to know of each other before names and records can be numbered
@@ -1177,6 +1194,7 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 		uint32_t cap = pow2_at_least(n_pass / 16 + 65536);
 		if (const char *e = getenv("MA_DICT_CAP_LOG2")) { int l2 = atoi(e); if (l2 >= 4 && l2 <= 31) cap = 1u << l2; } // tests: force the growth path
 		const bool short_names = n_long == 0 && !getenv("MA_DICT_EXACT_TEXT"); // every name is its own key: no text compared (k_dict_insert_short)
+		rp.dict_form = short_names ? MAHIP_PAF_DICT_SHORT : MAHIP_PAF_DICT_TEXT;
 		for (int attempt = 0;; ++attempt) {
 			CHK(dev_reserve(c, b->tab, (size_t)cap * 16)); CHK(dev_reserve(c, b->tmin, (size_t)cap * 4)); CHK(dev_reserve(c, b->slot_id, (size_t)cap * 4));
 			CHK(ctr_zero(c));
@@ -1191,6 +1209,8 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 			}
 			CHK(ctr_fetch(c));
 			const uint64_t distinct = c->h_ctr[PC_DISTINCT];
+			rp.n_attempts = attempt + 1; rp.cap[attempt] = cap; rp.n_distinct = distinct;
+			rp.end[attempt] = c->h_ctr[PC_OVERFLOW] ? MAHIP_PAF_TAB_PROBES : 2 * distinct > cap ? MAHIP_PAF_TAB_LOAD : MAHIP_PAF_TAB_OK;
 			if (c->h_ctr[PC_OVERFLOW] == 0 && 2 * distinct <= cap) break;
 			if (attempt >= 3 || cap >= cap_max) { if (c->h_ctr[PC_OVERFLOW] == 0) break; mahip_set_error("mahip_paf_parse: name table overflow"); return -1; }
 			uint32_t want = pow2_at_least(4 * distinct + 65536);
@@ -1356,6 +1376,8 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(c->st));
 	c->hint_max_qs = c->paf_max_qs = max_qs;
+	rp.n_excl = info->n_excl;
+	b->parsed = true;
 	c->run_stride = sharded ? 0 : bi_dir ? 2 : 1; // k_paf_emit_chain wrote a line's record and its mirror side by side (hit.c:87-98): the sort may take RUNS of records (hits.hip)
 	info->n_records = n_valid; info->n_stored_lines = n_pass; info->n_hits = n_hits; info->n_seq = R; info->max_qs = max_qs; info->name_bytes = b->name_bytes; info->n_lines = L;
 	if (sharded) { info->n_records = valid_total; info->n_stored_lines = pass_total; info->n_lines = lines_total; }
@@ -1409,6 +1431,46 @@ extern "C" int mahip_paf_seqs(mahip_ctx_t *c, char *names, void *seqs16, uint64_
 	if (tot_len) *tot_len = c->h_ctr[PC_VALID];
 	CHK(xfer_copy(c, b->names.p, names, b->name_bytes, 0));
 	CHK(xfer_copy(c, c->key[0].p, seqs16, (size_t)R * 16, 0));
+	return 0;
+}
+
+// ---- for stage tests: what the last parse decided, and its per-line columns (valid from mahip_paf_parse* to mahip_paf_release)
+extern "C" int mahip_paf_keep_odd(mahip_ctx_t *c, int on)
+{
+	c->paf_keep_odd = on != 0;
+	return 0;
+}
+static PafBufs *paf_parsed(mahip_ctx *c, const char *who)
+{
+	PafBufs *b = (PafBufs*)c->paf;
+	if (!b || !b->parsed) { mahip_set_error("%s: no parsed text in this context (not parsed yet, or released)", who); return nullptr; }
+	return b;
+}
+extern "C" int mahip_paf_last(mahip_ctx_t *c, mahip_paf_report_t *out)
+{
+	PafBufs *b = paf_parsed(c, "mahip_paf_last");
+	if (!b) return -1;
+	if (out) *out = b->rep;
+	return 0;
+}
+extern "C" int mahip_paf_cols_download(mahip_ctx_t *c, uint8_t *flags, uint8_t *odd, uint32_t *nums, uint32_t *tnoff, uint32_t *qlen, uint32_t *tlen, uint64_t *lstart, uint64_t *tfirst)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	PafBufs *b = paf_parsed(c, "mahip_paf_cols_download");
+	if (!b) return -1;
+	const size_t L = (size_t)b->rep.n_lines;
+	if (odd) {
+		if (b->odd_snap.size() != L) { mahip_set_error("mahip_paf_cols_download: no snapshot of the odd lines (mahip_paf_keep_odd was off during the parse)"); return -1; }
+		if (L) memcpy(odd, b->odd_snap.data(), L);
+	}
+	if (L == 0) return 0;
+	if (flags) CHK(xfer_copy(c, b->flags.p, flags, L, 0));
+	if (nums) for (int k = 0; k < 8; ++k) CHK(xfer_copy(c, b->num[k].p, nums + (size_t)k * L, L * 4, 0));
+	if (tnoff) CHK(xfer_copy(c, b->tnoff.p, tnoff, L * 4, 0));
+	if (qlen) CHK(xfer_copy(c, b->qlen.p, qlen, L * 4, 0));
+	if (tlen) CHK(xfer_copy(c, b->tlen.p, tlen, L * 4, 0));
+	if (lstart) CHK(xfer_copy(c, b->lstart.p, lstart, (L + 1) * 8, 0));
+	if (tfirst && b->rep.n_tiles) CHK(xfer_copy(c, b->tfirst.p, tfirst, (size_t)b->rep.n_tiles * 8, 0));
 	return 0;
 }
 

@@ -13,7 +13,9 @@ reversed with guard pages.  Its 196 608 / 196 609-entry probes take 63 s alone a
 bubble tiers 3 and 4; they run by default under `-m gpu`.
 tests/test_gpu_sort_edges.py adds about three minutes: 62 to 69 s in normal order for its 217 cases (the 526 337-id case takes under a second, so it is not held
 back) and 131 s reversed with guard pages, the latter measured while other builds were using the box.  Its production-form case (67 M records) skips itself on
-the CPU build."""
+the CPU build.
+tests/test_gpu_ingest_edges.py adds about two minutes: 45 s in normal order for its 68 tests (about 700 texts; the group-fallback texts of 4 to 8.5 MiB take
+4 s together, so none is held back for MA_EMU_FULL) and 58 s reversed with guard pages, both measured while other builds were using the box."""
 import os
 import subprocess
 import sys
@@ -79,6 +81,7 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     run_gpu_tests(["tests/test_gpu_fused_hits.py", "-k", "group_size_edges"], 3000, env)  # tier B's global scratch (4097 and 9001 hits) ends at a guard page too
     run_gpu_tests(["tests/test_gpu_graph_edges.py"], 3000, env)  # the arc sort's rows, the reduction's neighbour lists and the cleanup's tails at their size edges
     run_gpu_tests(["tests/test_gpu_clean_edges.py"] + CLEAN_EDGES_SEL, 3000, env)  # the bubble tables, stacks and stamp arrays at their borders; the wave form without lock-step
+    run_gpu_tests(["tests/test_gpu_ingest_edges.py"], 3000, env)  # the staged over-read in front of a tile, the n + 64 padding of the text, s_lend[256], lstart[L], cnt[n_gran]
     run_gpu_tests(["tests/test_gpu_sort_edges.py"], 3000, env)  # rkey[r00 - 1], the n + 128 padding of sidx, the rows / chunk sums / totals of the radix histograms and the tile minima of the group starts
 
 
@@ -113,6 +116,12 @@ def test_tie_filter_on_cpu(emu_built):
     """tests/test_gpu_cli.py: push conflicts the reference's arc sort cannot see -- the hit walk is skipped, every dump equals the reference's byte for byte; and the
     realistic inputs (jittered coordinates, lines grouped by target) through both walks"""
     run_gpu_tests(["tests/test_gpu_cli.py", "-k", "out_of_sight or in_sight_only or (tie_rich and jitter and default)"], 3000)
+
+
+def test_ingest_size_edges_on_cpu(emu_built):
+    """tests/test_gpu_ingest_edges.py: the device PAF reader stage by stage (tile parser against byte-wise kernel, tile geometry, group fallback, stale bl, both
+    dictionary forms and the table growth, query runs, records, -R) against a model, the host reader and the reference library; three quarters of a minute"""
+    run_gpu_tests(["tests/test_gpu_ingest_edges.py"], 1800)
 
 
 def test_kernels_ingest_on_cpu(emu_built):
