@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void k_hit_gather(const ma_hit_t *__restrict__
 	}
 }
 
-// group offsets alone, from the sorted keys (the gather itself is left to the first coverage pass: k_hit_sub<false,*,true>)
+// group offsets alone, from the sorted keys (the gather itself is left to the first coverage pass: k_hit_sub<false,*,1>)
 // On a shard the reads below q_lo and above q_hi have no hits here: their (empty) groups are written by k_goff_outside, all lanes at once -- left to the
 // thread that meets the first hit / the sentinel they were one serial loop over up to 7/8 of the reads (found by the round-3 projection: 17 - 29 ms per pass
 // on every rank of a sharded run, however small its shard).
@@ -366,25 +366,61 @@ struct SubFuse {
 };
 struct SubAcc { uint32_t n_cut, n_flt; uint64_t dp; }; // per-lane partial counters of the fused passes
 
+// ---- the per-hit rules of ma_hit_cut, ma_hit_flt and ma_hit_contained, each stated once for every kernel that applies it (the stand-alone passes further
+// down, the fused coverage pass, k_hit_cut_contained).  A kernel fetches the hit's columns and its two reads' intervals in its own order; the rules only compute. ----
+__device__ __forceinline__ uint32_t sub_len(uint2 s) { return s.y - (s.x & 0x7fffffffu); } // length of a kept interval (s is a 31-bit field under the del bit)
+__device__ __forceinline__ bool subs_live(uint2 rq, uint2 rt) { return !(rq.x & DEAD) && !(rt.x & DEAD); } // neither read lost its interval (hit.c:171, 201)
+
+// ma_hit_cut (hit.c:162-193): the hit dies with either read's interval, else it is clipped to both and must still span min_span; the coordinates change only if it stays
+__device__ __forceinline__ int hit_cut(uint2 rq, uint2 rt, uint32_t &qs, uint32_t &qe, uint32_t &ts, uint32_t &te, uint32_t ml, int min_span)
+{
+	return subs_live(rq, rt) && mc_cut(&qs, &qe, &ts, &te, ml >> 31, (int32_t)rq.x, rq.y, (int32_t)rt.x, rt.y, min_span);
+}
+// the clipped coordinates of a hit that stays: most hits lie inside both intervals, untouched columns are not written back
+__device__ __forceinline__ void store_cut_cols(const HitCols &c, size_t i, uint32_t qs, uint32_t qe, uint32_t ts, uint32_t te, uint32_t oqs, uint32_t oqe, uint32_t ots, uint32_t ote)
+{
+	if (qs != oqs) c.qs[i] = qs;
+	if (qe != oqe) c.qe[i] = qe;
+	if (ts != ots) c.ts[i] = ts;
+	if (te != ote) c.te[i] = te;
+}
+// ma_hit_flt (hit.c:195-216; int_frac is the literal .5 there) for a hit whose reads both have an interval: arcs and containments stay.  A kept hit adds its
+// share to the coverage estimate (dp) and marks its query group (r_live)
+__device__ __forceinline__ int hit_flt(uint32_t q, uint32_t qs, uint32_t qe, uint32_t tn, uint32_t ts, uint32_t te, uint32_t ml, uint2 sq, uint2 st,
+                                       int max_hang, int min_ovlp, uint64_t &dp, uint8_t *r_live)
+{
+	mc_arc_t a;
+	const uint32_t ql = sub_len(sq), tl = sub_len(st);
+	const int r = mc_hit2arc(q, qs, qe, tn, ts, te, ml >> 31, (int)ql, (int)tl, max_hang, .5f, min_ovlp, &a);
+	if (r >= 0 || r == MC_HT_QCONT || r == MC_HT_TCONT) {
+		dp += r >= 0 ? (uint32_t)r : r == MC_HT_QCONT ? ql : tl;
+		r_live[q] = 1;
+		return 1;
+	}
+	return 0;
+}
+// pass 1 of ma_hit_contained for one live hit (hit.c:225-256, hit.c:24-36): classified with the final thresholds; contained reads and reads touched by any hit
+__device__ __forceinline__ void hit_contained_flags(uint32_t q, uint32_t qs, uint32_t qe, uint32_t t, uint32_t ts, uint32_t te, uint32_t ml, uint2 sq, uint2 st,
+                                                    int max_hang, float int_frac, int min_ovlp, uint8_t *r_cont, uint8_t *r_used)
+{
+	mc_arc_t a;
+	const int r = mc_hit2arc(q, qs, qe, t, ts, te, ml >> 31, (int)sub_len(sq), (int)sub_len(st), max_hang, int_frac, min_ovlp, &a);
+	if (r == MC_HT_QCONT) r_cont[q] = 1;
+	else if (r == MC_HT_TCONT) r_cont[t] = 1;
+	r_used[q] = 1; r_used[t] = 1;
+}
+
 // cut + filter of one live hit held in registers; returns 0 if the hit dies (its dead bit is written), else 1
 __device__ __forceinline__ int fuse_cut_flt_v(const HitCols &c, uint32_t i, const SubFuse &f, uint32_t q, uint2 rq, uint32_t tn,
                                               uint32_t &qs, uint32_t &qe, uint32_t ml, uint32_t bl, SubAcc &acc, uint2 rt, uint32_t ts, uint32_t te)
 { // rt = the target's interval, ts/te = the hit's target columns: fetched by the caller (ahead of time in the SMALL kernels)
 	int keep = 0;
 	const uint32_t oqs = qs, oqe = qe, ots = ts, ote = te;
-	if (!(rq.x & DEAD) && !(rt.x & DEAD) && mc_cut(&qs, &qe, &ts, &te, ml >> 31, (int32_t)rq.x, rq.y, (int32_t)rt.x, rt.y, f.min_span)) {
-		mc_arc_t a;
-		uint32_t ql = rq.y - (rq.x & 0x7fffffffu), tl = rt.y - (rt.x & 0x7fffffffu);
+	if (hit_cut(rq, rt, qs, qe, ts, te, ml, f.min_span)) {
 		++acc.n_cut;
-		int r = mc_hit2arc(q, qs, qe, tn, ts, te, ml >> 31, (int)ql, (int)tl, f.max_hang, .5f, f.min_ovlp, &a);
-		if (r >= 0 || r == MC_HT_QCONT || r == MC_HT_TCONT) {
+		if (hit_flt(q, qs, qe, tn, ts, te, ml, rq, rt, f.max_hang, f.min_ovlp, acc.dp, f.r_live)) {
 			keep = 1; ++acc.n_flt;
-			acc.dp += r >= 0 ? (uint32_t)r : r == MC_HT_QCONT ? ql : tl;
-			f.r_live[q] = 1;
-			if (qs != oqs) c.qs[i] = qs; // untouched columns are not written back
-			if (qe != oqe) c.qe[i] = qe;
-			if (ts != ots) c.ts[i] = ts;
-			if (te != ote) c.te[i] = te;
+			store_cut_cols(c, i, qs, qe, ts, te, oqs, oqe, ots, ote);
 		}
 	}
 	if (!keep) c.bl[i] = bl | DEAD;
@@ -514,16 +550,9 @@ __device__ __forceinline__ uint32_t sub_group_regs(const HitCols &c, uint32_t q,
 		if (i < end) {
 			uint32_t bl, ml, qs, qe, tn, es, ee;
 			int alive;
-			if (pre && h < 2) {
+			if (pre) { // (ITEMS is 2 or 4 here: SubPre's two slots per lane)
 				bl = pre->bl[h]; ml = pre->ml[h]; qs = pre->qs[h]; qe = pre->qe[h]; tn = pre->tn[h];
 				alive = !(bl & DEAD) && (!FUSE || fuse_cut_flt_v(c, i, f, q, rq, tn, qs, qe, ml, bl, acc, pre->rt[h], pre->ts[h], pre->te[h]));
-			} else if (GATHER) { // the record through the sorted key; the columns are written on the way
-				const uint32_t j = gather_pos(*g, i);
-				const uint4 *p = (const uint4*)(g->aos + j);
-				const uint4 a = p[0], b = p[1];
-				gather_store<GATHER>(c, *g, i, j, a, b);
-				bl = b.w & ~DEAD; ml = b.z; qs = a.x; qe = a.z; tn = a.w;
-				alive = 1;
 			} else {
 				bl = c.bl[i]; ml = c.ml[i]; qs = c.qs[i]; qe = c.qe[i]; tn = c.tn[i]; // independent loads
 				alive = !(bl & DEAD) && (!FUSE || fuse_cut_flt(c, i, f, q, rq, tn, qs, qe, ml, bl, acc));
@@ -604,6 +633,13 @@ __device__ __forceinline__ unsigned sub_block_id()
 #define SUB_WPE_F0 6 // the fused first tier: the compiler's own choice (82 registers, 6 waves by count but no target) 3.26 ms, target 6: 3.11, target 8 (29 spills): 3.15
 #endif
 constexpr unsigned sub_wpe(bool fuse, int cls, int gather) { return gather && cls == 0 ? SUB_WPE_G0 : fuse && cls == 1 ? 5 : fuse && cls == 0 ? SUB_WPE_F0 : 0; }
+// the fused passes' counters at the end of a block (register tiers and tier B)
+template <bool FUSE>
+__device__ __forceinline__ void sub_flush_acc(unsigned long long *ctr, const SubAcc &acc)
+{
+	if (FUSE) { blk_add_u64(&ctr[CT_CUT], acc.n_cut); blk_add_u64(&ctr[CT_LIVE], acc.n_flt); blk_add_u64(&ctr[CT_TOTDP], acc.dp); }
+}
+
 template <bool FUSE, int CLS, int GATHER = 0>
 __global__ __launch_bounds__(256) SUB_WPE_ATTR(FUSE, CLS, GATHER) void k_hit_sub(HitCols c, const uint32_t *__restrict__ goff, uint32_t n_seq,
                                                   int min_dp, float min_iden, int end_clip, uint2 *__restrict__ sub,
@@ -705,7 +741,7 @@ __global__ __launch_bounds__(256) SUB_WPE_ATTR(FUSE, CLS, GATHER) void k_hit_sub
 	}
 	}
 	blk_add_u64(&ctr[CT_REMAIN], lane == 0 ? n_kept : 0);
-	if (FUSE) { blk_add_u64(&ctr[CT_CUT], acc.n_cut); blk_add_u64(&ctr[CT_LIVE], acc.n_flt); blk_add_u64(&ctr[CT_TOTDP], acc.dp); }
+	sub_flush_acc<FUSE>(ctr, acc);
 }
 
 // sweep over sorted events held in memory (tier B): ballot prefix counts per 64-event chunk, run starts by rank
@@ -788,7 +824,7 @@ __global__ __launch_bounds__(256) void k_hit_sub_big(HitCols c, const uint32_t *
 		}
 		__syncthreads();
 	}
-	if (FUSE) { blk_add_u64(&ctr[CT_CUT], acc.n_cut); blk_add_u64(&ctr[CT_LIVE], acc.n_flt); blk_add_u64(&ctr[CT_TOTDP], acc.dp); }
+	sub_flush_acc<FUSE>(ctr, acc);
 }
 
 // ------------------------------------------------------------------------------------------------ ma_hit_cut
@@ -801,9 +837,9 @@ __global__ __launch_bounds__(256) void k_hit_cut(HitCols c, size_t n, const uint
 		if (bl & DEAD) continue;
 		int keep = 0;
 		uint2 rq = sub[c.qid[i]], rt = sub[c.tn[i]];
-		if (!(rq.x & DEAD) && !(rt.x & DEAD)) {
+		if (subs_live(rq, rt)) { // (the columns of a hit whose read lost its interval are not fetched)
 			uint32_t qs = c.qs[i], qe = c.qe[i], ts = c.ts[i], te = c.te[i];
-			keep = mc_cut(&qs, &qe, &ts, &te, c.ml[i] >> 31, (int32_t)rq.x, rq.y, (int32_t)rt.x, rt.y, min_span);
+			keep = hit_cut(rq, rt, qs, qe, ts, te, c.ml[i], min_span);
 			if (keep) c.qs[i] = qs, c.qe[i] = qe, c.ts[i] = ts, c.te[i] = te;
 		}
 		if (!keep) c.bl[i] = bl | DEAD;
@@ -813,7 +849,7 @@ __global__ __launch_bounds__(256) void k_hit_cut(HitCols c, size_t n, const uint
 }
 
 // ------------------------------------------------------------------------------------------------ ma_hit_flt
-// reference hit.c:195-216 (int_frac is the literal .5 there); r_live[q] marks query groups that keep a hit
+// reference hit.c:195-216; r_live[q] marks query groups that keep a hit
 __global__ __launch_bounds__(256) void k_hit_flt(HitCols c, size_t n, const uint2 *__restrict__ sub, int max_hang, int min_ovlp,
                                                   uint8_t *__restrict__ r_live, unsigned long long *__restrict__ ctr)
 {
@@ -825,16 +861,7 @@ __global__ __launch_bounds__(256) void k_hit_flt(HitCols c, size_t n, const uint
 		int keep = 0;
 		uint32_t q = c.qid[i], t = c.tn[i];
 		uint2 sq = sub[q], st = sub[t];
-		if (!(sq.x & DEAD) && !(st.x & DEAD)) {
-			mc_arc_t a;
-			uint32_t ql = sq.y - (sq.x & 0x7fffffffu), tl = st.y - (st.x & 0x7fffffffu);
-			int r = mc_hit2arc(q, c.qs[i], c.qe[i], t, c.ts[i], c.te[i], c.ml[i] >> 31, (int)ql, (int)tl, max_hang, .5f, min_ovlp, &a);
-			if (r >= 0 || r == MC_HT_QCONT || r == MC_HT_TCONT) {
-				keep = 1;
-				dp += r >= 0 ? (uint32_t)r : r == MC_HT_QCONT ? ql : tl;
-				r_live[q] = 1;
-			}
-		}
+		if (subs_live(sq, st)) keep = hit_flt(q, c.qs[i], c.qe[i], t, c.ts[i], c.te[i], c.ml[i], sq, st, max_hang, min_ovlp, dp, r_live);
 		if (!keep) c.bl[i] = bl | DEAD;
 		n_keep += keep;
 	}
@@ -846,7 +873,7 @@ __global__ __launch_bounds__(256) void k_flt_totlen(const uint2 *__restrict__ su
 {
 	uint64_t x = 0;
 	for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < n_seq; r += gridDim.x * 256)
-		if (r_live[r]) { uint2 s = sub[r]; x += (uint32_t)(s.y - (s.x & 0x7fffffffu)); }
+		if (r_live[r]) x += sub_len(sub[r]);
 	blk_add_u64(&ctr[CT_TOTLEN], x);
 }
 
@@ -873,12 +900,7 @@ __global__ __launch_bounds__(256) void k_hit_contained(HitCols c, size_t n, cons
 		if (c.bl[i] & DEAD) continue;
 		uint32_t q = c.qid[i], t = c.tn[i];
 		uint2 sq = sub[q], st = sub[t];
-		mc_arc_t a;
-		int r = mc_hit2arc(q, c.qs[i], c.qe[i], t, c.ts[i], c.te[i], c.ml[i] >> 31, (int)(sq.y - (sq.x & 0x7fffffffu)),
-		                   (int)(st.y - (st.x & 0x7fffffffu)), max_hang, int_frac, min_ovlp, &a);
-		if (r == MC_HT_QCONT) r_cont[q] = 1;
-		else if (r == MC_HT_TCONT) r_cont[t] = 1;
-		r_used[q] = 1; r_used[t] = 1;
+		hit_contained_flags(q, c.qs[i], c.qe[i], t, c.ts[i], c.te[i], c.ml[i], sq, st, max_hang, int_frac, min_ovlp, r_cont, r_used);
 	}
 }
 
@@ -916,18 +938,11 @@ __global__ __launch_bounds__(256) void k_hit_cut_contained(HitCols c, size_t n, 
 			if (bl[u] & DEAD) continue;
 			const uint2 rq = make_uint2(pq[u].x, pq[u].y), rt = make_uint2(pt[u].x, pt[u].y);
 			uint32_t qs_ = qs[u], qe_ = qe[u], ts_ = ts[u], te_ = te[u];
-			if (!(rq.x & DEAD) && !(rt.x & DEAD) && mc_cut(&qs_, &qe_, &ts_, &te_, ml[u] >> 31, (int32_t)rq.x, rq.y, (int32_t)rt.x, rt.y, min_span)) {
+			if (hit_cut(rq, rt, qs_, qe_, ts_, te_, ml[u], min_span)) {
 				const uint2 sq = make_uint2(pq[u].z, pq[u].w), st = make_uint2(pt[u].z, pt[u].w);
-				mc_arc_t a;
-				if (qs_ != qs[u]) c.qs[i] = qs_; // most hits lie inside both intervals: untouched columns are not written back
-				if (qe_ != qe[u]) c.qe[i] = qe_;
-				if (ts_ != ts[u]) c.ts[i] = ts_;
-				if (te_ != te[u]) c.te[i] = te_;
+				store_cut_cols(c, i, qs_, qe_, ts_, te_, qs[u], qe[u], ts[u], te[u]);
 				++n_keep;
-				int r = mc_hit2arc(q[u], qs_, qe_, t[u], ts_, te_, ml[u] >> 31, (int)(sq.y - (sq.x & 0x7fffffffu)), (int)(st.y - (st.x & 0x7fffffffu)), max_hang, int_frac, min_ovlp, &a);
-				if (r == MC_HT_QCONT) r_cont[q[u]] = 1;
-				else if (r == MC_HT_TCONT) r_cont[t[u]] = 1;
-				r_used[q[u]] = 1; r_used[t[u]] = 1;
+				hit_contained_flags(q[u], qs_, qe_, t[u], ts_, te_, ml[u], sq, st, max_hang, int_frac, min_ovlp, r_cont, r_used);
 			} else c.bl[i] = bl[u] | DEAD;
 		}
 	}
@@ -1111,6 +1126,17 @@ __global__ __launch_bounds__(256) void k_qid_count(const ma_hit_t *__restrict__ 
 		if (q < n_seq) atomicAdd(&cnt[q], 1u);
 	}
 }
+// b[1 .. world - 1] from the hits of every read (cnt, n_hits in all): rank r starts at the first read behind which r/world of the hits lie (b[0] = 0 and b[world] = the
+// number of reads, like every entry no rank reaches, are the caller's)
+static void balanced_bounds(const std::vector<uint32_t> &cnt, unsigned long long n_hits, int world, std::vector<uint32_t> &b)
+{
+	unsigned long long run = 0;
+	int r = 1;
+	for (uint32_t q = 0; q < cnt.size() && r < world; ++q) {
+		run += cnt[q];
+		while (r < world && run * (unsigned long long)world >= n_hits * (unsigned long long)r) b[r++] = q + 1;
+	}
+}
 // bounds[0..world]: rank r owns the reads [bounds[r], bounds[r+1]); computed from the unsorted records in the context (every rank that holds the whole
 // input computes the same table).  The table is kept in the context (mahip_shard_bounds) for the orchestrator.
 extern "C" int mahip_hits_balance(mahip_ctx_t *c, int world, uint32_t *bounds)
@@ -1128,12 +1154,7 @@ extern "C" int mahip_hits_balance(mahip_ctx_t *c, int world, uint32_t *bounds)
 		std::vector<uint32_t> cnt(R);
 		HIPCHK(hipMemcpyAsync(cnt.data(), c->keep.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->st));
 		HIPCHK(hipStreamSynchronize(c->st));
-		unsigned long long run = 0;
-		int r = 1;
-		for (uint32_t q = 0; q < R && r < world; ++q) { // rank r starts at the first read behind which r/world of the hits lie
-			run += cnt[q];
-			while (r < world && run * (unsigned long long)world >= (unsigned long long)n * (unsigned long long)r) b[r++] = q + 1;
-		}
+		balanced_bounds(cnt, n, world, b);
 	} else if (world > 1) { // nothing to weigh: equal read counts
 		const uint32_t per = (uint32_t)(((uint64_t)R + world - 1) / world);
 		for (int r = 1; r < world; ++r) b[r] = (uint64_t)r * per < R ? (uint32_t)((uint64_t)r * per) : R;
@@ -1185,12 +1206,7 @@ extern "C" int mahip_hits_route(mahip_ctx_t *c, uint64_t *n_total_out, uint64_t 
 		if (hipMemcpyAsync(cnt.data(), c->keep.p, (size_t)R * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) {
 			mahip_set_error("mahip_hits_route: the summed hit counts did not come down"); lrc_pre = -1; // (the marker in the row gathered below tells the others)
 		}
-		unsigned long long run = 0;
-		int r = 1;
-		for (uint32_t q = 0; q < R && r < W && lrc_pre == 0; ++q) { // as mahip_hits_balance: rank r starts behind the read that completes r/W of the hits
-			run += cnt[q];
-			while (r < W && run * (unsigned long long)W >= (unsigned long long)total * (unsigned long long)r) b[r++] = q + 1;
-		}
+		if (lrc_pre == 0) balanced_bounds(cnt, total, W, b);
 	}
 	// (2) my records by destination, each with its position in the whole input
 	DevBuf send_rec, send_pos, recv_rec, recv_pos;
@@ -1709,7 +1725,7 @@ extern "C" int mahip_hits_index(mahip_ctx_t *c)
 struct SubFork {
 	mahip_ctx *c; bool on;
 	hipStream_t side[2]; hipEvent_t start, done[2];
-	SubFork(mahip_ctx *c_) : c(c_), on(true) {
+	SubFork(mahip_ctx *c_, bool want) : c(c_), on(want) { // !want: all three classes on the context's stream
 		if (!on) return;
 		if (!c->sub_side[0] && !c->sub_fork_failed) { // streams and events are made once per context; if any of them cannot be had, all three size classes run on the context's stream
 			bool ok = true;
@@ -1732,56 +1748,68 @@ struct SubFork {
 	void join() { if (!on) return; for (int k = 0; k < 2; ++k) { (void)hipEventRecord(done[k], side[k]); (void)hipStreamWaitEvent(c->st, done[k], 0); } }
 };
 
+// the three size classes of one form of the register tier, every class on the same grid
+template <bool FUSE, int GATHER>
+static void sub_launch_classes(const SubFork &fk, dim3 grd, HitCols h, const uint32_t *goff, uint32_t q_hi, int min_dp, float min_iden, int end_clip, uint2 *sub,
+                               uint32_t *ovf, unsigned long long *ctr, const SubFuse &f, const SubGather &g)
+{
+	hipLaunchKernelGGL((k_hit_sub<FUSE, 0, GATHER>), grd, dim3(256), 0, fk.st(0), h, goff, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+	hipLaunchKernelGGL((k_hit_sub<FUSE, 1, GATHER>), grd, dim3(256), 0, fk.st(1), h, goff, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+	hipLaunchKernelGGL((k_hit_sub<FUSE, 2, GATHER>), grd, dim3(256), 0, fk.st(2), h, goff, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+}
+// One coverage pass over the context's reads (n_seq > 0): the register tier under the scope `name`, then tier B.  fuse: cut + filter on the way (else null);
+// gather: where the records' positions stand (else null: the columns are there) -- with a sidx to write they come from the sorted keys (k_hit_sub's gather
+// mode 1), without one they are sidx itself (mode 2: hits sorted as runs); chunk and q_lo are filled in here.  fork: the size classes side by side (SubFork).
+static int sub_pass(mahip_ctx *c, const char *name, double alg_bytes, const SubFuse *fuse, const SubGather *gather, bool fork, int min_dp, float min_iden, int end_clip, uint2 *sub)
+{
+	const uint32_t q_lo = shard_lo(c), q_hi = shard_hi(c), Rr = q_hi > q_lo ? q_hi - q_lo : 1; // a shard sweeps its own reads only (everybody else's have no hits here)
+	const HitCols h = cols_of(c);
+	const uint32_t *gf = (const uint32_t*)P<uint32_t>(c->goff);
+	unsigned long long *ctr = P<unsigned long long>(c->ctr);
+	const SubFuse f = fuse ? *fuse : SubFuse{nullptr, 0, 0, 0, nullptr};
+	SubGather g = gather ? *gather : SubGather{nullptr, 0, 0, nullptr, nullptr, 0, 0, 0};
+	g.chunk = sub_chunk(Rr); g.q_lo = q_lo;
+	CHK(dev_reserve(c, c->ovf, ((size_t)c->n_seq + 1) * 4));
+	uint32_t *ovf = P<uint32_t>(c->ovf);
+	{
+		ProfScope ps(c, name, alg_bytes);
+		SubFork fk(c, fork);
+		const dim3 grd(grid_for(Rr, 4, SUB_BLOCKS));
+		if (fuse) sub_launch_classes<true, 0>(fk, grd, h, gf, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+		else if (!gather) sub_launch_classes<false, 0>(fk, grd, h, gf, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+		else if (g.sidx) sub_launch_classes<false, 1>(fk, grd, h, gf, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g);
+		else sub_launch_classes<false, 2>(fk, grd, h, gf, q_hi, min_dp, min_iden, end_clip, sub, ovf, ctr, f, g); // (sidx is not written again)
+		fk.join();
+	}
+	// tier B always runs behind the register tiers on a small grid: it finds its work list (usually empty) in the device counter
+	CHK(dev_reserve(c, c->big0, (2 * c->n_hits + 8) * 4));
+	CHK(dev_reserve(c, c->big1, (c->n_hits + 8) * 4));
+	ProfScope ps(c, "k_hit_sub_big", 0);
+	if (fuse) hipLaunchKernelGGL(k_hit_sub_big<true>, dim3(256), dim3(256), 0, c->st, h, gf, (const uint32_t*)ovf, (const unsigned long long*)(ctr + CT_OVF),
+	                             min_dp, min_iden, end_clip, sub, P<uint32_t>(c->big0), P<uint32_t>(c->big1), ctr, f);
+	else hipLaunchKernelGGL(k_hit_sub_big<false>, dim3(256), dim3(256), 0, c->st, h, gf, (const uint32_t*)ovf, (const unsigned long long*)(ctr + CT_OVF),
+	                        min_dp, min_iden, end_clip, sub, P<uint32_t>(c->big0), P<uint32_t>(c->big1), ctr, f);
+	return 0;
+}
+
 extern "C" int mahip_hits_sub(mahip_ctx_t *c, int min_dp, float min_iden, int end_clip, int slot, size_t *n_remained)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	if (!c->soa_ready) { mahip_set_error("mahip_hits_sub: hits not indexed"); return -1; }
-	HitCols h = cols_of(c);
-	uint32_t R = c->n_seq;
-	const uint32_t q_lo = shard_lo(c), q_hi = shard_hi(c), Rr = q_hi > q_lo ? q_hi - q_lo : 1; // a shard sweeps its own reads only (everybody else's have no hits here)
+	const uint32_t R = c->n_seq;
 	CHK(ctr_zero(c));
-	CHK(dev_reserve(c, c->ovf, ((size_t)R + 1) * 4));
-	unsigned long long *ctr = P<unsigned long long>(c->ctr);
 	uint2 *sub = P<uint2>(c->sub[slot]);
-	SubFuse nofuse = {nullptr, 0, 0, 0, nullptr};
-	SubGather nog = {nullptr, 0, 0, nullptr, nullptr, 0, sub_chunk(Rr), q_lo};
 	const bool fuse_gather = c->gather_pending && R && c->n_hits;
 	if (c->gather_pending && !fuse_gather) CHK(hits_need_cols(c, "mahip_hits_sub"));
 	if (fuse_gather) { // the sweep fetches the records itself and writes the columns on the way
 		const uint32_t pmask = c->gk_bi >= 32 ? 0xffffffffu : (1u << c->gk_bi) - 1u;
-		const SubGather g = c->gk_runs ? SubGather{(const uint32_t*)P<uint32_t>(c->sidx), 1u, 0xffffffffu, c->d_aos, nullptr, (uint32_t)c->n_hits, sub_chunk(Rr), q_lo}
-		                               : SubGather{(const uint32_t*)P<uint64_t>(c->key[c->gk_gen]), 2u, pmask, c->d_aos, P<uint32_t>(c->sidx), (uint32_t)c->n_hits, sub_chunk(Rr), q_lo};
-		ProfScope ps(c, "k_hit_sub<gather>", (64.0 + 48.0) * (double)c->n_hits); // hit sort 64 (32 r + 32 w, counted once whatever the digit passes) + ma_hit_sub 48 B per stored hit
-		SubFork fk(c);
-		const dim3 grd(grid_for(Rr, 4, SUB_BLOCKS)), blk(256);
-		const uint32_t *gf = (const uint32_t*)P<uint32_t>(c->goff);
-		if (c->gk_runs) { // positions from sidx (k_runs_expand), which is not written again
-			hipLaunchKernelGGL((k_hit_sub<false, 0, 2>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			hipLaunchKernelGGL((k_hit_sub<false, 1, 2>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			hipLaunchKernelGGL((k_hit_sub<false, 2, 2>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-		} else {
-			hipLaunchKernelGGL((k_hit_sub<false, 0, 1>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			hipLaunchKernelGGL((k_hit_sub<false, 1, 1>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-			hipLaunchKernelGGL((k_hit_sub<false, 2, 1>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, nofuse, g);
-		}
-		fk.join();
+		const SubGather g = c->gk_runs ? SubGather{(const uint32_t*)P<uint32_t>(c->sidx), 1u, 0xffffffffu, c->d_aos, nullptr, (uint32_t)c->n_hits, 0, 0} // positions from sidx (k_runs_expand)
+		                               : SubGather{(const uint32_t*)P<uint64_t>(c->key[c->gk_gen]), 2u, pmask, c->d_aos, P<uint32_t>(c->sidx), (uint32_t)c->n_hits, 0, 0};
+		// hit sort 64 (32 r + 32 w, counted once whatever the digit passes) + ma_hit_sub 48 B per stored hit
+		CHK(sub_pass(c, "k_hit_sub<gather>", (64.0 + 48.0) * (double)c->n_hits, nullptr, &g, true, min_dp, min_iden, end_clip, sub));
 		c->gather_pending = false;
-	} else if (R) {
-		ProfScope ps(c, "k_hit_sub", 48.0 * (double)c->n_hits + 8.0 * R); // 32 r + 8 w events + 8 r events per stored hit
-		hipLaunchKernelGGL((k_hit_sub<false, 0>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
-		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
-		hipLaunchKernelGGL((k_hit_sub<false, 1>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
-		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
-		hipLaunchKernelGGL((k_hit_sub<false, 2>), dim3(grid_for(Rr, 4, SUB_BLOCKS)), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), q_hi, min_dp, min_iden, end_clip,
-		                   sub, P<uint32_t>(c->ovf), ctr, nofuse, nog);
-	}
-	if (R) { // tier B always runs behind the register tiers on a small grid: it finds its work list (usually empty) in the device counter
-		CHK(dev_reserve(c, c->big0, (2 * c->n_hits + 8) * 4));
-		CHK(dev_reserve(c, c->big1, (c->n_hits + 8) * 4));
-		ProfScope ps(c, "k_hit_sub_big", 0);
-		hipLaunchKernelGGL(k_hit_sub_big<false>, dim3(256), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), (const uint32_t*)P<uint32_t>(c->ovf), (const unsigned long long*)(ctr + CT_OVF),
-		                   min_dp, min_iden, end_clip, sub, P<uint32_t>(c->big0), P<uint32_t>(c->big1), ctr, nofuse);
-	}
+	} else if (R) // 32 r + 8 w events + 8 r events per stored hit
+		CHK(sub_pass(c, "k_hit_sub", 48.0 * (double)c->n_hits + 8.0 * R, nullptr, nullptr, false, min_dp, min_iden, end_clip, sub));
 	CHK(ctr_fetch(c));
 	HIPCHK(hipGetLastError());
 	if (n_remained) *n_remained = (size_t)c->h_ctr[CT_REMAIN];
@@ -1794,34 +1822,14 @@ extern "C" int mahip_hits_cutflt_sub(mahip_ctx_t *c, int cut_slot, int min_span,
 {
 	HIPCHK(hipSetDevice(c->dev));
 	CHK(hits_need_cols(c, "mahip_hits_cutflt_sub"));
-	HitCols h = cols_of(c);
-	uint32_t R = c->n_seq;
-	const uint32_t q_lo = shard_lo(c), q_hi = shard_hi(c), Rr = q_hi > q_lo ? q_hi - q_lo : 1;
+	const uint32_t R = c->n_seq;
 	CHK(ctr_zero(c));
-	CHK(dev_reserve(c, c->ovf, ((size_t)R + 1) * 4));
 	HIPCHK(hipMemsetAsync(c->r_live.p, 0, R, c->st));
-	unsigned long long *ctr = P<unsigned long long>(c->ctr);
-	uint2 *sub = P<uint2>(c->sub[out_slot]);
-	SubFuse f = {(const uint2*)P<uint2>(c->sub[cut_slot]), min_span, max_hang, min_ovlp, P<uint8_t>(c->r_live)};
-	if (R) {
-		ProfScope ps(c, "k_hit_sub<cut+flt>", (80.0 + 80.0 + 48.0) * (double)c->n_hits + 8.0 * R); // cut 80 + flt 80 + sub 48 B per hit
-		SubFork fk(c);
-		const dim3 grd(grid_for(Rr, 4, SUB_BLOCKS)), blk(256);
-		const uint32_t *gf = (const uint32_t*)P<uint32_t>(c->goff);
-		const SubGather nog2 = SubGather{nullptr, 0, 0, nullptr, nullptr, 0, sub_chunk(Rr), q_lo};
-		hipLaunchKernelGGL((k_hit_sub<true, 0>), grd, blk, 0, fk.st(0), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-		hipLaunchKernelGGL((k_hit_sub<true, 1>), grd, blk, 0, fk.st(1), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-		hipLaunchKernelGGL((k_hit_sub<true, 2>), grd, blk, 0, fk.st(2), h, gf, q_hi, min_dp, min_iden, end_clip, sub, P<uint32_t>(c->ovf), ctr, f, nog2);
-		fk.join();
+	const SubFuse f = {(const uint2*)P<uint2>(c->sub[cut_slot]), min_span, max_hang, min_ovlp, P<uint8_t>(c->r_live)};
+	if (R) { // cut 80 + flt 80 + sub 48 B per hit
+		CHK(sub_pass(c, "k_hit_sub<cut+flt>", (80.0 + 80.0 + 48.0) * (double)c->n_hits + 8.0 * R, &f, nullptr, true, min_dp, min_iden, end_clip, P<uint2>(c->sub[out_slot])));
+		hipLaunchKernelGGL(k_flt_totlen, dim3(grid_for(R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, f.cut_sub, (const uint8_t*)P<uint8_t>(c->r_live), R, P<unsigned long long>(c->ctr));
 	}
-	if (R) {
-		CHK(dev_reserve(c, c->big0, (2 * c->n_hits + 8) * 4));
-		CHK(dev_reserve(c, c->big1, (c->n_hits + 8) * 4));
-		ProfScope ps(c, "k_hit_sub_big", 0);
-		hipLaunchKernelGGL(k_hit_sub_big<true>, dim3(256), dim3(256), 0, c->st, h, (const uint32_t*)P<uint32_t>(c->goff), (const uint32_t*)P<uint32_t>(c->ovf), (const unsigned long long*)(ctr + CT_OVF),
-		                   min_dp, min_iden, end_clip, sub, P<uint32_t>(c->big0), P<uint32_t>(c->big1), ctr, f);
-	}
-	if (R) hipLaunchKernelGGL(k_flt_totlen, dim3(grid_for(R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, f.cut_sub, (const uint8_t*)P<uint8_t>(c->r_live), R, ctr);
 	CHK(ctr_fetch(c));
 	HIPCHK(hipGetLastError());
 	c->n_live = (size_t)c->h_ctr[CT_LIVE];
@@ -1856,20 +1864,26 @@ extern "C" int mahip_hits_cut_contained_flags(mahip_ctx_t *c, int cut_slot, int 
 	return 0;
 }
 
+// Pass 2 of ma_hit_contained (both finishers): per-read delete flags from the intervals, the flag arrays and what r_del holds on entry (the caller's seq[].del, or
+// zeroes), then the squeeze map and its inverse; the number of surviving reads is left in CT_TOTAL
+static int reads_squeeze_map(mahip_ctx *c)
+{
+	const uint32_t R = c->n_seq;
+	CHK(dev_reserve(c, c->keep, ((size_t)R + 16) * 4));
+	if (R == 0) return 0;
+	hipLaunchKernelGGL(k_read_del, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint2*)P<uint2>(c->sub[0]), (const uint8_t*)P<uint8_t>(c->r_cont),
+	                   (const uint8_t*)P<uint8_t>(c->r_used), P<uint8_t>(c->r_del), P<uint32_t>(c->keep), R);
+	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), (uint32_t*)c->map.p, R, (uint32_t*)(P<unsigned long long>(c->ctr) + CT_TOTAL)));
+	hipLaunchKernelGGL(k_map_fix, dim3(grid_for(R, 256)), dim3(256), 0, c->st, P<int32_t>(c->map), (const uint8_t*)P<uint8_t>(c->r_del), R, P<uint32_t>(c->surv));
+	return 0;
+}
+
 extern "C" int mahip_hits_cut_contained_finish(mahip_ctx_t *c, size_t *n_cut, uint32_t *n_seq_new)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	uint32_t R = c->n_seq;
-	CHK(dev_reserve(c, c->keep, ((size_t)R + 16) * 4));
 	HIPCHK(hipMemsetAsync(c->r_del.p, 0, R, c->st));
-	unsigned long long *ctr = P<unsigned long long>(c->ctr);
-	uint32_t *d_tot = (uint32_t*)(ctr + CT_TOTAL);
-	if (R) {
-		hipLaunchKernelGGL(k_read_del, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint2*)P<uint2>(c->sub[0]), (const uint8_t*)P<uint8_t>(c->r_cont),
-		                   (const uint8_t*)P<uint8_t>(c->r_used), P<uint8_t>(c->r_del), P<uint32_t>(c->keep), R);
-		CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), (uint32_t*)c->map.p, R, d_tot));
-		hipLaunchKernelGGL(k_map_fix, dim3(grid_for(R, 256)), dim3(256), 0, c->st, P<int32_t>(c->map), (const uint8_t*)P<uint8_t>(c->r_del), R, P<uint32_t>(c->surv));
-	}
+	CHK(reads_squeeze_map(c));
 	CHK(ctr_fetch(c));
 	HIPCHK(hipGetLastError());
 	c->n_live = (size_t)c->h_ctr[CT_LIVE];
@@ -1959,16 +1973,9 @@ extern "C" int mahip_hits_contained_finish(mahip_ctx_t *c, const uint8_t *seq_de
 	size_t n = c->n_hits;
 	uint32_t R = c->n_seq;
 	CHK(ctr_zero(c));
-	CHK(dev_reserve(c, c->keep, ((size_t)R + 16) * 4));
 	if (seq_del) HIPCHK(hipMemcpyAsync(c->r_del.p, seq_del, R, hipMemcpyHostToDevice, c->st));
 	else HIPCHK(hipMemsetAsync(c->r_del.p, 0, R, c->st));
-	uint32_t *d_tot = (uint32_t*)(P<unsigned long long>(c->ctr) + CT_TOTAL);
-	if (R) {
-		hipLaunchKernelGGL(k_read_del, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint2*)P<uint2>(c->sub[0]), (const uint8_t*)P<uint8_t>(c->r_cont),
-		                   (const uint8_t*)P<uint8_t>(c->r_used), P<uint8_t>(c->r_del), P<uint32_t>(c->keep), R);
-		CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), (uint32_t*)c->map.p, R, d_tot));
-		hipLaunchKernelGGL(k_map_fix, dim3(grid_for(R, 256)), dim3(256), 0, c->st, P<int32_t>(c->map), (const uint8_t*)P<uint8_t>(c->r_del), R, P<uint32_t>(c->surv));
-	}
+	CHK(reads_squeeze_map(c));
 	if (n) {
 		ProfScope ps(c, "k_hit_squeeze", 72.0 * (double)c->n_live);
 		hipLaunchKernelGGL(k_hit_squeeze, dim3(grid_for(n, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, cols_of(c), n, (const uint8_t*)P<uint8_t>(c->r_del), P<unsigned long long>(c->ctr));
