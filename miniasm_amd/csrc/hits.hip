@@ -2014,7 +2014,7 @@ extern "C" int mahip_copy_out(mahip_ctx_t *c, int which, void *d_dst, size_t fir
 	HIPCHK(hipSetDevice(c->dev));
 	size_t es;
 	DevBuf *b = xbuf(c, which, &es);
-	if (!b || (first + count) * es > b->cap) { mahip_set_error("mahip_copy_out: bad buffer/range"); return -1; }
+	if (!b || first + count > c->n_seq || (first + count) * es > b->cap) { mahip_set_error("mahip_copy_out: bad buffer/range"); return -1; } // (the arrays hold n_seq entries; their buffers are padded)
 	if (count) HIPCHK(hipMemcpyAsync(d_dst, (char*)b->p + first * es, count * es, hipMemcpyDeviceToDevice, c->st));
 	if (xchg_needs_sync(c)) HIPCHK(hipStreamSynchronize(c->st)); // the exchange runs on somebody else's stream (mahip_internal.hpp)
 	return 0;
@@ -2025,7 +2025,7 @@ extern "C" int mahip_copy_in(mahip_ctx_t *c, int which, const void *d_src, size_
 	HIPCHK(hipSetDevice(c->dev));
 	size_t es;
 	DevBuf *b = xbuf(c, which, &es);
-	if (!b || (first + count) * es > b->cap) { mahip_set_error("mahip_copy_in: bad buffer/range"); return -1; }
+	if (!b || first + count > c->n_seq || (first + count) * es > b->cap) { mahip_set_error("mahip_copy_in: bad buffer/range"); return -1; } // (the arrays hold n_seq entries; their buffers are padded)
 	if (count) HIPCHK(hipMemcpyAsync((char*)b->p + first * es, d_src, count * es, hipMemcpyDeviceToDevice, c->st));
 	if (xchg_needs_sync(c)) HIPCHK(hipStreamSynchronize(c->st)); // the exchange runs on somebody else's stream (mahip_internal.hpp)
 	return 0;

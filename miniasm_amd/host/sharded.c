@@ -149,6 +149,12 @@ int ma_pipeline_head_sharded(mahip_ctx_t *c, const ma_opt_t *opt, uint32_t n_seq
 		mahip_tie_info_t ti;
 		mahip_tie_stats(c, &ti);
 		st->tie_groups = ti.arc_tie_groups;
+		/* A table may give ONE rank every read ([0, n, n]: all hits on the last read).  That rank's context is no shard ((q_beg, q_end) == (0, n_seq)): its ma_sg_gen
+		 * took the census and walked by itself and kept no push rows, yet the census behind the import above says `unrepaired` on every rank.  The repair below
+		 * then gathers ZERO push rows and walks over what exchange buffer 0 still holds: the rows of the exchange above, the owner's graph in the order its own walk
+		 * left.  That is safe: those rows are sorted by (u,len), and on a sequence sorted by its keys the reference's sort moves nothing (every record stands in
+		 * its radix bucket already, the insertion sort of the small buckets is stable) -- every rank ends with the owner's graph again.  Nothing may write to
+		 * exchange buffer 0 between the two exchanges.  tests/test_gpu_shard_edges.py: test_one_rank_owns_every_read holds both facts. */
 		if (ti.unrepaired) {
 			uint64_t conf = 0, two[2];
 			GPU(mahip_sg_push_conflicts(c, &conf));

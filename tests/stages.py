@@ -1328,3 +1328,424 @@ def sort_model(qid, stride, n_seq):
     plan = digit_plan(lo, bq)
     M["shift"], M["bits"] = [p[0] for p in plan], [p[1] for p in plan]
     return M
+
+
+# --------------------------------------------------------------------------------------------- the sharded head in one process (tests/test_gpu_shard_edges.py)
+ROW_DT = np.dtype([("u", "<u4"), ("v", "<u4"), ("len", "<u4"), ("oldel", "<u4")])  # include/mahip.h: the packed rows of mahip_asg_export_rows
+BUF_SUB0, BUF_SUB1, BUF_RCONT, BUF_RUSED, BUF_SDEL = range(5)  # MAHIP_BUF_*
+
+
+def shard_api():
+    """the C ABI building blocks of the sharded mode (include/mahip.h) that the thin harness does not wrap"""
+    L = graph_api()
+    vp, sz, u32, i32, u64 = C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_uint64
+    L.mahip_set_shard.argtypes = [vp, u32, u32]
+    L.mahip_set_full_input.argtypes = [vp, i32]
+    L.mahip_set_shard_bounds.argtypes = [vp, vp, i32]
+    L.mahip_shard_bounds.restype = C.POINTER(u32)
+    L.mahip_shard_bounds.argtypes = [vp, C.POINTER(i32)]
+    L.mahip_hits_balance.argtypes = [vp, i32, vp]
+    L.mahip_hits_set_positions.argtypes = [vp, vp, i32, u64]
+    L.mahip_hits_have_positions.argtypes = [vp]
+    L.mahip_xbuf.argtypes = [vp, i32, sz, C.POINTER(vp)]
+    L.mahip_copy_out.argtypes = [vp, i32, vp, sz, sz]
+    L.mahip_copy_in.argtypes = [vp, i32, vp, sz, sz]
+    L.mahip_hits_cut_contained_flags.argtypes = [vp, i32, i32, C.POINTER(ma.MaOpt)]
+    L.mahip_hits_cut_contained_finish.argtypes = [vp, C.POINTER(sz), C.POINTER(u32)]
+    L.mahip_sg_flags.argtypes = [vp, C.POINTER(ma.MaOpt), i32, vp, vp]
+    L.mahip_sg_finish.argtypes = [vp, C.POINTER(u32)]
+    L.mahip_asg_export_rows.argtypes = [vp, vp]
+    L.mahip_asg_import_rows.argtypes = [vp, vp, vp, i32, sz]
+    L.mahip_sg_push_conflicts.argtypes = [vp, C.POINTER(u64)]
+    L.mahip_sg_push_fix.argtypes = [vp]
+    L.mahip_asg_export_rows_push.argtypes = [vp, vp]
+    L.mahip_asg_import_push_rows.argtypes = [vp, vp, vp, i32, sz]
+    L.mahip_asg_flags_out.argtypes = [vp, vp, sz, sz]
+    L.mahip_asg_flags_in.argtypes = [vp, vp, sz, sz]
+    return L
+
+
+def shard_phase_names():
+    """host/sharded.c: ma_shard_phase_name[], read from the library"""
+    return [s.decode() for s in (C.c_char_p * ma.SHARD_N_PHASES).in_dll(ma.lib(), "ma_shard_phase_name")]
+
+
+def xbuf(ctx, slot, nbytes):
+    p = C.c_void_p(0)
+    ma._chk(shard_api().mahip_xbuf(ctx.h, slot, nbytes, C.byref(p)), "xbuf")
+    return p.value
+
+
+def dev_read(ctx, dptr, nbytes):
+    """mahip_memcpy_d2h -> bytes as a u8 array"""
+    out = np.zeros(max(nbytes, 1), dtype=np.uint8)
+    if nbytes:
+        ma._chk(ma.lib().mahip_memcpy_d2h(ctx.h, out.ctypes.data, dptr, nbytes), "memcpy_d2h")
+    return out[:nbytes]
+
+
+def dev_write(ctx, dptr, arr):
+    a = np.ascontiguousarray(arr).view(np.uint8).reshape(-1)
+    if len(a):
+        ma._chk(ma.lib().mahip_memcpy_h2d(ctx.h, dptr, a.ctypes.data, len(a)), "memcpy_h2d")
+
+
+BUF_ELEM = {BUF_SUB0: SUB_DT, BUF_SUB1: SUB_DT, BUF_RCONT: np.dtype(np.uint8), BUF_RUSED: np.dtype(np.uint8), BUF_SDEL: np.dtype(np.uint8)}
+
+
+def buf_get(ctx, which, first, count):
+    """elements [first, first + count) of one of the read-indexed arrays: mahip_copy_out into exchange buffer 1, then down (buffer 0 is left alone: the
+    orchestrator's send side, whose contents between two exchanges are part of what the stage tests look at)"""
+    dt = BUF_ELEM[which]
+    p = xbuf(ctx, 1, count * dt.itemsize)
+    ma._chk(shard_api().mahip_copy_out(ctx.h, which, p, first, count), "copy_out")
+    return dev_read(ctx, p, count * dt.itemsize).view(dt).copy()
+
+
+def shard_range(ctx, n_seq, world, rank):
+    """host/sharded.c shard_range: the context's table when it has one for this world size and dictionary, else equal read counts
+    -> (per, q0, q1, bounds or None)"""
+    bw = C.c_int(0)
+    p = shard_api().mahip_shard_bounds(ctx.h, C.byref(bw))
+    if p and bw.value == world and p[world] == n_seq:
+        b = [int(p[r]) for r in range(world + 1)]
+        return max([1] + [b[r + 1] - b[r] for r in range(world)]), b[rank], b[rank + 1], b
+    cc = (n_seq + world - 1) // world if world > 0 else n_seq
+    return cc, min(rank * cc, n_seq), min(rank * cc + cc, n_seq), None
+
+
+def rows_to_arcs(rows, mp=None):
+    """packed rows (ids of the dictionary before the squeeze) -> asg_arc_t records, renumbered by the squeeze map when given"""
+    u, v = rows["u"].astype(np.int64), rows["v"].astype(np.int64)
+    if mp is not None and len(rows):
+        u, v = mp[u >> 1].astype(np.int64) << 1 | (u & 1), mp[v >> 1].astype(np.int64) << 1 | (v & 1)
+    a = np.zeros(len(rows), dtype=ARC_DT)
+    a["ul"], a["v"], a["oldel"] = u.astype(np.uint64) << np.uint64(32) | rows["len"].astype(np.uint64), v, rows["oldel"]
+    return a
+
+
+def sharded_stages(ctxs, hits, n_seq, opt, bounds, full_input, tie_mode, positions=None, stride=None):
+    """ma_pipeline_head_sharded (host/sharded.c) walked on len(bounds) - 1 contexts in ONE process, rank after rank, phase by phase: every ABI call with the
+    arguments sharded.c derives, every exchange done here -- mahip_xbuf + mahip_copy_out / export, mahip_memcpy_d2h, the combine in numpy (rank-major gather
+    with the slot of the longest range, element-wise max, sums), mahip_memcpy_h2d, mahip_copy_in / import.  A test model of the ORDER, not a second orchestrator:
+    the phases carry the names of ma_shard_phase_name[] (read from the library; S["order"] is what was walked).
+    bounds: the table of read ranges (installed with mahip_set_shard_bounds after the upload), or an int = the world size with NO table (equal read counts).
+    full_input 0: every context is uploaded only the records whose query lies in its range, in input order; positions (True): and told where they stood.
+    -> S[phase] = dict(contrib = what every rank contributed, held = what every rank held afterwards, ...)"""
+    L = shard_api()
+    names = shard_phase_names()
+    table = not isinstance(bounds, (int, np.integer))
+    W = len(bounds) - 1 if table else int(bounds)
+    assert 1 <= W <= len(ctxs)
+    ctxs = list(ctxs[:W])
+    active = W > 1
+    hits = np.ascontiguousarray(hits, dtype=HIT_DT)
+    qid = (hits["qns"] >> np.uint64(32)).astype(np.int64)
+    S = {"order": [], "world": W}
+
+    def phase(name):
+        assert name in names, "host/sharded.c has no phase %r" % name
+        S["order"].append(name)
+        S[name] = {}
+        return S[name]
+
+    def each(f):
+        return [f(r, c) for r, c in enumerate(ctxs)]
+
+    def x_slices(which):  # exchange_slices
+        es = BUF_ELEM[which].itemsize
+        loc = []
+        for r, c in enumerate(ctxs):
+            p = xbuf(c, 0, per * es)
+            xbuf(c, 1, per * es * W)
+            ma._chk(L.mahip_copy_out(c.h, which, p, rng[r][0], rng[r][1] - rng[r][0]), "copy_out")
+            loc.append(dev_read(c, p, per * es))
+        gathered = np.concatenate(loc)
+        for c in ctxs:
+            p = xbuf(c, 1, per * es * W)
+            dev_write(c, p, gathered)
+            if tab is None:
+                ma._chk(L.mahip_copy_in(c.h, which, p, 0, n_seq), "copy_in")
+            else:
+                for r in range(W):
+                    ma._chk(L.mahip_copy_in(c.h, which, p + r * per * es, tab[r], tab[r + 1] - tab[r]), "copy_in")
+        return [loc[r][:(rng[r][1] - rng[r][0]) * es].view(BUF_ELEM[which]).copy() for r in range(W)]
+
+    def x_flags(which):  # exchange_flags
+        nw = len(which)
+        loc = []
+        for c in ctxs:
+            p = xbuf(c, 0, n_seq * nw)
+            for k, w in enumerate(which):
+                ma._chk(L.mahip_copy_out(c.h, w, p + k * n_seq, 0, n_seq), "copy_out")
+            loc.append(dev_read(c, p, n_seq * nw))
+        red = np.maximum.reduce(loc) if loc else np.zeros(0, np.uint8)
+        for c in ctxs:
+            p = xbuf(c, 0, n_seq * nw)
+            dev_write(c, p, red)
+            for k, w in enumerate(which):
+                ma._chk(L.mahip_copy_in(c.h, w, p + k * n_seq, 0, n_seq), "copy_in")
+        return [[l[k * n_seq:(k + 1) * n_seq].copy() for k in range(nw)] for l in loc]
+
+    def x_rows(export, imp):  # the arc blocks, padded to the largest: export -> all-gather -> import
+        loc = []
+        for c in ctxs:
+            p = xbuf(c, 0, stride_a * 16)
+            xbuf(c, 1, stride_a * 16 * W)
+            ma._chk(export(c.h, p), "export rows")
+            loc.append(dev_read(c, p, stride_a * 16))
+        gathered = np.concatenate(loc)
+        for c in ctxs:
+            p = xbuf(c, 1, stride_a * 16 * W)
+            dev_write(c, p, gathered)
+            ma._chk(imp(c.h, p, counts.ctypes.data, W, stride_a), "import rows")
+        return [loc[r][:int(counts[r]) * 16].view(ROW_DT).copy() for r in range(W)]
+
+    try:
+        for r, c in enumerate(ctxs):
+            c.set_exact_ties(tie_mode)
+            if full_input or not active:
+                own = hits
+            else:  # (before the upload: the rank's range by sharded.c's rule, stated here)
+                cc = (n_seq + W - 1) // W
+                lo, hi = (int(bounds[r]), int(bounds[r + 1])) if table else (min(r * cc, n_seq), min(r * cc + cc, n_seq))
+                own = hits[(qid >= lo) & (qid < hi)]
+            c.hits_upload(own, n_seq)
+            c.set_run_stride(run_stride(stride))
+            if table:  # a table describes one upload: after the records
+                b = np.ascontiguousarray(bounds, dtype="<u4")
+                ma._chk(L.mahip_set_shard_bounds(c.h, b.ctypes.data, W), "set_shard_bounds")
+            if positions and not full_input and active:
+                pos = np.ascontiguousarray(np.flatnonzero((qid >= lo) & (qid < hi)), dtype="<u4")
+                ma._chk(L.mahip_hits_set_positions(c.h, pos.ctypes.data, 0, len(hits)), "hits_set_positions")
+        got = each(lambda r, c: shard_range(c, n_seq, W, r))
+        per, tab = got[0][0], got[0][3]
+        rng = [(g[1], g[2]) for g in got]
+        S["per"], S["ranges"], S["table"] = per, rng, tab
+        mh, mo = flt_params(opt)
+
+        P = phase("sort")
+        for r, c in enumerate(ctxs):
+            ma._chk(L.mahip_set_full_input(c.h, 1 if full_input or W == 1 else 0), "set_full_input")
+            ma._chk(L.mahip_set_shard(c.h, rng[r][0] if active else 0, rng[r][1] if active else 0xffffffff), "set_shard")
+            c.sort()
+        P["path"] = each(lambda r, c: sort_last(c)["path"])
+
+        P = phase("sub#1")
+        P["n_rem1"] = each(lambda r, c: c.sub(opt.min_dp, opt.min_iden, 0, 0))
+        P["contrib"] = each(lambda r, c: c.sub_download(0, n_seq)[rng[r][0]:rng[r][1]])  # (the rest of the array is not the rank's to say)
+        P = phase("x:sub0")
+        if active:
+            P["contrib"] = x_slices(BUF_SUB0)
+        P["held"] = each(lambda r, c: c.sub_download(0, n_seq))
+
+        P = phase("cut+flt+sub#2")
+        res = each(lambda r, c: c.cutflt_sub(0, opt.min_span, mh, mo, opt.min_dp, opt.min_iden, opt.min_span // 2, 1))
+        P["n_cut"], P["n_flt"], P["cov"], P["n_rem2"] = [x[0] for x in res], [x[1] for x in res], [x[2] for x in res], [x[3] for x in res]
+        P["contrib"] = each(lambda r, c: c.sub_download(1, n_seq)[rng[r][0]:rng[r][1]])
+        P = phase("x:sub1")
+        if active:
+            P["contrib"] = x_slices(BUF_SUB1)
+        P["held"] = each(lambda r, c: c.sub_download(1, n_seq))
+
+        P = phase("merge+cut+contained")
+        for c in ctxs:
+            c.sub_merge()
+            ma._chk(L.mahip_hits_cut_contained_flags(c.h, 1, opt.min_span, C.byref(opt)), "hits_cut_contained_flags")
+        P["subm"] = each(lambda r, c: c.sub_download(0, n_seq))
+        P["r_cont"] = each(lambda r, c: buf_get(c, BUF_RCONT, 0, n_seq))
+        P["r_used"] = each(lambda r, c: buf_get(c, BUF_RUSED, 0, n_seq))
+        P = phase("x:flags")
+        if active:
+            P["contrib"] = x_flags([BUF_RCONT, BUF_RUSED])
+        P["held"] = each(lambda r, c: (buf_get(c, BUF_RCONT, 0, n_seq), buf_get(c, BUF_RUSED, 0, n_seq)))
+
+        P = phase("squeeze+sg flags")
+        P["n_cut"], P["n_seq_new"] = [], []
+        for c in ctxs:
+            nc, nn = C.c_size_t(0), C.c_uint32(0)
+            ma._chk(L.mahip_hits_cut_contained_finish(c.h, C.byref(nc), C.byref(nn)), "hits_cut_contained_finish")
+            P["n_cut"].append(nc.value); P["n_seq_new"].append(nn.value)
+        P["map"] = each(lambda r, c: c.map_download(n_seq))
+        P["sub"] = each(lambda r, c: c.sub_download(0, n_seq, squeezed=True)[:P["n_seq_new"][r]])
+        for c in ctxs:
+            ma._chk(L.mahip_sg_flags(c.h, C.byref(opt), 1, None, None), "sg_flags")
+        P["sdel"] = each(lambda r, c: buf_get(c, BUF_SDEL, 0, n_seq))
+        P = phase("x:seq.del")
+        if active:
+            P["contrib"] = [x[0] for x in x_flags([BUF_SDEL])]
+        P["held"] = each(lambda r, c: buf_get(c, BUF_SDEL, 0, n_seq))
+
+        P = phase("local arcs")
+        P["n_loc"], P["kernels"] = [], []  # kernels: the profiled launches of the call -- which arc sort ran (tests/test_gpu_graph_edges.py reads it the same way)
+        for c in ctxs:
+            n = C.c_uint32(0)
+            c.prof_enable(True)
+            c.prof_reset()
+            try:
+                ma._chk(L.mahip_sg_finish(c.h, C.byref(n)), "sg_finish")
+                P["kernels"].append(sorted({k["name"] for k in c.prof_get()}))
+            finally:
+                c.prof_enable(False)
+            P["n_loc"].append(n.value)
+        P["n_hits"] = each(lambda r, c: int(L.mahip_hits_live(c.h)))
+        n_loc = P["n_loc"]
+
+        P = phase("x:arc counts")  # one counter per rank, summed
+        counts = np.asarray(n_loc, dtype="<u4")
+        stride_a = max(1, int(counts.max()))
+        first = [int(counts[:r].sum()) for r in range(W)]
+        tot = int(counts.sum())
+        P["counts"], P["stride"], P["first"], P["tot"] = counts.copy(), stride_a, first, tot
+
+        P = phase("x:arc blocks")
+        if active:
+            P["contrib"] = x_rows(L.mahip_asg_export_rows, L.mahip_asg_import_rows)
+        P["held"] = each(lambda r, c: c.asg_download())
+        P["tie"] = each(lambda r, c: c.tie_stats())
+
+        P = phase("tie repair")
+        P["repaired"], P["conflicts"] = 0, None
+        if active:
+            unrep = [t["unrepaired"] for t in S["x:arc blocks"]["tie"]]
+            assert len(set(unrep)) == 1, "the ranks hold one graph and must take one decision: unrepaired %r" % unrep
+            if unrep[0]:
+                conf = []
+                for c in ctxs:
+                    n = C.c_uint64(0)
+                    ma._chk(L.mahip_sg_push_conflicts(c.h, C.byref(n)), "sg_push_conflicts")
+                    conf.append(n.value)
+                have_pos = sum(1 for c in ctxs if L.mahip_hits_have_positions(c.h))
+                P["conflicts"] = conf
+                if sum(conf) == 0 or full_input or have_pos == W:
+                    if sum(conf) and not full_input:
+                        P["repaired"] = None  # own records with positions: hits_reference_rank gathers the keys of all ranks through a live communicator -- the multi-process tests
+                    else:
+                        if sum(conf):
+                            for c in ctxs:
+                                ma._chk(L.mahip_sg_push_fix(c.h), "sg_push_fix")
+                        P["contrib"] = x_rows(L.mahip_asg_export_rows_push, L.mahip_asg_import_push_rows)
+                        P["repaired"] = 1
+        else:
+            P["repaired"] = ctxs[0].tie_stats()["arc_walk"]
+        P["held"] = each(lambda r, c: c.asg_download())
+
+        P = phase("reduction (own vertices)")
+        P["n_red"] = []
+        for r, c in enumerate(ctxs):
+            n = C.c_uint32(0)
+            ma._chk(L.mahip_asg_del_trans_range(c.h, opt.gap_fuzz, 2 * rng[r][0], 2 * rng[r][1] if active else 2 * n_seq, C.byref(n)), "asg_del_trans_range")
+            P["n_red"].append(n.value)
+        n_red = P["n_red"]
+
+        P = phase("x:del flags")
+        if active:
+            loc = []
+            for r, c in enumerate(ctxs):
+                p = xbuf(c, 0, stride_a * 4)
+                xbuf(c, 1, stride_a * 4 * W)
+                ma._chk(L.mahip_asg_flags_out(c.h, p, first[r], n_loc[r]), "asg_flags_out")
+                loc.append(dev_read(c, p, stride_a * 4))
+            gathered = np.concatenate(loc)
+            for r, c in enumerate(ctxs):
+                p = xbuf(c, 1, stride_a * 4 * W)
+                dev_write(c, p, gathered)
+                off = 0
+                for i in range(W):
+                    if i != r and counts[i]:
+                        ma._chk(L.mahip_asg_flags_in(c.h, p + i * stride_a * 4, off, int(counts[i])), "asg_flags_in")
+                    off += int(counts[i])
+            P["contrib"] = [loc[r][:n_loc[r] * 4].view("<u4").copy() for r in range(W)]
+        P["held"] = each(lambda r, c: c.asg_download()[0]["oldel"].copy())
+
+        P = phase("rank 0: cleanup+symm")
+        c = ctxs[0]
+        n_arc, P["n_multi"], P["n_asymm"] = C.c_uint32(0), 0, 0
+        if active:
+            ma._chk(L.mahip_asg_cleanup(c.h, C.byref(n_arc)), "asg_cleanup")
+            P["n_red"] = tot - n_arc.value
+            if P["n_red"]:
+                P["n_multi"], P["n_asymm"] = c.symm()
+        else:
+            P["n_red"] = n_red[0]
+            if n_red[0]:
+                ma._chk(L.mahip_asg_cleanup(c.h, C.byref(n_arc)), "asg_cleanup")
+                P["n_multi"], P["n_asymm"] = c.symm()
+        P["graph"] = c.asg_download()
+    finally:
+        for c in ctxs:
+            L.mahip_set_shard(c.h, 0, 0xffffffff)
+            L.mahip_set_full_input(c.h, 1)
+            c.set_exact_ties(2)
+    return S
+
+
+def one_context_flags(ctx, hits, n_seq, opt):
+    """the contained / touched-by-a-hit flags (hit.c:234-235, 24-36) of an unsharded run, read between the two halves of mahip_hits_cut_contained"""
+    L = shard_api()
+    ctx.hits_upload(hits, n_seq)
+    ctx.set_run_stride(run_stride())
+    ctx.sort()
+    ctx.sub(opt.min_dp, opt.min_iden, 0, 0)
+    mh, mo = flt_params(opt)
+    ctx.cutflt_sub(0, opt.min_span, mh, mo, opt.min_dp, opt.min_iden, opt.min_span // 2, 1)
+    ctx.sub_merge()
+    ma._chk(L.mahip_hits_cut_contained_flags(ctx.h, 1, opt.min_span, C.byref(opt)), "hits_cut_contained_flags")
+    out = buf_get(ctx, BUF_RCONT, 0, n_seq), buf_get(ctx, BUF_RUSED, 0, n_seq)
+    nc, nn = C.c_size_t(0), C.c_uint32(0)
+    ma._chk(L.mahip_hits_cut_contained_finish(ctx.h, C.byref(nc), C.byref(nn)), "hits_cut_contained_finish")
+    return out
+
+
+def ref_graph(hits, n_seq, opt):
+    """the unmodified reference library from a hit array to the reduced graph: the passes of ref_hit_stages, then ma_sg_gen against the merged intervals and
+    asg_arc_del_trans (with the cleanup and asg_symm it runs itself when something was reduced) -> dict(sg_arcs, sg_seq, n_red, tr_arcs, tr_idx)"""
+    L = R.ref()
+    L.radix_sort_hit.argtypes = [C.c_void_p, C.c_void_p]
+    L.radix_sort_hit.restype = None
+    a = np.ascontiguousarray(hits, dtype=HIT_DT)
+    n = len(a)
+    p = L.malloc_buf(max(n, 1) * HIT_DT.itemsize)
+    C.memmove(p, a.ctypes.data, n * HIT_DT.itemsize)
+    d = L.sd_init()
+    for i in range(n_seq):
+        L.sd_put(d, b"r%d" % i, 10000)
+    L.radix_sort_hit(p, p + n * HIT_DT.itemsize)
+    sub = L.ma_hit_sub(opt.min_dp, opt.min_iden, 0, n, p, n_seq)
+    n = L.ma_hit_cut(sub, opt.min_span, n, p)
+    cov = C.c_float(0)
+    mh, mo = flt_params(opt)
+    n = L.ma_hit_flt(sub, mh, mo, n, p, C.byref(cov))
+    sub2 = L.ma_hit_sub(opt.min_dp, opt.min_iden, opt.min_span // 2, n, p, n_seq)
+    n = L.ma_hit_cut(sub2, opt.min_span, n, p)
+    L.ma_sub_merge(n_seq, sub, sub2)
+    L.free_buf(sub2)
+    n = L.ma_hit_contained(C.byref(opt), d, sub, n, p)
+    g = L.ma_sg_gen(C.byref(opt), d, sub, n, p)
+    S = {}
+    S["sg_arcs"], S["sg_seq"], _ = R.asg_arrays(g)
+    S["n_red"] = L.asg_arc_del_trans(g, opt.gap_fuzz)
+    S["tr_arcs"], _, S["tr_idx"] = R.asg_arrays(g)
+    L.asg_destroy(g)
+    L.free_buf(sub)
+    L.free_buf(p)
+    L.sd_destroy(d)
+    return S
+
+
+def balance_model(qid, n_seq, world):
+    """include/mahip.h mahip_hits_balance: rank r starts at the first read behind which r / world of the hits lie -- the smallest q + 1 with
+    cum[q] * world >= n_hits * r (records with an id outside the dictionary count as hits of no read); entries no rank reaches are n_seq; without reads or hits:
+    equal read counts"""
+    qid = np.asarray(qid, dtype=np.int64)
+    n_hits = len(qid)
+    b = [0] + [n_seq] * world
+    if n_seq and n_hits and world > 1:
+        cum = np.cumsum(np.bincount(qid[qid < n_seq], minlength=n_seq)[:n_seq]).tolist()
+        for r in range(1, world):
+            b[r] = next((q + 1 for q in range(n_seq) if cum[q] * world >= n_hits * r), n_seq)
+    elif world > 1:
+        per = (n_seq + world - 1) // world
+        for r in range(1, world):
+            b[r] = min(r * per, n_seq)
+    return b

@@ -15,7 +15,10 @@ tests/test_gpu_sort_edges.py adds about three minutes: 62 to 69 s in normal orde
 back) and 131 s reversed with guard pages, the latter measured while other builds were using the box.  Its production-form case (67 M records) skips itself on
 the CPU build.
 tests/test_gpu_ingest_edges.py adds about two minutes: 45 s in normal order for its 68 tests (about 700 texts; the group-fallback texts of 4 to 8.5 MiB take
-4 s together, so none is held back for MA_EMU_FULL) and 58 s reversed with guard pages, both measured while other builds were using the box."""
+4 s together, so none is held back for MA_EMU_FULL) and 58 s reversed with guard pages, both measured while other builds were using the box.
+tests/test_gpu_shard_edges.py adds about three minutes: 71 s in normal order for its 60 tests (about 90 walks of the sharded head on up to eight contexts; the slowest
+test, four walks over the 56 000-record input, takes 7 s, so none is held back for MA_EMU_FULL) and 100 s reversed with guard pages, the latter measured while other
+builds were using the box."""
 import os
 import subprocess
 import sys
@@ -83,6 +86,7 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     run_gpu_tests(["tests/test_gpu_clean_edges.py"] + CLEAN_EDGES_SEL, 3000, env)  # the bubble tables, stacks and stamp arrays at their borders; the wave form without lock-step
     run_gpu_tests(["tests/test_gpu_ingest_edges.py"], 3000, env)  # the staged over-read in front of a tile, the n + 64 padding of the text, s_lend[256], lstart[L], cnt[n_gran]
     run_gpu_tests(["tests/test_gpu_sort_edges.py"], 3000, env)  # rkey[r00 - 1], the n + 128 padding of sidx, the rows / chunk sums / totals of the radix histograms and the tile minima of the group starts
+    run_gpu_tests(["tests/test_gpu_shard_edges.py"], 3000, env)  # the Rr-sized grids of the coverage sweeps and of the arc sort on a read range, goff[q_hi], the stride-padded row blocks of the imports
 
 
 def test_kernels_graph_api_on_cpu(emu_built):
@@ -101,6 +105,13 @@ def test_sort_size_edges_on_cpu(emu_built):
     """tests/test_gpu_sort_edges.py: the hit sort's own result (sidx, goff) and its report at every size the sort branches on, runs path, record paths, shard
     form and order sort; only the production-form case (67 M records) needs a real device and skips itself here"""
     run_gpu_tests(["tests/test_gpu_sort_edges.py"], 1800)
+
+
+def test_shard_edges_on_cpu(emu_built):
+    """tests/test_gpu_shard_edges.py: the sharded head phase by phase in one process (one context per rank, the exchanges done by the test through the ABI) on
+    read-range tables with borders at the deep and the many-arc reads, empty ranges, one rank owning every read, a world larger than the dictionary; against
+    the oracle, the one-context chain and the reference library"""
+    run_gpu_tests(["tests/test_gpu_shard_edges.py"], 1800)
 
 
 CLEAN_EDGES_SEL = [] if FULL else ["-k", "not border[3]"]  # the 196 608 / 196 609-entry probes (tiers 3 and 4): MA_EMU_FULL=1
