@@ -1051,7 +1051,6 @@ static int arc_cleanup(mahip_ctx *c, size_t n_in, int keep_in, int index_mode)
 	return 0;
 }
 
-static int bitlen_u64(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
 
 extern "C" int mahip_sg_flags(mahip_ctx_t *c, const ma_opt_t *opt, int use_sub, const uint32_t *seq_len, const uint8_t *seq_del)
 { // asm.c:14-35: seq.len/seq.del, one candidate arc per hit at the hit's slot, local seq.del side effects

@@ -1014,7 +1014,6 @@ __global__ __launch_bounds__(256) void k_sub_squeeze(const uint2 *__restrict__ s
 
 // ================================================================================================ host side
 
-static int bitlen(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
 
 static HitCols cols_of(mahip_ctx *c)
 {
@@ -1469,7 +1468,7 @@ int hits_reference_rank(mahip_ctx *c, bool collective_ok, bool wanted_only)
 		const size_t W = ids.size();
 		if (W == 0 || W > R / 4) break; // (nobody: cannot be, the caller saw conflicts; a quarter of the reads: the restriction buys little -- the whole walk)
 		// the stable order (what every other read keeps) and where the wanted reads' hits stand in it
-		const int bs = hits_qs_bits(c), bq = bitlen(R - 1);
+		const int bs = hits_qs_bits(c), bq = bitlen_u64(R - 1);
 		int g = 0;
 		CHK(radix_sort_pairs(c, N, 0, bs, 32, 32 + (bq ? bq : 1), &g));
 		CHK(dev_reserve(c, c->wseg, W * 12 + 64));
@@ -1503,12 +1502,12 @@ int hits_reference_rank(mahip_ctx *c, bool collective_ok, bool wanted_only)
 // bits of the largest query start (the caller's hint, else one sweep over the records)
 int hits_qs_bits(mahip_ctx *c)
 {
-	if (c->hint_max_qs) return bitlen(c->hint_max_qs);
+	if (c->hint_max_qs) return bitlen_u64(c->hint_max_qs);
 	if (c->n_in == 0 || !c->d_aos) return 32;
 	if (ctr_zero(c) != 0) return 32;
 	hipLaunchKernelGGL(k_hit_bounds, dim3(grid_for(c->n_in, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, c->d_aos, c->n_in, P<unsigned long long>(c->ctr));
 	if (ctr_fetch(c) != 0) return 32;
-	int b = bitlen(c->h_ctr[CT_MAXQS]);
+	int b = bitlen_u64(c->h_ctr[CT_MAXQS]);
 	return b ? b : 1;
 }
 
@@ -1525,7 +1524,7 @@ static int hits_order_rank(mahip_ctx *c, const uint32_t **rank)
 	if (c->hrank_ready && !ctx_sharded(c)) { *rank = P<uint32_t>(c->hrank); return 0; }
 	if (!c->orank_ready) {
 		unsigned long long *ctr = P<unsigned long long>(c->ctr);
-		const int bs = hits_qs_bits(c), bq = c->n_seq ? bitlen(c->n_seq - 1) : 32;
+		const int bs = hits_qs_bits(c), bq = c->n_seq ? bitlen_u64(c->n_seq - 1) : 32;
 		for (int k = 0; k < 2; ++k) { CHK(dev_reserve(c, c->key[k], (n + 1) * 8)); CHK(dev_reserve(c, c->val[k], (n + 1) * 4)); }
 		CHK(dev_reserve(c, c->orank, (n + 1) * 4));
 		hipLaunchKernelGGL(k_slot_keys, dim3(grid_for(n, 256)), dim3(256), 0, c->st, c->d_aos, (const uint32_t*)P<uint32_t>(c->sidx), n, P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
@@ -1570,13 +1569,13 @@ extern "C" int mahip_hits_sort(mahip_ctx_t *c)
 	CHK(dev_reserve(c, c->sidx, (n + 128) * 4));
 	c->sorted_here = true; c->hrank_ready = false; c->orank_ready = false;
 	// digit plan: bits of the query id above the bits of the record index
-	int bq, bi = bitlen(n - 1);
-	if (c->n_seq) bq = bitlen(c->n_seq - 1); // ids are < n_seq by contract (sdict.c:45-57 hands them out densely)
+	int bq, bi = bitlen_u64(n - 1);
+	if (c->n_seq) bq = bitlen_u64(c->n_seq - 1); // ids are < n_seq by contract (sdict.c:45-57 hands them out densely)
 	else {
 		CHK(ctr_zero(c));
 		hipLaunchKernelGGL(k_hit_bounds, dim3(grid_for(n, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, c->d_aos, n, ctr);
 		CHK(ctr_fetch(c));
-		bq = bitlen(c->h_ctr[CT_MAXQID]);
+		bq = bitlen_u64(c->h_ctr[CT_MAXQID]);
 	}
 	if (bi == 0) bi = 1;
 	if (bq == 0) bq = 1;

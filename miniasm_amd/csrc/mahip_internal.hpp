@@ -224,6 +224,9 @@ void clean_free(mahip_ctx *c);
 void ug_free(mahip_ctx *c);
 void useq_free(mahip_ctx *c);
 
+// bits needed for x (0 for 0): the width of a radix key that holds values up to x
+static inline int bitlen_u64(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
+
 static inline unsigned grid_for(size_t n, unsigned per_block, unsigned cap = 0x7fffffffu)
 {
 	size_t g = (n + per_block - 1) / per_block;

@@ -22,13 +22,11 @@
 #define PAF_EMPTY 0xffffffffffffffffull
 
 // counter slots used by this file (aliases into ctx->ctr)
-#define PC_LINES CT_TOTAL
 #define PC_VALID CT_LIVE
 #define PC_PASS CT_REMAIN
 #define PC_NOBL CT_OVF
 #define PC_MAXQS CT_MAXQS
 #define PC_OVERFLOW CT_OVF2
-#define PC_HITS CT_NRED
 #define PC_DISTINCT CT_NMULTI
 
 struct PafBufs {
@@ -176,10 +174,10 @@ __global__ __launch_bounds__(256) void k_paf_bl_compact(const uint32_t *__restri
 	uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i < L && f_hasbl[i]) blv[pos[i]] = bl[i];
 }
-__global__ __launch_bounds__(256) void k_paf_bl_fill(const uint32_t *__restrict__ f_hasbl, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ blv, uint32_t L, uint32_t *__restrict__ bl)
-{
+__global__ __launch_bounds__(256) void k_bl_fill_from(const uint32_t *__restrict__ f_hasbl, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ blv, uint32_t L, uint32_t *__restrict__ bl, uint32_t before)
+{ // before: what a line in front of the text's first 11-column line inherits -- 0 at the start of the file, the previous ranges' last bl in a range that does not start it
 	uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i < L && !f_hasbl[i]) bl[i] = pos[i] ? blv[pos[i] - 1] : 0u;
+	if (i < L && !f_hasbl[i]) bl[i] = pos[i] ? blv[pos[i] - 1] : before;
 }
 
 // ------------------------------------------------------------------------------------------------ tile parser (round 6)
@@ -333,9 +331,7 @@ __device__ __forceinline__ uint64_t lds_name_key(const uint32_t *__restrict__ w,
 	return h;
 }
 
-#ifndef PAF_TILE_WAVES
-#define PAF_TILE_WAVES 1 // __launch_bounds__' second argument (waves per SIMD the register allocation has to leave room for): an experiment handle
-#endif
+#define PAF_TILE_WAVES 1 // __launch_bounds__' second argument (waves per SIMD the register allocation has to leave room for)
 // the block's dynamic LDS (declared outside the template: the CPU test build's g++ gets an extern thread_local declared inside a template wrong)
 extern __shared__ __attribute__((aligned(16))) unsigned char s_text[];
 template <int CH> // a block stages up to CH * 16 KiB of text: CH * 64 bytes per thread in the newline ranking
@@ -868,11 +864,6 @@ __global__ __launch_bounds__(256) void k_name_rows(const uint64_t *__restrict__ 
 	uint32_t j = blockIdx.x * 256u + threadIdx.x;
 	if (j < R) { NameRow r; r.occ = (uint32_t)key[j] + occ_base; r.seq_len = seq_len[j]; r.name_len = name_len[j]; r.name_pos = name_pos[j]; out[j] = r; }
 }
-__global__ __launch_bounds__(256) void k_bl_fill_from(const uint32_t *__restrict__ f_hasbl, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ blv, uint32_t L, uint32_t *__restrict__ bl, uint32_t before)
-{ // k_paf_bl_fill for a text range that does not start the file: lines in front of the range's first 11-column line inherit `before`, the previous ranges' last bl
-	uint32_t i = blockIdx.x * 256u + threadIdx.x;
-	if (i < L && !f_hasbl[i]) bl[i] = pos[i] ? blv[pos[i] - 1] : before;
-}
 
 // ------------------------------------------------------------------------------------------------ records
 
@@ -881,9 +872,7 @@ __global__ __launch_bounds__(256) void k_bl_fill_from(const uint32_t *__restrict
 // A lane has a LINE (row r of the tile = lines 64 r .. 64 r + 63, wave w takes rows w, w + 4, ...): a line's 32 or 64 bytes of records leave from one lane, so the
 // lanes of a store instruction fill neighbouring 64-byte stretches (four lines per lane, as the first version had it, put them 256 bytes apart: 4.7 ms against
 // the 4.1 of the three launches it replaced).
-#ifndef EM_ROWS
 #define EM_ROWS 16u // rows per tile: a tile draws ONE ticket from one word (12 - 17 ns each, serial): 1 row 5.57 ms, 2: 4.59, 4: 4.09, 8: 3.96 per 100 M lines
-#endif
 #define EM_TILE (256u * EM_ROWS)
 __global__ __launch_bounds__(256) void k_paf_emit_chain(PafCols o, const uint32_t *__restrict__ slot_id, uint32_t L, int bi_dir, uint4 *__restrict__ rec, uint32_t *__restrict__ d_total,
                                                          unsigned long long *state, uint32_t *ticket, uint32_t ticket_base, uint32_t epoch)
@@ -906,9 +895,7 @@ __global__ __launch_bounds__(256) void k_paf_emit_chain(PafCols o, const uint32_
 	for (unsigned k = 0; k < EM_ROWS; ++k) {
 		cnt[k] = 0;
 		if (fl[k] & 2u) {
-#ifndef EXP_EMIT_NO_LOOKUP // (experiment: what the pass costs without its random fetches -- the ids are wrong then)
 			qid[k] = slot_id[qid[k]]; tid[k] = slot_id[tid[k]];
-#endif
 			cnt[k] = 1u + (bi_dir && qid[k] != tid[k]); // hit.c:87-98
 		}
 		const uint32_t incl = (uint32_t)wv_scan_incl_i32((int)cnt[k], lane);
@@ -998,11 +985,387 @@ extern "C" int mahip_paf_load_fd_range(mahip_ctx_t *c, int fd, size_t off, size_
 }
 
 static uint32_t pow2_at_least(uint64_t x) { uint64_t p = 1; while (p < x) p <<= 1; return p > 0x80000000ull ? 0x80000000u : (uint32_t)p; }
-static int bits_of(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
+
+// a few bytes of device memory, now (the stream is idle afterwards)
+static int fetch_bytes(mahip_ctx *c, const void *dptr, void *v, size_t bytes)
+{
+	HIPCHK(hipMemcpyAsync(v, dptr, bytes, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+static int fetch_u32(mahip_ctx *c, const void *dptr, uint32_t *v) { return fetch_bytes(c, dptr, v, 4); }
 
 extern "C" int mahip_paf_parse(mahip_ctx_t *c, int min_span, int min_match, int bi_dir, mahip_paf_info_t *info)
 {
 	return mahip_paf_parse_excl(c, min_span, min_match, bi_dir, 0, 0, 0.f, info);
+}
+
+// What the stages of one parse hand each other; lives for one mahip_paf_parse*.  The stages, in the order of this file's header: paf_census, paf_reserve_cols,
+// paf_fields, paf_cross_counts (ranks only), paf_stale_bl, paf_dict_local, paf_dict_merged (ranks only), paf_records + paf_adopt.
+struct PafParse {
+	uint32_t L = 0;           // lines (the virtual newline of an unterminated tail is counted)
+	size_t n_eff = 0;         // the tile parser's text: n + the appended newline
+	int open_line = 0;
+	uint32_t n_gran = 0, tile_k = 1, n_tiles = 0;
+	PafCols o;
+	size_t n_valid = 0, n_pass = 0, n_nobl = 0, n_long = 0, n_hits = 0;
+	uint32_t max_qs = 0, n_excl = 0;
+	uint64_t line_base = 0, lines_total = 0, valid_total = 0, pass_total = 0, nobl_total = 0; // lines of the ranges in front of this one; totals over the ranks
+	uint32_t R = 0, cap_used = 0; // names with an id; slots of the local table
+	int gen_local = 0;            // c->key[gen_local]: the local first appearances, sorted
+	const uint32_t *slot_to_id = nullptr; // table slot -> id, for the records
+};
+
+// ---- line starts: newline census per KiB, the tile geometry (the tile parser writes the line starts itself)
+static int paf_census(mahip_ctx *c, PafBufs *b, PafParse &ps)
+{
+	const size_t n = b->nbytes;
+	const unsigned char *text = P<unsigned char>(b->text);
+	CHK(dev_reserve(c, b->scal, 64));
+	CHK(ctr_zero(c));
+	ps.n_eff = n;
+	if (!n) return 0;
+	{ // same decision as the kernels': L = newlines + an unterminated tail
+		unsigned char last = 0;
+		CHK(fetch_bytes(c, text + n - 1, &last, 1));
+		ps.open_line = last != '\n';
+	}
+	// every line ends with a newline: a text that does not gets one (the buffer has 64 spare bytes; the line start after it is n + 1),
+	// and zeros follow, so that the kernels read whole 16-byte pieces
+	HIPCHK(hipMemsetAsync((void*)(text + n), 0, 64, c->st));
+	if (ps.open_line) HIPCHK(hipMemsetAsync((void*)(text + n), '\n', 1, c->st));
+	ps.n_eff = n + (size_t)ps.open_line;
+	const size_t ng = (ps.n_eff + PAF_GRAN - 1) / PAF_GRAN;
+	if (ng > 0x7ffffff0ull) { mahip_set_error("mahip_paf_parse: text too large"); return -1; }
+	const uint32_t n_gran = ps.n_gran = (uint32_t)ng;
+	CHK(dev_reserve(c, b->tile, ((size_t)n_gran + 8) * 4)); CHK(dev_reserve(c, b->glast, ((size_t)n_gran + 8) * 4));
+	{
+		ProfScope ps_(c, "k_paf_nl_count", (double)n);
+		hipLaunchKernelGGL(k_paf_gran_count, dim3((n_gran + 4 * PAF_GC_PER_WAVE - 1) / (4 * PAF_GC_PER_WAVE)), dim3(256), 0, c->st, text, ps.n_eff, n_gran, P<uint32_t>(b->tile), P<uint32_t>(b->glast));
+	}
+	CHK(scan_exclusive_u32(c, P<uint32_t>(b->tile), P<uint32_t>(b->tile), n_gran, P<uint32_t>(b->tile) + n_gran)); // goff[n_gran] = all newlines
+	uint32_t n_nl = 0;
+	CHK(fetch_u32(c, P<uint32_t>(b->tile) + n_gran, &n_nl));
+	if ((uint64_t)n_nl + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse: more than 2^31 lines"); return -1; }
+	const uint32_t L = ps.L = n_nl; // (the virtual newline is counted)
+	CHK(dev_reserve(c, b->lstart, ((size_t)L + 4) * 8));
+	if (!L) return 0;
+	// tile = K granules with about 240 lines (a lane per line, 256 lanes); at most what a block stages (15 KiB + 1 KiB in front with 16 KiB of LDS text, 31 + 1 with 32)
+	double k = 240.0 * ((double)n / (double)L) / (double)PAF_GRAN;
+	if (const char *e = getenv("MA_PAF_TILE_K")) k = atof(e);
+	ps.tile_k = k < 1.0 ? 1u : k > 31.0 ? 31u : (uint32_t)k;
+	ps.n_tiles = (n_gran + ps.tile_k - 1) / ps.tile_k;
+	const uint32_t n_grp = (n_gran >> PAF_BGRP) + 1;
+	CHK(dev_reserve(c, b->gmax, ((size_t)n_grp + 1) * 8)); CHK(dev_reserve(c, b->tfirst, ((size_t)ps.n_tiles + 1) * 8));
+	hipLaunchKernelGGL(k_paf_gran_bmax, dim3(n_grp), dim3(64), 0, c->st, (const uint32_t*)P<uint32_t>(b->glast), n_gran, P<unsigned long long>(b->gmax));
+	hipLaunchKernelGGL(k_paf_tile_first, dim3(grid_for(ps.n_tiles, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->glast), (const unsigned long long*)P<unsigned long long>(b->gmax), ps.tile_k, ps.n_tiles,
+	                   P<unsigned long long>(b->tfirst));
+	return 0;
+}
+
+// ---- the per-line columns (and the two work arrays of the passes over them)
+static int paf_reserve_cols(mahip_ctx *c, PafBufs *b, PafParse &ps)
+{
+	PafCols &o = ps.o;
+	const size_t Lr = (size_t)ps.L + 4;
+	CHK(dev_reserve(c, b->flags, Lr));
+	for (int k = 0; k < 8; ++k) CHK(dev_reserve(c, b->num[k], Lr * 4));
+	CHK(dev_reserve(c, b->tnoff, Lr * 4)); CHK(dev_reserve(c, b->qlen, Lr * 4)); CHK(dev_reserve(c, b->tlen, Lr * 4));
+	CHK(dev_reserve(c, b->hq, Lr * 8)); CHK(dev_reserve(c, b->ht, Lr * 8));
+	CHK(dev_reserve(c, b->qslot, Lr * 4)); CHK(dev_reserve(c, b->tslot, Lr * 4));
+	o.flags = P<uint8_t>(b->flags);
+	o.ql = P<uint32_t>(b->num[0]); o.qs = P<uint32_t>(b->num[1]); o.qe = P<uint32_t>(b->num[2]); o.tl = P<uint32_t>(b->num[3]);
+	o.ts = P<uint32_t>(b->num[4]); o.te = P<uint32_t>(b->num[5]); o.ml = P<uint32_t>(b->num[6]); o.bl = P<uint32_t>(b->num[7]);
+	o.tnoff = P<uint32_t>(b->tnoff); o.qlen = P<uint32_t>(b->qlen); o.tlen = P<uint32_t>(b->tlen);
+	o.hq = P<uint64_t>(b->hq); o.ht = P<uint64_t>(b->ht); o.qslot = P<uint32_t>(b->qslot); o.tslot = P<uint32_t>(b->tslot);
+	if (ps.L) { CHK(dev_reserve(c, c->keep, ((size_t)ps.L + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)ps.L + 16) * 4)); }
+	return 0;
+}
+
+// ---- fields: the tile parser, the byte-wise routine on the lines it left, the counts
+static int paf_fields(mahip_ctx *c, PafBufs *b, PafParse &ps, int min_span, int min_match)
+{
+	const uint32_t L = ps.L;
+	if (!L) return 0;
+	const unsigned char *text = P<unsigned char>(b->text);
+	unsigned long long *ctr = P<unsigned long long>(c->ctr);
+	mahip_paf_report_t &rp = b->rep;
+	{
+		ProfScope ps_(c, "k_paf_parse", (double)b->nbytes + 69.0 * (double)L);
+		TileArgs ta;
+		ta.text = text; ta.n = ps.n_eff; ta.K = ps.tile_k; ta.n_gran = ps.n_gran; ta.n_tiles = ps.n_tiles; ta.L = L;
+		ta.goff = (const uint32_t*)P<uint32_t>(b->tile); ta.first = (const unsigned long long*)P<unsigned long long>(b->tfirst);
+		ta.min_span = min_span; ta.min_match = min_match;
+		const int ch = ps.tile_k <= 15 ? 1 : 2;
+		const uint32_t reg = (uint32_t)ch * 16384u, lds = reg + 32 + 2 * (reg / 16 + 8) * 2 + 260 * 4;
+		uint32_t per_cu = (160u * 1024u) / (lds + 64u); if (per_cu > 8) per_cu = 8; // blocks a CU holds: the grid is what fits the chip, a block works through tiles (one set of counter atomics per block)
+		const unsigned grid = grid_for(ps.n_tiles, 1, 256u * per_cu);
+		rp.tile_form = ch;
+		if (ch == 1) hipLaunchKernelGGL(k_paf_parse_tile<1>, dim3(grid), dim3(256), lds, c->st, ta, ps.o, P<uint64_t>(b->lstart), ctr);
+		else hipLaunchKernelGGL(k_paf_parse_tile<2>, dim3(grid), dim3(256), lds, c->st, ta, ps.o, P<uint64_t>(b->lstart), ctr);
+	}
+	CHK(ctr_fetch(c));
+	rp.n_odd = c->h_ctr[PC_ODD];
+	if (c->paf_keep_odd) { // tests: which lines the tile parser left to the byte-wise routine (the final flags do not say)
+		b->odd_snap.resize(L);
+		CHK(fetch_bytes(c, ps.o.flags, b->odd_snap.data(), L));
+		for (uint8_t &f : b->odd_snap) f = f == PF_ODD;
+	}
+	if (c->h_ctr[PC_ODD]) { // lines the straight-line parser does not cover: the byte-wise routine on them (the counters add up)
+		ProfScope ps_(c, "k_paf_parse_odd", 0.0);
+		hipLaunchKernelGGL(k_paf_parse_odd, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, min_span, min_match, ps.o, ctr);
+		CHK(ctr_fetch(c));
+		rp.odd_ran = 1;
+	}
+	ps.n_valid = (size_t)c->h_ctr[PC_VALID]; ps.n_pass = (size_t)c->h_ctr[PC_PASS]; ps.n_nobl = (size_t)c->h_ctr[PC_NOBL];
+	ps.n_long = (size_t)c->h_ctr[PC_LONG];
+	ps.max_qs = (uint32_t)c->h_ctr[PC_MAXQS];
+	return 0;
+}
+
+// ---- what the ranges have to know of each other before names and records can be numbered (a collective)
+static int paf_cross_counts(mahip_ctx *c, PafParse &ps)
+{
+	const int W = mahip_comm_world(c), me = mahip_comm_rank(c);
+	uint64_t mine[5] = { ps.L, ps.n_valid, ps.n_pass, ps.n_nobl, ps.max_qs }, all[5 * 32];
+	CHK(mahip_comm_all_gather_u64(c, mine, 5, all));
+	for (int r = 0; r < W; ++r) {
+		if (r < me) ps.line_base += all[5 * r];
+		ps.lines_total += all[5 * r]; ps.valid_total += all[5 * r + 1]; ps.pass_total += all[5 * r + 2]; ps.nobl_total += all[5 * r + 3];
+		if (all[5 * r + 4] > ps.max_qs) ps.max_qs = (uint32_t)all[5 * r + 4];
+	}
+	if (ps.lines_total + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse_sharded: more than 2^31 lines"); return -1; }
+	return 0;
+}
+
+// ---- stale bl: rare (PAF writers emit 12+ columns).  The bl of the lines that have one, compacted; a line without takes the one in front of it.
+// exchange (a collective: every rank comes here when ANY rank has a 10-column line): every range says what `bl` it leaves behind (the bl of its last 11-column
+// line), and a line in front of a range's first 11-column line inherits from the nearest range before it that has one (paf.c:54: the field is simply not written)
+static int paf_stale_bl(mahip_ctx *c, PafBufs *b, PafParse &ps, bool exchange)
+{
+	const uint32_t L = ps.L;
+	uint32_t *has = P<uint32_t>(c->keep), *pos = P<uint32_t>(c->pos);
+	uint32_t n_has = 0, last_bl = 0, before = 0;
+	if (L) {
+		CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
+		hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)ps.o.flags, L, has);
+		CHK(scan_exclusive_u32(c, has, pos, L, exchange ? P<uint32_t>(b->scal) : nullptr));
+		hipLaunchKernelGGL(k_paf_bl_compact, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)has, (const uint32_t*)pos, (const uint32_t*)ps.o.bl, L, P<uint32_t>(b->blv));
+		if (exchange) {
+			CHK(fetch_u32(c, b->scal.p, &n_has));
+			if (n_has) CHK(fetch_u32(c, P<uint32_t>(b->blv) + (n_has - 1), &last_bl));
+		}
+	}
+	if (exchange) {
+		const int me = mahip_comm_rank(c);
+		uint64_t two[2] = { n_has ? 1u : 0u, last_bl }, every[2 * 32];
+		CHK(mahip_comm_all_gather_u64(c, two, 2, every));
+		for (int r = 0; r < me; ++r) if (every[2 * r]) before = (uint32_t)every[2 * r + 1];
+	}
+	if (L && ps.n_nobl) hipLaunchKernelGGL(k_bl_fill_from, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)has, (const uint32_t*)pos, (const uint32_t*)P<uint32_t>(b->blv), L, ps.o.bl, before);
+	return 0;
+}
+
+// A temporary of one stage: its memory goes back when the scope ends, however it ends.  dev_free does not wait and hands the memory to the next buffer that asks, so the
+// destructor waits for the stream first: kernels that read the buffer may still be queued when a stage gives up half way
+struct ScopedDev {
+	mahip_ctx *c;
+	DevBuf b;
+	explicit ScopedDev(mahip_ctx *c_) : c(c_) {}
+	ScopedDev(const ScopedDev&) = delete;
+	ScopedDev &operator=(const ScopedDev&) = delete;
+	~ScopedDev() { release(); }
+	void release() { if (b.p) { (void)hipStreamSynchronize(c->st); dev_free(c, b); } }
+};
+
+// lengths + 1 of R names in c->keep -> name_pos and the size of the block; the block; the names copied into it out of `src` (name_off counts from there), a NUL behind
+// each.  done_first: a temporary nothing needs any more once the scan is through, released before the block is reserved (the stage's peak memory)
+static int paf_name_block(mahip_ctx *c, PafBufs *b, const unsigned char *src, uint32_t R, ScopedDev *done_first = nullptr)
+{
+	uint32_t nb = 0;
+	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(b->name_pos), R, P<uint32_t>(b->scal)));
+	CHK(fetch_u32(c, b->scal.p, &nb));
+	if (done_first) done_first->release();
+	CHK(dev_reserve(c, b->names, (size_t)nb + 16));
+	if (R) hipLaunchKernelGGL(k_dict_names, dim3(grid_for(R, 256)), dim3(256), 0, c->st, src, (const uint64_t*)P<uint64_t>(b->name_off), (const uint32_t*)P<uint32_t>(b->name_len),
+	                          (const uint32_t*)P<uint32_t>(b->name_pos), R, P<char>(b->names));
+	b->name_bytes = nb;
+	return 0;
+}
+
+// ---- dictionary: distinct names, ids in order of first appearance
+static int paf_dict_local(mahip_ctx *c, PafBufs *b, PafParse &ps, int no_cont, int max_hang, float int_frac)
+{
+	const uint32_t L = ps.L;
+	const PafCols &o = ps.o;
+	const unsigned char *text = P<unsigned char>(b->text);
+	unsigned long long *ctr = P<unsigned long long>(c->ctr);
+	mahip_paf_report_t &rp = b->rep;
+	// The number of distinct names is not known before the pass (<= 2 per stored line; in overlap files a read has tens of lines).  Start with a
+	// table sized for 16 lines per name -- 8x smaller than the safe size, it stays in the last-level cache -- count the names as they go in, and
+	// repeat the pass with a table for 4x that many only if the load factor came out above 1/2 (or a probe sequence ran out)
+	const uint32_t cap_max = pow2_at_least(4 * (uint64_t)ps.n_pass + 65536); // load <= 1/2 whatever the file holds
+	uint32_t cap = pow2_at_least(ps.n_pass / 16 + 65536);
+	if (const char *e = getenv("MA_DICT_CAP_LOG2")) { int l2 = atoi(e); if (l2 >= 4 && l2 <= 31) cap = 1u << l2; } // tests: force the growth path
+	const bool short_names = ps.n_long == 0 && !getenv("MA_DICT_EXACT_TEXT"); // every name is its own key: no text compared (k_dict_insert_short)
+	rp.dict_form = short_names ? MAHIP_PAF_DICT_SHORT : MAHIP_PAF_DICT_TEXT;
+	for (int attempt = 0;; ++attempt) {
+		CHK(dev_reserve(c, b->tab, (size_t)cap * 16)); CHK(dev_reserve(c, b->tmin, (size_t)cap * 4)); CHK(dev_reserve(c, b->slot_id, (size_t)cap * 4));
+		CHK(ctr_zero(c));
+		if (short_names) {
+			HIPCHK(hipMemsetAsync(b->tab.p, 0, (size_t)cap * 16, c->st));
+			ProfScope ps_(c, "k_dict_insert", 2.0 * 40.0 * (double)ps.n_pass);
+			hipLaunchKernelGGL(k_dict_insert_short, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, (DSlot*)b->tab.p, cap - 1, ctr);
+		} else {
+			HIPCHK(hipMemsetAsync(b->tab.p, 0xff, (size_t)cap * 16, c->st));
+			ProfScope ps_(c, "k_dict_insert", 2.0 * 40.0 * (double)ps.n_pass);
+			hipLaunchKernelGGL(k_dict_insert, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, o, (XSlot*)b->tab.p, cap - 1, ctr);
+		}
+		CHK(ctr_fetch(c));
+		const uint64_t distinct = c->h_ctr[PC_DISTINCT];
+		rp.n_attempts = attempt + 1; rp.cap[attempt] = cap; rp.n_distinct = distinct;
+		rp.end[attempt] = c->h_ctr[PC_OVERFLOW] ? MAHIP_PAF_TAB_PROBES : 2 * distinct > cap ? MAHIP_PAF_TAB_LOAD : MAHIP_PAF_TAB_OK;
+		if (c->h_ctr[PC_OVERFLOW] == 0 && 2 * distinct <= cap) break;
+		if (attempt >= 3 || cap >= cap_max) { if (c->h_ctr[PC_OVERFLOW] == 0) break; mahip_set_error("mahip_paf_parse: name table overflow"); return -1; }
+		uint32_t want = pow2_at_least(4 * distinct + 65536);
+		if (want <= cap) want = cap < 0x10000000u ? cap << 3 : cap_max; // a probe sequence ran out: the count is incomplete
+		cap = want < cap_max ? want : cap_max;
+	}
+	if (short_names) hipLaunchKernelGGL(k_dict_short_tmin, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const DSlot*)b->tab.p, cap, P<uint32_t>(b->tmin));
+	else hipLaunchKernelGGL(k_dict_exact_tmin, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const XSlot*)b->tab.p, cap, P<uint32_t>(b->tmin));
+	if (no_cont) { // hit.c:38-68 + hit.c:86
+		CHK(dev_reserve(c, b->excl, (size_t)cap + 16));
+		HIPCHK(hipMemsetAsync(b->excl.p, 0, cap, c->st));
+		hipLaunchKernelGGL(k_paf_nocont, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, max_hang, int_frac, P<uint8_t>(b->excl));
+		HIPCHK(hipMemsetAsync(b->tmin.p, 0xff, (size_t)cap * 4, c->st));
+		CHK(ctr_zero(c));
+		hipLaunchKernelGGL(k_paf_refilter, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, (const uint8_t*)P<uint8_t>(b->excl), P<uint32_t>(b->tmin), ctr);
+		hipLaunchKernelGGL(k_excl_count, dim3(grid_for(cap, 256, 2048)), dim3(256), 0, c->st, (const uint8_t*)P<uint8_t>(b->excl), cap, ctr);
+		CHK(ctr_fetch(c));
+		ps.n_pass = (size_t)c->h_ctr[PC_PASS];
+		ps.n_excl = (uint32_t)c->h_ctr[PC_VALID];
+	}
+	// the slots in use, sorted by first appearance: rank = id
+	uint32_t R = 0;
+	CHK(dev_reserve(c, c->keep, ((size_t)cap + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)cap + 16) * 4));
+	hipLaunchKernelGGL(k_dict_flag, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->tmin), cap, P<uint32_t>(c->keep));
+	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), cap, P<uint32_t>(b->scal)));
+	CHK(fetch_u32(c, b->scal.p, &R));
+	for (int k = 0; k < 2; ++k) { CHK(dev_reserve(c, c->key[k], ((size_t)R + 1) * 8)); CHK(dev_reserve(c, c->val[k], ((size_t)R + 1) * 4)); }
+	hipLaunchKernelGGL(k_dict_collect, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->tmin), cap,
+	                   P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
+	int gen = 0;
+	CHK(radix_sort_pairs(c, R, 0, bitlen_u64(2ull * L), 0, 0, &gen));
+	CHK(dev_reserve(c, b->seq_len, ((size_t)R + 4) * 4)); CHK(dev_reserve(c, b->name_off, ((size_t)R + 4) * 8));
+	CHK(dev_reserve(c, b->name_len, ((size_t)R + 4) * 4)); CHK(dev_reserve(c, b->name_pos, ((size_t)R + 4) * 4));
+	hipLaunchKernelGGL(k_dict_assign, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint64_t*)P<uint64_t>(c->key[gen]), (const uint32_t*)P<uint32_t>(c->val[gen]), R,
+	                   (const uint64_t*)P<uint64_t>(b->lstart), o, P<uint32_t>(b->slot_id), P<uint32_t>(b->seq_len), P<uint64_t>(b->name_off), P<uint32_t>(b->name_len), P<uint32_t>(c->keep));
+	CHK(paf_name_block(c, b, text, R));
+	ps.R = R; ps.cap_used = cap; ps.gen_local = gen;
+	return 0;
+}
+
+// ---- the ranks' name tables -> one dictionary (kernels above; a collective)
+static int paf_dict_merged(mahip_ctx *c, PafBufs *b, PafParse &ps)
+{
+	const int W = mahip_comm_world(c), me = mahip_comm_rank(c);
+	unsigned long long *ctr = P<unsigned long long>(c->ctr);
+	const uint32_t R_loc = ps.R, cap_used = ps.cap_used;
+	const size_t nb_loc = b->name_bytes;
+	uint64_t mine[2] = { R_loc, nb_loc }, all[2 * 32];
+	CHK(mahip_comm_all_gather_u64(c, mine, 2, all));
+	uint32_t stride_rows = 1, h_rows[32];
+	size_t stride_bytes = 16, sum_rows = 0;
+	for (int r = 0; r < W; ++r) { h_rows[r] = (uint32_t)all[2 * r]; sum_rows += all[2 * r]; if (all[2 * r] > stride_rows) stride_rows = (uint32_t)all[2 * r]; if (all[2 * r + 1] > stride_bytes) stride_bytes = (size_t)all[2 * r + 1]; }
+	stride_bytes = (stride_bytes + 15) & ~(size_t)15;
+	if ((uint64_t)stride_rows * (uint64_t)W >= 0xffffffffull) { mahip_set_error("mahip_paf_parse_sharded: too many names"); return -1; }
+	// my rows and name bytes into exchange buffers, gathered with the stride of the largest range
+	ScopedDev rows_all(c), blobs_all(c), aux(c);
+	void *xr = nullptr, *xb = nullptr;
+	CHK(mahip_xbuf(c, 0, (size_t)stride_rows * sizeof(NameRow) + stride_bytes, &xr));
+	xb = (char*)xr + (size_t)stride_rows * sizeof(NameRow);
+	if (R_loc) {
+		hipLaunchKernelGGL(k_name_rows, dim3(grid_for(R_loc, 256)), dim3(256), 0, c->st, (const uint64_t*)P<uint64_t>(c->key[ps.gen_local]), R_loc, (uint32_t)(2 * ps.line_base), (const uint32_t*)P<uint32_t>(b->seq_len),
+		                   (const uint32_t*)P<uint32_t>(b->name_len), (const uint32_t*)P<uint32_t>(b->name_pos), (NameRow*)xr);
+		HIPCHK(hipMemcpyAsync(xb, b->names.p, nb_loc, hipMemcpyDeviceToDevice, c->st));
+	}
+	CHK(dev_reserve(c, rows_all.b, (size_t)W * stride_rows * sizeof(NameRow) + 64));
+	CHK(dev_reserve(c, blobs_all.b, (size_t)W * stride_bytes + 64));
+	CHK(mahip_comm_all_gather(c, xr, rows_all.b.p, (size_t)stride_rows * sizeof(NameRow)));
+	CHK(mahip_comm_all_gather(c, xb, blobs_all.b.p, stride_bytes));
+	// one table for all of them: at most sum_rows distinct names
+	const uint32_t gcap = pow2_at_least(2 * (uint64_t)sum_rows + 1024);
+	const size_t total_rows = (size_t)W * stride_rows;
+	// aux: tab[gcap] u64 | gkey[gcap] u64 | slot_of[total_rows] u32 | gid_of_slot[gcap] u32 | n_rows[32] u32
+	const size_t o_key = (size_t)gcap * 8, o_slot = o_key + (size_t)gcap * 8, o_gid = o_slot + ((total_rows * 4 + 7) & ~(size_t)7), o_n = o_gid + (size_t)gcap * 4;
+	CHK(dev_reserve(c, aux.b, o_n + 32 * 4 + 64));
+	char *const ax = (char*)aux.b.p;
+	unsigned long long *gtab = (unsigned long long*)ax, *gkey = (unsigned long long*)(ax + o_key);
+	uint32_t *slot_of = (uint32_t*)(ax + o_slot), *gid_of_slot = (uint32_t*)(ax + o_gid), *d_rows = (uint32_t*)(ax + o_n);
+	HIPCHK(hipMemsetAsync(ax, 0xff, o_slot, c->st));
+	HIPCHK(hipMemcpyAsync(d_rows, h_rows, (size_t)W * 4, hipMemcpyHostToDevice, c->st));
+	CHK(ctr_zero(c));
+	if (sum_rows) hipLaunchKernelGGL(k_dict_merge, dim3(grid_for(total_rows, 256, 8192)), dim3(256), 0, c->st, (const NameRow*)rows_all.b.p, (const unsigned char*)blobs_all.b.p, (const uint32_t*)d_rows, W,
+	                                 stride_rows, stride_bytes, gtab, gkey, gcap - 1, slot_of, ctr);
+	CHK(ctr_fetch(c));
+	if (c->h_ctr[PC_OVERFLOW]) { mahip_set_error("mahip_paf_parse_sharded: name table overflow"); return -1; }
+	// distinct names sorted by first appearance = ids
+	CHK(dev_reserve(c, c->keep, ((size_t)gcap + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)gcap + 16) * 4));
+	hipLaunchKernelGGL(k_merge_flag, dim3(grid_for(gcap, 256)), dim3(256), 0, c->st, (const unsigned long long*)gtab, gcap, P<uint32_t>(c->keep));
+	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), gcap, P<uint32_t>(b->scal)));
+	uint32_t Rg = 0;
+	CHK(fetch_u32(c, b->scal.p, &Rg));
+	for (int k = 0; k < 2; ++k) { CHK(dev_reserve(c, c->key[k], ((size_t)Rg + 1) * 8)); CHK(dev_reserve(c, c->val[k], ((size_t)Rg + 1) * 4)); }
+	hipLaunchKernelGGL(k_merge_collect, dim3(grid_for(gcap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const unsigned long long*)gkey, gcap,
+	                   P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
+	int gen = 0;
+	CHK(radix_sort_pairs(c, Rg, 0, bitlen_u64(2ull * ps.lines_total), 0, 0, &gen));
+	// the map for this rank's records BEFORE the local arrays are overwritten: local slot -> global id (k_merge_map needs the local "slot in use" flags)
+	if (cap_used) CHK(dev_reserve(c, b->excl, (size_t)cap_used * 4 + 16)); // (the -R flag array is free in this mode: the map lives there)
+	CHK(dev_reserve(c, b->seq_len, ((size_t)Rg + 4) * 4)); CHK(dev_reserve(c, b->name_off, ((size_t)Rg + 4) * 8));
+	CHK(dev_reserve(c, b->name_len, ((size_t)Rg + 4) * 4)); CHK(dev_reserve(c, b->name_pos, ((size_t)Rg + 4) * 4));
+	// keep / pos are about to be reused for the name lengths: the local flags first
+	ScopedDev used_local(c);
+	if (cap_used) {
+		CHK(dev_reserve(c, used_local.b, (size_t)cap_used * 4 + 16));
+		hipLaunchKernelGGL(k_dict_flag, dim3(grid_for(cap_used, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->tmin), cap_used, (uint32_t*)used_local.b.p);
+	}
+	CHK(dev_reserve(c, c->keep, ((size_t)Rg + 16) * 4));
+	if (Rg) hipLaunchKernelGGL(k_merge_assign, dim3(grid_for(Rg, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->val[gen]), Rg, (const unsigned long long*)gtab, (const unsigned long long*)gkey,
+	                           (const NameRow*)rows_all.b.p, stride_rows, stride_bytes, gid_of_slot, P<uint32_t>(b->seq_len), P<uint64_t>(b->name_off), P<uint32_t>(b->name_len), P<uint32_t>(c->keep));
+	if (cap_used) hipLaunchKernelGGL(k_merge_map, dim3(grid_for(cap_used, 256)), dim3(256), 0, c->st, (const uint32_t*)used_local.b.p, (const uint32_t*)P<uint32_t>(b->slot_id), cap_used,
+	                                 (const uint32_t*)slot_of, (uint32_t)((size_t)me * stride_rows), (const uint32_t*)gid_of_slot, P<uint32_t>(b->excl));
+	CHK(paf_name_block(c, b, (const unsigned char*)blobs_all.b.p, Rg, &used_local));
+	ps.R = Rg; b->n_seq = Rg;
+	ps.slot_to_id = (const uint32_t*)P<uint32_t>(b->excl);
+	return 0; // (the gathered blocks are released here: their guards wait for k_dict_names)
+}
+
+// ---- records: hit (+ mirrored hit) per stored line, in line order.  One pass: ids, record slots (chained tiles), records
+static int paf_records(mahip_ctx *c, PafBufs *b, PafParse &ps, int bi_dir)
+{
+	const size_t max_hits = bi_dir ? 2 * ps.n_pass : ps.n_pass;
+	if (max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
+	CHK(dev_reserve(c, c->aos_own, (max_hits + 1) * sizeof(ma_hit_t)));
+	const size_t nb = ((size_t)ps.L + EM_TILE - 1) / EM_TILE;
+	uint32_t *ticket; unsigned long long *state; uint32_t ticket_base, epoch;
+	CHK(scan_chain_begin(c, nb, &state, &ticket, &ticket_base, &epoch));
+	uint32_t nh = 0;
+	{
+		ProfScope ps_(c, "k_paf_emit", 37.0 * (double)ps.n_pass + 32.0 * (double)max_hits);
+		hipLaunchKernelGGL(k_paf_emit_chain, dim3((unsigned)nb), dim3(256), 0, c->st, ps.o, ps.slot_to_id, ps.L, bi_dir, (uint4*)c->aos_own.p, P<uint32_t>(b->scal), state, ticket, ticket_base, epoch);
+	}
+	CHK(fetch_u32(c, b->scal.p, &nh));
+	ps.n_hits = nh;
+	return 0;
+}
+// the context takes the records as its input (none: a one-record buffer, so that d_aos points somewhere)
+static int paf_adopt(mahip_ctx *c, PafParse &ps)
+{
+	CHK(mahip_hits_adopt(c, nullptr, ps.n_hits, ps.R)); // resets the per-upload state and sizes the read arrays
+	CHK(dev_reserve(c, c->aos_own, sizeof(ma_hit_t)));
+	c->d_aos = (const ma_hit_t*)c->aos_own.p;
+	return 0;
 }
 
 // sharded: the text in the context is THIS RANK'S byte range of the file (cut at line starts, ranges in rank order); the context has a communicator.  The ranks
@@ -1013,14 +1376,9 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 {
 	HIPCHK(hipSetDevice(c->dev));
 	PafBufs *b = paf_of(c);
-	const int W = sharded ? mahip_comm_world(c) : 1, me = sharded ? mahip_comm_rank(c) : 0;
 	if (sharded && no_cont) { mahip_set_error("mahip_paf_parse_sharded: the -R pre-filter needs the whole text on one rank"); return -1; }
-	if (sharded && W > 32) { mahip_set_error("mahip_paf_parse_sharded: at most 32 ranks"); return -1; }
-	uint64_t line_base = 0, lines_total = 0, valid_total = 0, pass_total = 0;
+	if (sharded && mahip_comm_world(c) > 32) { mahip_set_error("mahip_paf_parse_sharded: at most 32 ranks"); return -1; }
 	if (!b->loaded) { mahip_set_error("mahip_paf_parse: no text loaded"); return -1; }
-	const size_t n = b->nbytes;
-	const unsigned char *text = P<unsigned char>(b->text);
-	unsigned long long *ctr = P<unsigned long long>(c->ctr);
 	memset(info, 0, sizeof(*info));
 	b->n_seq = 0; b->name_bytes = 0;
 	b->parsed = false; b->rep = {}; b->odd_snap.clear();
@@ -1037,350 +1395,35 @@ static int paf_parse_impl(mahip_ctx_t *c, int min_span, int min_match, int bi_di
 		fprintf(stderr, "[T::paf_parse] %-28s %9.3f ms\n", what, ((double)(t1.tv_sec - lap_t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - lap_t0.tv_nsec)) * 1e3);
 		lap_t0 = t1;
 	};
-
-	// ---- line starts
-	CHK(dev_reserve(c, b->scal, 64));
-	CHK(ctr_zero(c));
-	uint32_t L = 0;
-	int open_line = 0;
-	uint32_t n_gran = 0, tile_k = 1, n_tiles = 0;
-	size_t n_eff = n; // the tile parser's text: n + the appended newline
-	if (n) { // same decision as the kernels': L = newlines + an unterminated tail
-		unsigned char last = 0;
-		HIPCHK(hipMemcpyAsync(&last, text + n - 1, 1, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		open_line = last != '\n';
-	}
-	if (n) { // newline census per KiB; the tile parser writes the line starts itself
-		// every line ends with a newline: a text that does not gets one (the buffer has 64 spare bytes; the line start after it is n + 1),
-		// and zeros follow, so that the kernels read whole 16-byte pieces
-		HIPCHK(hipMemsetAsync((void*)(text + n), 0, 64, c->st));
-		if (open_line) HIPCHK(hipMemsetAsync((void*)(text + n), '\n', 1, c->st));
-		n_eff = n + (size_t)open_line;
-		const size_t ng = (n_eff + PAF_GRAN - 1) / PAF_GRAN;
-		if (ng > 0x7ffffff0ull) { mahip_set_error("mahip_paf_parse: text too large"); return -1; }
-		n_gran = (uint32_t)ng;
-		CHK(dev_reserve(c, b->tile, ((size_t)n_gran + 8) * 4)); CHK(dev_reserve(c, b->glast, ((size_t)n_gran + 8) * 4));
-		{
-			ProfScope ps(c, "k_paf_nl_count", (double)n);
-			hipLaunchKernelGGL(k_paf_gran_count, dim3((n_gran + 4 * PAF_GC_PER_WAVE - 1) / (4 * PAF_GC_PER_WAVE)), dim3(256), 0, c->st, text, n_eff, n_gran, P<uint32_t>(b->tile), P<uint32_t>(b->glast));
-		}
-		CHK(scan_exclusive_u32(c, P<uint32_t>(b->tile), P<uint32_t>(b->tile), n_gran, P<uint32_t>(b->tile) + n_gran)); // goff[n_gran] = all newlines
-		uint64_t n_nl = 0;
-		{
-			uint32_t t32 = 0;
-			HIPCHK(hipMemcpyAsync(&t32, P<uint32_t>(b->tile) + n_gran, 4, hipMemcpyDeviceToHost, c->st));
-			HIPCHK(hipStreamSynchronize(c->st));
-			n_nl = t32;
-		}
-		if (n_nl + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse: more than 2^31 lines"); return -1; }
-		L = (uint32_t)n_nl; // (the virtual newline is counted)
-		CHK(dev_reserve(c, b->lstart, ((size_t)L + 4) * 8));
-		if (L) {
-			// tile = K granules with about 240 lines (a lane per line, 256 lanes); at most what a block stages (15 KiB + 1 KiB in front with 16 KiB of LDS text, 31 + 1 with 32)
-			double k = 240.0 * ((double)n / (double)L) / (double)PAF_GRAN;
-			if (const char *e = getenv("MA_PAF_TILE_K")) k = atof(e);
-			tile_k = k < 1.0 ? 1u : k > 31.0 ? 31u : (uint32_t)k;
-			n_tiles = (n_gran + tile_k - 1) / tile_k;
-			const uint32_t n_grp = (n_gran >> PAF_BGRP) + 1;
-			CHK(dev_reserve(c, b->gmax, ((size_t)n_grp + 1) * 8)); CHK(dev_reserve(c, b->tfirst, ((size_t)n_tiles + 1) * 8));
-			hipLaunchKernelGGL(k_paf_gran_bmax, dim3(n_grp), dim3(64), 0, c->st, (const uint32_t*)P<uint32_t>(b->glast), n_gran, P<unsigned long long>(b->gmax));
-			hipLaunchKernelGGL(k_paf_tile_first, dim3(grid_for(n_tiles, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->glast), (const unsigned long long*)P<unsigned long long>(b->gmax), tile_k, n_tiles,
-			                   P<unsigned long long>(b->tfirst));
-		}
-	}
+	PafParse ps;
+	CHK(paf_census(c, b, ps));
 	lap("line census");
-	PafCols o;
-	{
-		const size_t Lr = (size_t)L + 4;
-		CHK(dev_reserve(c, b->flags, Lr));
-		for (int k = 0; k < 8; ++k) CHK(dev_reserve(c, b->num[k], Lr * 4));
-		CHK(dev_reserve(c, b->tnoff, Lr * 4)); CHK(dev_reserve(c, b->qlen, Lr * 4)); CHK(dev_reserve(c, b->tlen, Lr * 4));
-		CHK(dev_reserve(c, b->hq, Lr * 8)); CHK(dev_reserve(c, b->ht, Lr * 8));
-		CHK(dev_reserve(c, b->qslot, Lr * 4)); CHK(dev_reserve(c, b->tslot, Lr * 4));
-		o.flags = P<uint8_t>(b->flags);
-		o.ql = P<uint32_t>(b->num[0]); o.qs = P<uint32_t>(b->num[1]); o.qe = P<uint32_t>(b->num[2]); o.tl = P<uint32_t>(b->num[3]);
-		o.ts = P<uint32_t>(b->num[4]); o.te = P<uint32_t>(b->num[5]); o.ml = P<uint32_t>(b->num[6]); o.bl = P<uint32_t>(b->num[7]);
-		o.tnoff = P<uint32_t>(b->tnoff); o.qlen = P<uint32_t>(b->qlen); o.tlen = P<uint32_t>(b->tlen);
-		o.hq = P<uint64_t>(b->hq); o.ht = P<uint64_t>(b->ht); o.qslot = P<uint32_t>(b->qslot); o.tslot = P<uint32_t>(b->tslot);
-	}
-	size_t n_valid = 0, n_pass = 0, n_nobl = 0, n_long = 0;
-	uint32_t max_qs = 0;
-	if (L) {
-		CHK(dev_reserve(c, c->keep, ((size_t)L + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)L + 16) * 4));
-		lap("columns reserved");
-		{
-			ProfScope ps(c, "k_paf_parse", (double)n + 69.0 * (double)L);
-			TileArgs ta;
-			ta.text = text; ta.n = n_eff; ta.K = tile_k; ta.n_gran = n_gran; ta.n_tiles = n_tiles; ta.L = L;
-			ta.goff = (const uint32_t*)P<uint32_t>(b->tile); ta.first = (const unsigned long long*)P<unsigned long long>(b->tfirst);
-			ta.min_span = min_span; ta.min_match = min_match;
-			const int ch = tile_k <= 15 ? 1 : 2;
-			const uint32_t reg = (uint32_t)ch * 16384u, lds = reg + 32 + 2 * (reg / 16 + 8) * 2 + 260 * 4;
-			uint32_t per_cu = (160u * 1024u) / (lds + 64u); if (per_cu > 8) per_cu = 8; // blocks a CU holds: the grid is what fits the chip, a block works through tiles (one set of counter atomics per block)
-			const unsigned grid = grid_for(n_tiles, 1, 256u * per_cu);
-			rp.tile_form = ch;
-			if (ch == 1) hipLaunchKernelGGL(k_paf_parse_tile<1>, dim3(grid), dim3(256), lds, c->st, ta, o, P<uint64_t>(b->lstart), ctr);
-			else hipLaunchKernelGGL(k_paf_parse_tile<2>, dim3(grid), dim3(256), lds, c->st, ta, o, P<uint64_t>(b->lstart), ctr);
-		}
-		CHK(ctr_fetch(c));
-		rp.n_odd = c->h_ctr[PC_ODD];
-		if (c->paf_keep_odd) { // tests: which lines the tile parser left to the byte-wise routine (the final flags do not say)
-			b->odd_snap.resize(L);
-			HIPCHK(hipMemcpyAsync(b->odd_snap.data(), o.flags, L, hipMemcpyDeviceToHost, c->st));
-			HIPCHK(hipStreamSynchronize(c->st));
-			for (uint8_t &f : b->odd_snap) f = f == PF_ODD;
-		}
-		if (c->h_ctr[PC_ODD]) { // lines the straight-line parser does not cover: the byte-wise routine on them (the counters add up)
-			ProfScope ps(c, "k_paf_parse_odd", 0.0);
-			hipLaunchKernelGGL(k_paf_parse_odd, dim3(grid_for(L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, min_span, min_match, o, ctr);
-			CHK(ctr_fetch(c));
-			rp.odd_ran = 1;
-		}
-		n_valid = (size_t)c->h_ctr[PC_VALID]; n_pass = (size_t)c->h_ctr[PC_PASS]; n_nobl = (size_t)c->h_ctr[PC_NOBL];
-		n_long = (size_t)c->h_ctr[PC_LONG];
-		max_qs = (uint32_t)c->h_ctr[PC_MAXQS];
-		if (n_nobl && !sharded) { // stale bl: rare (PAF writers emit 12+ columns)
-			rp.bl_pass = 1;
-			CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
-			hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
-			CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, nullptr));
-			hipLaunchKernelGGL(k_paf_bl_compact, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)o.bl, L, P<uint32_t>(b->blv));
-			hipLaunchKernelGGL(k_paf_bl_fill, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->blv), L, o.bl);
-		}
-	}
-	rp.n_lines = L; rp.n_gran = n_gran; rp.tile_k = tile_k; rp.n_tiles = n_tiles; rp.open_line = open_line; rp.n_long = n_long;
+	CHK(paf_reserve_cols(c, b, ps));
+	if (ps.L) lap("columns reserved");
+	CHK(paf_fields(c, b, ps, min_span, min_match));
+	if (!sharded && ps.n_nobl) { rp.bl_pass = 1; CHK(paf_stale_bl(c, b, ps, false)); }
+	rp.n_lines = ps.L; rp.n_gran = ps.n_gran; rp.tile_k = ps.tile_k; rp.n_tiles = ps.n_tiles; rp.open_line = ps.open_line; rp.n_long = ps.n_long;
 	lap("fields");
-	uint64_t nobl_total = n_nobl;
-	if (sharded) { // what the ranges have to know of each other before names and records can be numbered
-		uint64_t mine[5] = { L, n_valid, n_pass, n_nobl, max_qs }, all[5 * 32];
-		CHK(mahip_comm_all_gather_u64(c, mine, 5, all));
-		nobl_total = 0;
-		for (int r = 0; r < W; ++r) {
-			if (r < me) line_base += all[5 * r];
-			lines_total += all[5 * r]; valid_total += all[5 * r + 1]; pass_total += all[5 * r + 2]; nobl_total += all[5 * r + 3];
-			if (all[5 * r + 4] > max_qs) max_qs = (uint32_t)all[5 * r + 4];
-		}
-		if (lines_total + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse_sharded: more than 2^31 lines"); return -1; }
-		if (nobl_total) { // somebody has a 10-column line: every range says what `bl` it leaves behind (the bl of its last 11-column line), and a line in front of
-			// a range's first 11-column line inherits from the nearest range before it that has one (paf.c:54: the field is simply not written)
-			uint64_t two[2] = { 0, 0 }, every[2 * 32];
-			uint32_t n_has = 0, last_bl = 0;
-			if (L) {
-				CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
-				hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)o.flags, L, P<uint32_t>(c->keep));
-				CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), L, P<uint32_t>(b->scal)));
-				hipLaunchKernelGGL(k_paf_bl_compact, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)o.bl, L, P<uint32_t>(b->blv));
-				HIPCHK(hipMemcpyAsync(&n_has, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-				HIPCHK(hipStreamSynchronize(c->st));
-				if (n_has) { HIPCHK(hipMemcpyAsync(&last_bl, P<uint32_t>(b->blv) + (n_has - 1), 4, hipMemcpyDeviceToHost, c->st)); HIPCHK(hipStreamSynchronize(c->st)); }
-			}
-			two[0] = n_has ? 1 : 0; two[1] = last_bl;
-			CHK(mahip_comm_all_gather_u64(c, two, 2, every));
-			uint32_t before = 0;
-			for (int r = 0; r < me; ++r) if (every[2 * r]) before = (uint32_t)every[2 * r + 1];
-			if (L && n_nobl) hipLaunchKernelGGL(k_bl_fill_from, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->blv), L, o.bl, before);
-		}
+	if (sharded) {
+		CHK(paf_cross_counts(c, ps));
+		if (ps.nobl_total) CHK(paf_stale_bl(c, b, ps, true));
 	}
-
-	// ---- dictionary: distinct names, ids in order of first appearance
-	uint32_t R = 0, cap_used = 0;
-	int gen_local = 0;
-	if (n_pass) {
-		// The number of distinct names is not known before the pass (<= 2 per stored line; in overlap files a read has tens of lines).  Start with a
-		// table sized for 16 lines per name -- 8x smaller than the safe size, it stays in the last-level cache -- count the names as they go in, and
-		// repeat the pass with a table for 4x that many only if the load factor came out above 1/2 (or a probe sequence ran out)
-		const uint32_t cap_max = pow2_at_least(4 * (uint64_t)n_pass + 65536); // load <= 1/2 whatever the file holds
-		uint32_t cap = pow2_at_least(n_pass / 16 + 65536);
-		if (const char *e = getenv("MA_DICT_CAP_LOG2")) { int l2 = atoi(e); if (l2 >= 4 && l2 <= 31) cap = 1u << l2; } // tests: force the growth path
-		const bool short_names = n_long == 0 && !getenv("MA_DICT_EXACT_TEXT"); // every name is its own key: no text compared (k_dict_insert_short)
-		rp.dict_form = short_names ? MAHIP_PAF_DICT_SHORT : MAHIP_PAF_DICT_TEXT;
-		for (int attempt = 0;; ++attempt) {
-			CHK(dev_reserve(c, b->tab, (size_t)cap * 16)); CHK(dev_reserve(c, b->tmin, (size_t)cap * 4)); CHK(dev_reserve(c, b->slot_id, (size_t)cap * 4));
-			CHK(ctr_zero(c));
-			if (short_names) {
-				HIPCHK(hipMemsetAsync(b->tab.p, 0, (size_t)cap * 16, c->st));
-				ProfScope ps(c, "k_dict_insert", 2.0 * 40.0 * (double)n_pass);
-				hipLaunchKernelGGL(k_dict_insert_short, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, (DSlot*)b->tab.p, cap - 1, ctr);
-			} else {
-				HIPCHK(hipMemsetAsync(b->tab.p, 0xff, (size_t)cap * 16, c->st));
-				ProfScope ps(c, "k_dict_insert", 2.0 * 40.0 * (double)n_pass);
-				hipLaunchKernelGGL(k_dict_insert, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->lstart), L, o, (XSlot*)b->tab.p, cap - 1, ctr);
-			}
-			CHK(ctr_fetch(c));
-			const uint64_t distinct = c->h_ctr[PC_DISTINCT];
-			rp.n_attempts = attempt + 1; rp.cap[attempt] = cap; rp.n_distinct = distinct;
-			rp.end[attempt] = c->h_ctr[PC_OVERFLOW] ? MAHIP_PAF_TAB_PROBES : 2 * distinct > cap ? MAHIP_PAF_TAB_LOAD : MAHIP_PAF_TAB_OK;
-			if (c->h_ctr[PC_OVERFLOW] == 0 && 2 * distinct <= cap) break;
-			if (attempt >= 3 || cap >= cap_max) { if (c->h_ctr[PC_OVERFLOW] == 0) break; mahip_set_error("mahip_paf_parse: name table overflow"); return -1; }
-			uint32_t want = pow2_at_least(4 * distinct + 65536);
-			if (want <= cap) want = cap < 0x10000000u ? cap << 3 : cap_max; // a probe sequence ran out: the count is incomplete
-			cap = want < cap_max ? want : cap_max;
-		}
-		if (short_names) hipLaunchKernelGGL(k_dict_short_tmin, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const DSlot*)b->tab.p, cap, P<uint32_t>(b->tmin));
-		else hipLaunchKernelGGL(k_dict_exact_tmin, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const XSlot*)b->tab.p, cap, P<uint32_t>(b->tmin));
-		if (no_cont) { // hit.c:38-68 + hit.c:86
-			CHK(dev_reserve(c, b->excl, (size_t)cap + 16));
-			HIPCHK(hipMemsetAsync(b->excl.p, 0, cap, c->st));
-			hipLaunchKernelGGL(k_paf_nocont, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, max_hang, int_frac, P<uint8_t>(b->excl));
-			HIPCHK(hipMemsetAsync(b->tmin.p, 0xff, (size_t)cap * 4, c->st));
-			CHK(ctr_zero(c));
-			hipLaunchKernelGGL(k_paf_refilter, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, o, L, (const uint8_t*)P<uint8_t>(b->excl), P<uint32_t>(b->tmin), ctr);
-			hipLaunchKernelGGL(k_excl_count, dim3(grid_for(cap, 256, 2048)), dim3(256), 0, c->st, (const uint8_t*)P<uint8_t>(b->excl), cap, ctr);
-			CHK(ctr_fetch(c));
-			n_pass = (size_t)c->h_ctr[PC_PASS];
-			info->n_excl = (uint32_t)c->h_ctr[PC_VALID];
-		}
-		CHK(dev_reserve(c, c->keep, ((size_t)cap + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)cap + 16) * 4));
-		hipLaunchKernelGGL(k_dict_flag, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->tmin), cap, P<uint32_t>(c->keep));
-		CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), cap, P<uint32_t>(b->scal)));
-		HIPCHK(hipMemcpyAsync(&R, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		for (int k = 0; k < 2; ++k) { CHK(dev_reserve(c, c->key[k], ((size_t)R + 1) * 8)); CHK(dev_reserve(c, c->val[k], ((size_t)R + 1) * 4)); }
-		hipLaunchKernelGGL(k_dict_collect, dim3(grid_for(cap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const uint32_t*)P<uint32_t>(b->tmin), cap,
-		                   P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
-		int gen = 0;
-		cap_used = cap;
-		CHK(radix_sort_pairs(c, R, 0, bits_of(2ull * L), 0, 0, &gen));
-		gen_local = gen;
-		CHK(dev_reserve(c, b->seq_len, ((size_t)R + 4) * 4)); CHK(dev_reserve(c, b->name_off, ((size_t)R + 4) * 8));
-		CHK(dev_reserve(c, b->name_len, ((size_t)R + 4) * 4)); CHK(dev_reserve(c, b->name_pos, ((size_t)R + 4) * 4));
-		hipLaunchKernelGGL(k_dict_assign, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint64_t*)P<uint64_t>(c->key[gen]), (const uint32_t*)P<uint32_t>(c->val[gen]), R,
-		                   (const uint64_t*)P<uint64_t>(b->lstart), o, P<uint32_t>(b->slot_id), P<uint32_t>(b->seq_len), P<uint64_t>(b->name_off), P<uint32_t>(b->name_len), P<uint32_t>(c->keep));
-		uint32_t nb = 0;
-		CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(b->name_pos), R, P<uint32_t>(b->scal)));
-		HIPCHK(hipMemcpyAsync(&nb, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		CHK(dev_reserve(c, b->names, (size_t)nb + 16));
-		hipLaunchKernelGGL(k_dict_names, dim3(grid_for(R, 256)), dim3(256), 0, c->st, text, (const uint64_t*)P<uint64_t>(b->name_off), (const uint32_t*)P<uint32_t>(b->name_len),
-		                   (const uint32_t*)P<uint32_t>(b->name_pos), R, P<char>(b->names));
-		b->name_bytes = nb;
-	}
-	b->n_seq = R;
+	if (ps.n_pass) CHK(paf_dict_local(c, b, ps, no_cont, max_hang, int_frac));
+	b->n_seq = ps.R;
 	lap("dictionary");
-	const uint32_t *slot_to_id = P<uint32_t>(b->slot_id); // table slot -> id, for the records
-	if (sharded) { // ---- the ranks' name tables -> one dictionary (kernels above)
-		const uint32_t R_loc = R;
-		const size_t nb_loc = b->name_bytes;
-		uint64_t mine[2] = { R_loc, nb_loc }, all[2 * 32];
-		CHK(mahip_comm_all_gather_u64(c, mine, 2, all));
-		uint32_t stride_rows = 1, h_rows[32];
-		size_t stride_bytes = 16, sum_rows = 0;
-		for (int r = 0; r < W; ++r) { h_rows[r] = (uint32_t)all[2 * r]; sum_rows += all[2 * r]; if (all[2 * r] > stride_rows) stride_rows = (uint32_t)all[2 * r]; if (all[2 * r + 1] > stride_bytes) stride_bytes = (size_t)all[2 * r + 1]; }
-		stride_bytes = (stride_bytes + 15) & ~(size_t)15;
-		if ((uint64_t)stride_rows * (uint64_t)W >= 0xffffffffull) { mahip_set_error("mahip_paf_parse_sharded: too many names"); return -1; }
-		// my rows and name bytes into exchange buffers, gathered with the stride of the largest range
-		DevBuf rows_all, blobs_all, aux;
-		void *xr = nullptr, *xb = nullptr;
-		CHK(mahip_xbuf(c, 0, (size_t)stride_rows * sizeof(NameRow) + stride_bytes, &xr));
-		xb = (char*)xr + (size_t)stride_rows * sizeof(NameRow);
-		if (R_loc) {
-			hipLaunchKernelGGL(k_name_rows, dim3(grid_for(R_loc, 256)), dim3(256), 0, c->st, (const uint64_t*)P<uint64_t>(c->key[gen_local]), R_loc, (uint32_t)(2 * line_base), (const uint32_t*)P<uint32_t>(b->seq_len),
-			                   (const uint32_t*)P<uint32_t>(b->name_len), (const uint32_t*)P<uint32_t>(b->name_pos), (NameRow*)xr);
-			HIPCHK(hipMemcpyAsync(xb, b->names.p, nb_loc, hipMemcpyDeviceToDevice, c->st));
-		}
-		int rc = 0;
-		do {
-			if ((rc = dev_reserve(c, rows_all, (size_t)W * stride_rows * sizeof(NameRow) + 64)) != 0) break;
-			if ((rc = dev_reserve(c, blobs_all, (size_t)W * stride_bytes + 64)) != 0) break;
-			if ((rc = mahip_comm_all_gather(c, xr, rows_all.p, (size_t)stride_rows * sizeof(NameRow))) != 0) break;
-			if ((rc = mahip_comm_all_gather(c, xb, blobs_all.p, stride_bytes)) != 0) break;
-			// one table for all of them: at most sum_rows distinct names
-			const uint32_t gcap = pow2_at_least(2 * (uint64_t)sum_rows + 1024);
-			const size_t total_rows = (size_t)W * stride_rows;
-			// aux: tab[gcap] u64 | gkey[gcap] u64 | slot_of[total_rows] u32 | gid_of_slot[gcap] u32 | n_rows[32] u32
-			const size_t o_key = (size_t)gcap * 8, o_slot = o_key + (size_t)gcap * 8, o_gid = o_slot + ((total_rows * 4 + 7) & ~(size_t)7), o_n = o_gid + (size_t)gcap * 4;
-			if ((rc = dev_reserve(c, aux, o_n + 32 * 4 + 64)) != 0) break;
-			unsigned long long *gtab = (unsigned long long*)aux.p, *gkey = (unsigned long long*)((char*)aux.p + o_key);
-			uint32_t *slot_of = (uint32_t*)((char*)aux.p + o_slot), *gid_of_slot = (uint32_t*)((char*)aux.p + o_gid), *d_rows = (uint32_t*)((char*)aux.p + o_n);
-			HIPCHK(hipMemsetAsync(aux.p, 0xff, o_slot, c->st));
-			HIPCHK(hipMemcpyAsync(d_rows, h_rows, (size_t)W * 4, hipMemcpyHostToDevice, c->st));
-			CHK(ctr_zero(c));
-			if (sum_rows) hipLaunchKernelGGL(k_dict_merge, dim3(grid_for(total_rows, 256, 8192)), dim3(256), 0, c->st, (const NameRow*)rows_all.p, (const unsigned char*)blobs_all.p, (const uint32_t*)d_rows, W,
-			                                 stride_rows, stride_bytes, gtab, gkey, gcap - 1, slot_of, ctr);
-			CHK(ctr_fetch(c));
-			if (c->h_ctr[PC_OVERFLOW]) { mahip_set_error("mahip_paf_parse_sharded: name table overflow"); rc = -1; break; }
-			// distinct names sorted by first appearance = ids
-			if ((rc = dev_reserve(c, c->keep, ((size_t)gcap + 16) * 4)) != 0 || (rc = dev_reserve(c, c->pos, ((size_t)gcap + 16) * 4)) != 0) break;
-			hipLaunchKernelGGL(k_merge_flag, dim3(grid_for(gcap, 256)), dim3(256), 0, c->st, (const unsigned long long*)gtab, gcap, P<uint32_t>(c->keep));
-			if ((rc = scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), gcap, P<uint32_t>(b->scal))) != 0) break;
-			uint32_t Rg = 0;
-			HIPCHK(hipMemcpyAsync(&Rg, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-			HIPCHK(hipStreamSynchronize(c->st));
-			for (int k = 0; k < 2 && rc == 0; ++k) { rc = dev_reserve(c, c->key[k], ((size_t)Rg + 1) * 8); if (rc == 0) rc = dev_reserve(c, c->val[k], ((size_t)Rg + 1) * 4); }
-			if (rc) break;
-			hipLaunchKernelGGL(k_merge_collect, dim3(grid_for(gcap, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const unsigned long long*)gkey, gcap,
-			                   P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
-			int gen = 0;
-			if ((rc = radix_sort_pairs(c, Rg, 0, bits_of(2ull * lines_total), 0, 0, &gen)) != 0) break;
-			// the map for this rank's records BEFORE the local arrays are overwritten: local slot -> global id (k_merge_map needs the local "slot in use" flags)
-			if (cap_used) {
-				if ((rc = dev_reserve(c, b->excl, (size_t)cap_used * 4 + 16)) != 0) break; // (the -R flag array is free in this mode: the map lives there)
-			}
-			if ((rc = dev_reserve(c, b->seq_len, ((size_t)Rg + 4) * 4)) != 0 || (rc = dev_reserve(c, b->name_off, ((size_t)Rg + 4) * 8)) != 0 ||
-			    (rc = dev_reserve(c, b->name_len, ((size_t)Rg + 4) * 4)) != 0 || (rc = dev_reserve(c, b->name_pos, ((size_t)Rg + 4) * 4)) != 0) break;
-			// keep / pos are about to be reused for the name lengths: the local flags first
-			DevBuf used_local;
-			if (cap_used) {
-				if ((rc = dev_reserve(c, used_local, (size_t)cap_used * 4 + 16)) != 0) break;
-				hipLaunchKernelGGL(k_dict_flag, dim3(grid_for(cap_used, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->tmin), cap_used, (uint32_t*)used_local.p);
-			}
-			if ((rc = dev_reserve(c, c->keep, ((size_t)Rg + 16) * 4)) != 0) { dev_free(c, used_local); break; }
-			if (Rg) hipLaunchKernelGGL(k_merge_assign, dim3(grid_for(Rg, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->val[gen]), Rg, (const unsigned long long*)gtab, (const unsigned long long*)gkey,
-			                           (const NameRow*)rows_all.p, stride_rows, stride_bytes, gid_of_slot, P<uint32_t>(b->seq_len), P<uint64_t>(b->name_off), P<uint32_t>(b->name_len), P<uint32_t>(c->keep));
-			if (cap_used) hipLaunchKernelGGL(k_merge_map, dim3(grid_for(cap_used, 256)), dim3(256), 0, c->st, (const uint32_t*)used_local.p, (const uint32_t*)P<uint32_t>(b->slot_id), cap_used,
-			                                 (const uint32_t*)slot_of, (uint32_t)((size_t)me * stride_rows), (const uint32_t*)gid_of_slot, P<uint32_t>(b->excl));
-			uint32_t nb = 0;
-			if ((rc = scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(b->name_pos), Rg, P<uint32_t>(b->scal))) != 0) { dev_free(c, used_local); break; }
-			HIPCHK(hipMemcpyAsync(&nb, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-			HIPCHK(hipStreamSynchronize(c->st));
-			dev_free(c, used_local);
-			if ((rc = dev_reserve(c, b->names, (size_t)nb + 16)) != 0) break;
-			if (Rg) hipLaunchKernelGGL(k_dict_names, dim3(grid_for(Rg, 256)), dim3(256), 0, c->st, (const unsigned char*)blobs_all.p, (const uint64_t*)P<uint64_t>(b->name_off), (const uint32_t*)P<uint32_t>(b->name_len),
-			                           (const uint32_t*)P<uint32_t>(b->name_pos), Rg, P<char>(b->names));
-			HIPCHK(hipStreamSynchronize(c->st)); // (the gathered blocks are released below)
-			b->name_bytes = nb;
-			R = Rg; b->n_seq = Rg;
-			slot_to_id = (const uint32_t*)P<uint32_t>(b->excl);
-		} while (0);
-		dev_free(c, rows_all); dev_free(c, blobs_all); dev_free(c, aux);
-		if (rc) return -1;
-	}
-
-	// ---- records: hit (+ mirrored hit) per stored line, in line order
-	size_t n_hits = 0;
-	if (n_pass) { // one pass: ids, record slots (chained tiles), records
-		const size_t max_hits = bi_dir ? 2 * n_pass : n_pass;
-		if (max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
-		CHK(dev_reserve(c, c->aos_own, (max_hits + 1) * sizeof(ma_hit_t)));
-		const size_t nb = ((size_t)L + EM_TILE - 1) / EM_TILE;
-		uint32_t *ticket; unsigned long long *state; uint32_t ticket_base, epoch;
-		CHK(scan_chain_begin(c, nb, &state, &ticket, &ticket_base, &epoch));
-		uint32_t nh = 0;
-		{
-			ProfScope ps(c, "k_paf_emit", 37.0 * (double)n_pass + 32.0 * (double)max_hits);
-			hipLaunchKernelGGL(k_paf_emit_chain, dim3((unsigned)nb), dim3(256), 0, c->st, o, slot_to_id, L, bi_dir, (uint4*)c->aos_own.p, P<uint32_t>(b->scal), state, ticket, ticket_base, epoch);
-		}
-		HIPCHK(hipMemcpyAsync(&nh, b->scal.p, 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipStreamSynchronize(c->st));
-		n_hits = nh;
-		lap("records");
-		CHK(mahip_hits_adopt(c, nullptr, n_hits, R)); // resets the per-upload state and sizes the read arrays
-		c->d_aos = (const ma_hit_t*)c->aos_own.p;
-		lap("adopt");
-	} else {
-		CHK(mahip_hits_adopt(c, nullptr, 0, R));
-		CHK(dev_reserve(c, c->aos_own, sizeof(ma_hit_t)));
-		c->d_aos = (const ma_hit_t*)c->aos_own.p;
-	}
+	ps.slot_to_id = P<uint32_t>(b->slot_id);
+	if (sharded) CHK(paf_dict_merged(c, b, ps));
+	if (ps.n_pass) { CHK(paf_records(c, b, ps, bi_dir)); lap("records"); }
+	CHK(paf_adopt(c, ps));
+	if (ps.n_pass) lap("adopt");
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(c->st));
-	c->hint_max_qs = c->paf_max_qs = max_qs;
-	rp.n_excl = info->n_excl;
+	c->hint_max_qs = c->paf_max_qs = ps.max_qs;
+	rp.n_excl = info->n_excl = ps.n_excl;
 	b->parsed = true;
 	c->run_stride = sharded ? 0 : bi_dir ? 2 : 1; // k_paf_emit_chain wrote a line's record and its mirror side by side (hit.c:87-98): the sort may take RUNS of records (hits.hip)
-	info->n_records = n_valid; info->n_stored_lines = n_pass; info->n_hits = n_hits; info->n_seq = R; info->max_qs = max_qs; info->name_bytes = b->name_bytes; info->n_lines = L;
-	if (sharded) { info->n_records = valid_total; info->n_stored_lines = pass_total; info->n_lines = lines_total; }
+	info->n_records = ps.n_valid; info->n_stored_lines = ps.n_pass; info->n_hits = ps.n_hits; info->n_seq = ps.R; info->max_qs = ps.max_qs; info->name_bytes = b->name_bytes; info->n_lines = ps.L;
+	if (sharded) { info->n_records = ps.valid_total; info->n_stored_lines = ps.pass_total; info->n_lines = ps.lines_total; }
 	return 0;
 }
 

@@ -429,7 +429,6 @@ __global__ __launch_bounds__(256) void k_perm_patch(const uint32_t *__restrict__
 	for (uint32_t j = o0 + threadIdx.x; j < o1; j += 256) perm[p + (j - o0)] = ord[j];
 }
 
-static int bitlen64(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
 
 // The walk's arrays (c->hwalk, c->hdig) stay with the context between the hit walk and the arc walk that follows it and are dropped by a thread of their
 // own when the repair is over (walk_scratch_release): unmapping 9 GB took 0.5 s of the 5.8 s of BASELINE configs[4], 60 ms of the 1.1 s of the 50 M-overlap
@@ -483,7 +482,7 @@ int reference_order(mahip_ctx *c, uint64_t *d_keys, size_t n, uint32_t *d_perm, 
 	HIPCHK(hipMemsetAsync(ctr + CT_MAXQID, 0, 16, c->st)); // (CT_MAXQID, CT_MAXQS: adjacent)
 	hipLaunchKernelGGL(k_key_bounds, dim3(grid_for(n, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint64_t*)d_keys, n, ctr);
 	CHK(ctr_fetch(c));
-	int bh = bitlen64(c->h_ctr[CT_MAXQID]), bl = bitlen64(c->h_ctr[CT_MAXQS]), bi = bitlen64(n - 1), shift_top = -1;
+	int bh = bitlen_u64(c->h_ctr[CT_MAXQID]), bl = bitlen_u64(c->h_ctr[CT_MAXQS]), bi = bitlen_u64(n - 1), shift_top = -1;
 	if (bh == 0) bh = 1;
 	if (bl == 0) bl = 1;
 	if (bi == 0) bi = 1;

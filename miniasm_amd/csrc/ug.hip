@@ -94,7 +94,6 @@ __global__ __launch_bounds__(256) void k_ug_arc_emit(ug_t a, size_t n, const uin
 	if (e < n && keep[e]) { uint32_t o[4]; ugk_arc_emit(&a, e, o); *(uint4*)(out + pos[e]) = make_uint4(o[0], o[1], o[2], o[3]); }
 }
 
-static int bitlen32(uint32_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }
 
 static ug_rank_t rank_bufs(UgBufs *b, int g)
 {
@@ -110,7 +109,7 @@ static int ug_rank(mahip_ctx *c, UgBufs *b, const ug_t &a, int *gen_out)
 	const uint32_t V = a.n_vtx;
 	int g = 0;
 	hipLaunchKernelGGL(k_ug_jump_init, dim3(grid_for(V, 256)), dim3(256), 0, c->st, a, rank_bufs(b, 0));
-	for (int k = bitlen32(V) + 1; k > 0; --k, g ^= 1)
+	for (int k = bitlen_u64(V) + 1; k > 0; --k, g ^= 1)
 		hipLaunchKernelGGL(k_ug_jump, dim3(grid_for(V, 256)), dim3(256), 0, c->st, V, rank_bufs(b, g), rank_bufs(b, g ^ 1));
 	*gen_out = g;
 	return 0;

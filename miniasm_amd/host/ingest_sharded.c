@@ -5,7 +5,7 @@
  * host's page cache, N full parses -- the command's end-to-end time could not shrink with N.  Here rank g reads the bytes [g S/N, (g+1) S/N), cut at
  * line starts (a rank's range begins behind the first newline at or after its nominal start; the line that straddles a border belongs to the rank
  * it starts in), parses them on its GPU, and the ranks exchange only what the reference's sequential reader carries across a border
- * (csrc/paf.hip: paf_parse_impl, sharded): line counts, the inherited `bl` of 10-column lines, the distinct names of each range with their first
+ * (csrc/paf.hip: paf_cross_counts, paf_stale_bl, paf_dict_merged): line counts, the inherited `bl` of 10-column lines, the distinct names of each range with their first
  * appearances -- merged into one dictionary, the reference's ids, on every rank.  The records then travel to the ranks that own their query reads
  * in one personalised exchange (csrc/hits.hip: mahip_hits_route), each with its position in the input's record sequence, and the sharded head
  * (sharded.c) runs on ranks that hold their own records only.  Plain files only (a byte range of a gzip stream is not a text range); -R needs

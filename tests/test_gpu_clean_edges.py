@@ -549,7 +549,7 @@ CHAIN_LENGTHS = (2, 3) + tuple(2 ** k + d for k in range(5, 18) for d in (-1, 0,
 
 @pytest.mark.parametrize("L_", CHAIN_LENGTHS)
 def test_one_chain_or_ring_that_is_the_whole_graph(L_, gpu_ctx, tmpdir_s):
-    """pointer jumping runs bitlen32(V) + 1 rounds: the whole vertex set in ONE chain (V == 2L), lengths on both sides of every power of two"""
+    """pointer jumping runs bitlen_u64(V) + 1 rounds: the whole vertex set in ONE chain (V == 2L), lengths on both sides of every power of two"""
     _ug_argtypes()
     small = L_ <= 4097
     for ring in (False, True):

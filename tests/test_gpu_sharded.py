@@ -174,6 +174,176 @@ def test_every_rank_ingests_its_own_byte_range(world, tmpdir_s):
     assert gz.returncode == 0 and gz.stdout == ref
 
 
+# ---- the byte-range ingest at its edges: hand-made texts whose lines are padded to one length, so that the [g S/N, (g+1) S/N) cut puts chosen lines on chosen ranks
+_EDGE_READS, _EDGE_LEN, _EDGE_STEP = 12, 10000, 2000
+_EDGE_POISON = 999999  # a `bl` under which ma_hit_sub drops the hit (hit.c:125: ml < bl * min_iden); the lines that inherit it are dropped with it
+
+
+def _edge_chain():
+    """twelve reads of 10 kb every 2 kb, every overlap of at least 2 kb once, grouped by query: 38 lines on which the reference writes one unitig of six reads"""
+    out = []
+    for i in range(_EDGE_READS):
+        for j in range(i + 1, _EDGE_READS):
+            d = _EDGE_STEP * (j - i)
+            if _EDGE_LEN - d < 2000:
+                break
+            out.append(dict(q="r%02d" % i, ql=_EDGE_LEN, qs=d, qe=_EDGE_LEN, t="r%02d" % j, tl=_EDGE_LEN, ts=0, te=_EDGE_LEN - d, ml=_EDGE_LEN - d, bl=_EDGE_LEN - d))
+    return out
+
+
+def _edge_unstored(k):
+    """a valid line that is not stored (spans below min_span), with names no other line has"""
+    return dict(q="u%02d" % k, ql=_EDGE_LEN, qs=0, qe=1000, t="v%02d" % k, tl=_EDGE_LEN, ts=0, te=1000, ml=900, bl=1000)
+
+
+def _edge_text(recs, width):
+    """every record as a line of exactly `width` bytes (newline included).  bl=None: a 10-column line, padded with leading zeros in its numbers (at most 8 digits each:
+    the tile parser's own form); otherwise 12 columns and a tag column that takes the padding"""
+    lines = []
+    for r in recs:
+        num = ["%05d" % r[k] for k in ("ql", "qs", "qe", "tl", "ts", "te", "ml")]
+        def cols():
+            return [r["q"], num[0], num[1], num[2], "+", r["t"], num[3], num[4], num[5], num[6]]
+        if r["bl"] is None:
+            k = 0
+            while len("\t".join(cols())) + 1 < width:
+                assert any(len(x) < 8 for x in num), "width too large for a 10-column line"
+                if len(num[k % 7]) < 8:
+                    num[k % 7] = "0" + num[k % 7]
+                k += 1
+            ln = "\t".join(cols())
+        else:
+            ln = "\t".join(cols() + ["%d" % r["bl"], "255"])
+            if len(ln) + 1 < width:
+                assert len(ln) + 1 + 6 <= width, "width too small for the tag column"
+                ln += "\tpd:Z:" + "x" * (width - len(ln) - 7)
+        assert len(ln) + 1 == width, (len(ln) + 1, width, ln)
+        lines.append(ln.encode() + b"\n")
+    return lines
+
+
+def _edge_split(lines, world):
+    """the line ranges of the ranks (host/ingest_sharded.c: a range begins at the first line start at or behind its nominal start): [(first line, end line, first byte, end byte)]"""
+    starts = [0]
+    for ln in lines:
+        starts.append(starts[-1] + len(ln))
+    size = starts[-1]
+    def cut(g):
+        at = size * g // world
+        return next(k for k, s in enumerate(starts) if s >= at) if g < world else len(lines)
+    return [(cut(g), cut(g + 1), starts[cut(g)], starts[cut(g + 1)]) for g in range(world)]
+
+
+def _edge_cases():
+    """name -> (records, width, worlds, check(records, ranges of line numbers) that the text is the case it claims to be)"""
+    chain = _edge_chain()
+    assert len(chain) == 38
+    cases = {}
+    def names(recs):
+        return {r["q"] for r in recs} | {r["t"] for r in recs}
+    def stored(r):
+        return r["qe"] - r["qs"] >= 2000 and r["te"] - r["ts"] >= 2000 and r["ml"] >= 100
+    def with_bl(recs, has, poison=()):
+        return [dict(r, bl=(_EDGE_POISON if k in poison else r["bl"]) if has(k) else None) for k, r in enumerate(recs)]
+
+    # more ranks than lines: some ranks get an empty range (L == 0, no local names, no local table)
+    def chk(recs, rg):
+        assert sum(1 for a, b in rg if a == b) == len(rg) - 2 and all(b - a <= 1 for a, b in rg)
+    cases["more_ranks_than_lines"] = (chain[:2], 72, (3, 5), chk)
+
+    # a range whose lines are all below min_span between two ranges with names: L > 0, n_pass == 0, R_loc == 0
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38), (38, 57)] and not any(stored(r) for r in recs[19:38]) and all(stored(r) for r in recs[:19] + recs[38:])
+    cases["range_without_names"] = (chain[:19] + [_edge_unstored(k) for k in range(19)] + chain[19:], 72, (3,), chk)
+
+    # stale bl.  Only the first range has 11-column lines, and the last of them leaves a bl behind under which every line of the second range is dropped
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38)] and all(r["bl"] is not None for r in recs[:19]) and all(r["bl"] is None for r in recs[19:]) and recs[18]["bl"] == _EDGE_POISON
+    cases["bl_first_range_only"] = (with_bl(chain, lambda k: k < 19, poison=(18,)), 72, (2,), chk)
+    # only the last range has them: the first inherits 0
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38)] and all(r["bl"] is None for r in recs[:19]) and all(r["bl"] is not None for r in recs[19:])
+    cases["bl_last_range_only"] = (with_bl(chain, lambda k: k >= 19), 72, (2,), chk)
+    # three ranks, the middle range has none: the third range's lines in front of its first 11-column line inherit the first range's last bl ACROSS the second
+    def chk(recs, rg):
+        assert rg == [(0, 13), (13, 26), (26, 38)] and recs[12]["bl"] == _EDGE_POISON and all(r["bl"] is None for r in recs[13:30]) and recs[30]["bl"] == recs[30]["ml"]
+        assert all(r["bl"] is None for r in recs[31:])
+    cases["bl_middle_range_has_none"] = (with_bl(chain, lambda k: k < 13 or k == 30, poison=(12,)), 72, (3,), chk)
+    # no range has any: every rank takes part in the exchange, nobody has anything to say
+    def chk(recs, rg):
+        assert all(r["bl"] is None for r in recs) and len(rg) in (2, 3)
+    cases["bl_nowhere"] = (with_bl(chain, lambda k: False), 72, (2, 3), chk)
+
+    # a name first seen as a TARGET in the first range with one length, then as a query in the second with another: the first length wins
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38)]
+        first = next(k for k, r in enumerate(recs) if "r05" in (r["q"], r["t"]))
+        assert first < 19 and recs[first]["t"] == "r05" and recs[first]["tl"] == _EDGE_LEN
+        assert all(r["q"] != "r05" for r in recs[:19]) and [r["ql"] for r in recs[19:] if r["q"] == "r05"] == [12000] * 4
+    cases["name_crosses_a_border"] = ([dict(r, ql=12000) if r["q"] == "r05" else r for r in chain], 72, (2,), chk)
+
+    # one range with names of 1..8 bytes only, the other with a name of 13: the ranks choose different local dictionary forms and the merge compares bytes
+    long_name = "r11_long_name"
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38)] and all(1 <= len(x) <= 8 for x in names(recs[:19])) and long_name in names(recs[19:]) and len(names(recs[:19]) & names(recs[19:])) >= 4
+    cases["mixed_name_lengths"] = ([dict(r, t=long_name) if r["t"] == "r11" else r for r in chain], 80, (2,), chk)
+
+    # every name in every range: the gathered rows are W times the distinct names
+    def chk(recs, rg):
+        assert rg == [(0, 19), (19, 38)] and names(recs[:19]) == names(recs[19:]) == names(recs) and len(names(recs)) == _EDGE_READS
+    cases["every_name_in_every_range"] = (chain[0::2] + chain[1::2], 72, (2,), chk)
+
+    # nothing stored anywhere
+    def chk(recs, rg):
+        assert not any(stored(r) for r in recs) and all(b > a for a, b in rg)
+    cases["nothing_stored"] = ([_edge_unstored(k) for k in range(6)], 72, (2, 3), chk)
+    return cases
+
+
+# cases on which the right answer is an empty GFA: too few lines, or (the two bl cases) so many lines dropped under the inherited bl that nothing assembles --
+# a rank that inherited 0 instead would keep its lines and write a unitig
+_EDGE_EMPTY_GFA = ("more_ranks_than_lines", "nothing_stored", "bl_first_range_only", "bl_middle_range_has_none")
+
+
+@pytest.mark.parametrize("case", sorted(_edge_cases()))
+def test_byte_range_ingest_at_its_edges(case, tmpdir_s):
+    """`MA_GPUS=N miniasm text.paf` on hand-made texts of at most 57 lines that put the edges of the sharded reader (csrc/paf.hip: the cross-range counts, the stale bl
+    across ranges, the merged dictionary) on chosen ranks: empty ranges, a range without names, 11-column lines in the first / the last / not the middle / no range, a
+    name that crosses a border with two lengths, ranges that choose different local dictionary forms, every name in every range, nothing stored.  stdout and the
+    reader's own summary (records read, hits stored, names, total length) equal the one-rank run's and, when it is built, the reference binary's; the `rank g of N:
+    bytes [a, b)` lines on stderr must show the split the case was built for."""
+    import re
+    import subprocess
+    recs, width, worlds, check = _edge_cases()[case]
+    lines = _edge_text(recs, width)
+    paf = os.path.join(tmpdir_s, "edge_%s.paf" % case)
+    with open(paf, "wb") as fo:
+        fo.write(b"".join(lines))
+    size = os.path.getsize(paf)
+    summary = lambda err: re.findall(r"read (\d+) hits; stored (\d+) hits and (\d+) sequences \((\d+) bp\)", err)
+    env1 = dict(os.environ)
+    env1.pop("MA_GPUS", None)
+    r1 = subprocess.run([ma.CLI_PATH, paf], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env1, timeout=120)
+    assert r1.returncode == 0, r1.stderr.decode()[-2000:]
+    one, one_sum = r1.stdout, summary(r1.stderr.decode())
+    assert len(one_sum) == 1
+    assert (b"\na\t" in b"\n" + one) == (case not in _EDGE_EMPTY_GFA), "the case is built to assemble (or not): it would no longer test what it says"
+    if R.have_ref():
+        ref, ref_err = R.run_cli(R.REF_BIN, [], paf)
+        assert one == ref and one_sum == summary(ref_err), "one rank differs from the reference"
+    for world in worlds:
+        split = _edge_split(lines, world)
+        check(recs, [(a, b) for a, b, _, _ in split])
+        env = dict(os.environ, MA_GPUS=str(world), MA_COMM="shm", MA_PIPE_TIMING="1")
+        r = subprocess.run([ma.CLI_PATH, paf], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=120)
+        err = r.stderr.decode()
+        assert r.returncode == 0, err[-2000:]
+        spans = sorted((int(g), int(a), int(b)) for g, a, b in re.findall(r"rank (\d+) of %d: bytes \[(\d+), (\d+)\) of %d;" % (world, size), err))
+        assert spans == [(g, a, b) for g, (_, _, a, b) in enumerate(split)], "the ranks did not get the lines the case puts on them: %r" % spans
+        assert r.stdout == one, "%d ranks: GFA differs from the one-rank run's" % world
+        assert summary(err) == one_sum, "%d ranks: %r, one rank: %r" % (world, summary(err), one_sum)
+
+
 @pytest.mark.parametrize("who", ["one_gpu", "child", "parent"])
 def test_cli_on_n_ranks_never_leaves_a_rank_waiting(who, tmpdir_s):
     """no rank is ever left waiting: a request the sharded head does not serve (hit dumps, early -S stages, -1 / -2) is decided before the ranks
