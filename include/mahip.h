@@ -313,6 +313,47 @@ enum { MAHIP_USEQ_HOST = 1, MAHIP_USEQ_DEVICE = 2 };
 typedef struct { int reader, reason, format; uint64_t n_records, n_matched, n_dup, n_short; } mahip_useq_info_t;
 void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in);
 int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out);
+/* ---- bgzip-compressed (BGZF) input inflated on the device (csrc/xfer.hip: k_bgzf_inflate, csrc/inflate_core.h; the member walk: host/ingest_gpu.c).
+ * A BGZF file is a chain of gzip members of at most 64 KiB of text each, every one with its compressed size in a `BC` extra subfield and its inflated size in
+ * its trailer: the host walks the chain once (one small read per member) into a table -- where each member's deflate bytes lie, its CRC and ISIZE, and where
+ * its text goes (out_off: a 64-bit exclusive prefix sum of ISIZE, the text of a big overlap file exceeds 4 GiB) -- the compressed file goes to HBM as it is, one
+ * wave inflates one member into its slice of the text buffer, and a second pass checks every member's CRC-32.  Afterwards the text lies where
+ * mahip_paf_load_fd / mahip_fastx_load_fd would have put it.  Everything that keeps the device from doing this comes back as a `reason`, which is not an error:
+ * nothing is loaded then and the caller inflates with zlib, as it does for plain gzip and stdin.
+ *   the walk's refusals  NOT_BGZF: the first member is not a BGZF member (plain gzip: no extra field, or none with `BC`); NO_BC: a later member without `BC`;
+ *                        PAST_END: a member (or its header) runs past the end of the file, or is too short for its header and trailer; TRAILING: bytes behind the
+ *                        chain that do not begin a gzip member; BAD_FLG: a header flag that adds a field the walk does not skip (FNAME, FCOMMENT, FHCRC, reserved);
+ *                        ISIZE: a member claims more than 65536 bytes of text
+ *   the kernel's statuses (of the first member that has one; csrc/inflate_core.h)  BAD_BTYPE: block type 3; STORED_LEN: LEN != ~NLEN; BAD_LENGTHS: over-subscribed
+ *                        or otherwise invalid code lengths; BAD_SYMBOL; DIST_TOO_FAR: a distance reaches in front of the member's own output; OUT_OVERFLOW: more
+ *                        output than ISIZE; IN_EXHAUSTED: the deflate bytes end early; OUT_SHORT: less output than ISIZE; CRC: the text's CRC-32 is not the trailer's
+ *   NOMEM: no device memory for the compressed bytes, the table or (target NONE, FASTX) the text; NOT_SEEKABLE: not a regular file; FORCED: MA_BGZF_HOST is set;
+ *   EMPTY: target FASTX and no text at all (the reads-file reader has nothing to index, as for an empty plain file) */
+enum { MAHIP_BGZF_OK = 0, MAHIP_BGZF_NOT_BGZF, MAHIP_BGZF_NO_BC, MAHIP_BGZF_PAST_END, MAHIP_BGZF_TRAILING, MAHIP_BGZF_BAD_FLG, MAHIP_BGZF_ISIZE,
+       MAHIP_BGZF_BAD_BTYPE, MAHIP_BGZF_STORED_LEN, MAHIP_BGZF_BAD_LENGTHS, MAHIP_BGZF_BAD_SYMBOL, MAHIP_BGZF_DIST_TOO_FAR, MAHIP_BGZF_OUT_OVERFLOW, MAHIP_BGZF_IN_EXHAUSTED,
+       MAHIP_BGZF_OUT_SHORT, MAHIP_BGZF_CRC, MAHIP_BGZF_NOMEM, MAHIP_BGZF_NOT_SEEKABLE, MAHIP_BGZF_FORCED, MAHIP_BGZF_EMPTY };
+enum { MAHIP_BGZF_HOST = 1, MAHIP_BGZF_DEVICE = 2 };
+enum { MAHIP_BGZF_PAF = 1, MAHIP_BGZF_FASTX = 2 }; /* target: whose text buffer the members are inflated into */
+typedef struct {
+	uint64_t n_members, n_empty;           /* members of the chain; those with ISIZE == 0 (the end-of-file marker is one) */
+	uint64_t n_stored, n_fixed, n_dynamic; /* deflate blocks by type, over all members (counted by the kernel: 0 when it did not run) */
+	uint64_t comp_bytes, text_bytes;       /* the file; the sum of ISIZE */
+	int reader, reason;                    /* MAHIP_BGZF_DEVICE <=> reason == MAHIP_BGZF_OK */
+	int64_t first_bad_member;              /* the member the reason is about (walk: where it stopped; kernel: the first member with a status), else -1 */
+	double laps_ms[4];                     /* walk, upload, inflate, CRC */
+} mahip_bgzf_info_t;
+/* one row of the block table (host/ingest_gpu.c: ma_bgzf_walk makes it, the kernels read it) */
+typedef struct { uint64_t in_off, out_off; uint32_t in_len, isize, crc, pad; } mahip_bgzf_member_t;
+/* 0 with info->reason == MAHIP_BGZF_OK: the context is in the state mahip_paf_load_fd (target PAF: the same reservation, the same padding, MA_PAF_MAX_BYTES
+ * applies to the inflated size) or mahip_fastx_load_fd (target FASTX) leaves, the compressed bytes and the table are back in the pool.  0 with another reason:
+ * nothing is loaded, take the host road.  -1: a real error (a read error, a HIP error, what mahip_paf_load_fd itself fails on). */
+int mahip_bgzf_load_fd(mahip_ctx_t *c, int fd, size_t nbytes, int target, mahip_bgzf_info_t *info);
+int mahip_bgzf_load_mem(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, mahip_bgzf_info_t *info);
+/* for stage tests: a BGZF image in host memory -> its text in host memory (out_cap >= info->text_bytes, else -1); nothing stays loaded */
+int mahip_bgzf_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, void *out, size_t out_cap, mahip_bgzf_info_t *info);
+int mahip_bgzf_last(mahip_ctx_t *c, mahip_bgzf_info_t *out); /* what the context's last BGZF load (or mahip_bgzf_note) decided */
+void mahip_bgzf_note(mahip_ctx_t *c, const mahip_bgzf_info_t *in); /* a caller that did not get as far as a load (MA_BGZF_HOST) says so */
+const char *mahip_bgzf_reason_name(int reason);
 uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
 /* how many device-wide scans (csrc/scan.hip) of this context, since it was created, took each form: one tile (k_scan_down alone, n <= 2048), the chained
  * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */

@@ -89,6 +89,24 @@ FASTX_FORMATS = {0: None, 1: "fasta", 2: "fastq"}
 USEQ_READERS = {0: None, 1: "host", 2: "device"}
 
 
+class BgzfInfo(C.Structure):  # include/mahip.h: mahip_bgzf_info_t
+    _fields_ = [("n_members", C.c_uint64), ("n_empty", C.c_uint64), ("n_stored", C.c_uint64), ("n_fixed", C.c_uint64), ("n_dynamic", C.c_uint64),
+                ("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("reader", C.c_int), ("reason", C.c_int), ("first_bad_member", C.c_int64),
+                ("laps_ms", C.c_double * 4)]
+
+
+# include/mahip.h: MAHIP_BGZF_* reasons, readers, targets
+BGZF_REASONS = ["OK", "NOT_BGZF", "NO_BC", "PAST_END", "TRAILING", "BAD_FLG", "ISIZE", "BAD_BTYPE", "STORED_LEN", "BAD_LENGTHS", "BAD_SYMBOL", "DIST_TOO_FAR", "OUT_OVERFLOW",
+                "IN_EXHAUSTED", "OUT_SHORT", "CRC", "NOMEM", "NOT_SEEKABLE", "FORCED", "EMPTY"]
+BGZF_READERS = {0: None, 1: "host", 2: "device"}
+BGZF_TARGETS = {"paf": 1, "fastx": 2}
+
+
+def _bgzf_dict(b):
+    return dict(n_members=b.n_members, n_empty=b.n_empty, n_stored=b.n_stored, n_fixed=b.n_fixed, n_dynamic=b.n_dynamic, comp_bytes=b.comp_bytes, text_bytes=b.text_bytes,
+                reader=BGZF_READERS[b.reader], reason=BGZF_REASONS[b.reason], first_bad_member=b.first_bad_member, laps_ms=dict(zip(("walk", "upload", "inflate", "crc"), b.laps_ms)))
+
+
 class PafInfo(C.Structure):  # include/mahip.h: mahip_paf_info_t
     _fields_ = [("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("n_stored_lines", C.c_uint64), ("n_hits", C.c_uint64), ("name_bytes", C.c_uint64),
                 ("n_seq", C.c_uint32), ("max_qs", C.c_uint32), ("n_excl", C.c_uint32)]
@@ -196,6 +214,12 @@ def lib():
         L.mahip_useq_end.argtypes = [vp, vp]
         L.mahip_useq_place_text.argtypes = [vp, vp, sz, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
         L.mahip_useq_last.argtypes = [vp, C.POINTER(UseqInfo)]
+        L.mahip_bgzf_load_fd.argtypes = [vp, i32, sz, i32, C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_load_mem.argtypes = [vp, vp, sz, i32, C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_inflate_mem.argtypes = [vp, vp, sz, vp, sz, C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_last.argtypes = [vp, C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_reason_name.restype = C.c_char_p
+        L.mahip_bgzf_reason_name.argtypes = [i32]
         L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
         L.mahip_scan_forms.restype = None
         L.ma_opt_init.argtypes = [C.POINTER(MaOpt)]
@@ -428,6 +452,28 @@ class Ctx:
         u = UseqInfo()
         _chk(lib().mahip_useq_last(self.h, C.byref(u)), "useq_last")
         return dict(reader=USEQ_READERS[u.reader], reason=FASTX_REASONS[u.reason], format=FASTX_FORMATS[u.format], n_records=u.n_records, n_matched=u.n_matched, n_dup=u.n_dup, n_short=u.n_short)
+
+    # ---- bgzip-compressed input inflated on the device (csrc/xfer.hip, csrc/inflate_core.h)
+    def bgzf_inflate(self, comp, out_cap=None):
+        """a BGZF image (bytes) -> (text, info dict); text is None when the device refused it (info["reason"] says why) -- nothing stays loaded either way"""
+        bi = BgzfInfo()
+        cap = out_cap if out_cap is not None else 65536 * (len(comp) // 28 + 1)  # a member is at least 28 bytes and holds at most 64 KiB
+        out = C.create_string_buffer(max(cap, 1))
+        _chk(lib().mahip_bgzf_inflate_mem(self.h, comp, len(comp), out, cap, C.byref(bi)), "bgzf_inflate_mem")
+        info = _bgzf_dict(bi)
+        return (out.raw[:bi.text_bytes] if info["reason"] == "OK" else None), info
+
+    def bgzf_load(self, comp, target="paf"):
+        """a BGZF image into the text buffer of the PAF reader or of the reads-file reader, as mahip_paf_load_mem / mahip_fastx_load_mem leave it -> info dict"""
+        bi = BgzfInfo()
+        _chk(lib().mahip_bgzf_load_mem(self.h, comp, len(comp), BGZF_TARGETS[target], C.byref(bi)), "bgzf_load_mem")
+        return _bgzf_dict(bi)
+
+    def bgzf_last(self):
+        """what the context's last BGZF load decided"""
+        bi = BgzfInfo()
+        _chk(lib().mahip_bgzf_last(self.h, C.byref(bi)), "bgzf_last")
+        return _bgzf_dict(bi)
 
     def scan_forms(self):
         """device-wide scans of this context so far by form: (one tile, chained, three-phase)"""

@@ -126,6 +126,7 @@ struct mahip_ctx {
 	void *xfer = nullptr;      // staged-copy worker pool (xfer.hip)
 	void *paf = nullptr;       // text-ingest buffers (paf.hip)
 	bool paf_keep_odd = false; // mahip_paf_keep_odd: the next parses keep a host snapshot of the lines left to the byte-wise parser (tests)
+	mahip_bgzf_info_t bgzf_last = {}; // what the last BGZF load decided (xfer.hip: mahip_bgzf_last)
 
 	hipEvent_t mark_ev[64] = {}; // phase marks (mahip_mark)
 	hipStream_t sub_side[2] = {}; hipEvent_t sub_ev[3] = {}; // side streams of the coverage passes' size classes (hits.hip: SubFork)
@@ -220,6 +221,12 @@ void xfer_pool_free(mahip_ctx *c);
 int xfer_from_fd(mahip_ctx *c, void *dev_ptr, int fd, size_t bytes);
 int xfer_from_fd_at(mahip_ctx *c, void *dev_ptr, int fd, size_t off, size_t bytes);
 void paf_free(mahip_ctx *c);
+// the text buffers of the two readers, for a loader that fills them on the device (xfer.hip: the BGZF road): reserve as mahip_paf_load_fd / mahip_fastx_load_fd
+// do (same padding, same caps), then say that the text is there
+int paf_text_reserve(mahip_ctx *c, size_t nbytes, void **d_text);
+void paf_text_loaded(mahip_ctx *c);
+int fx_text_reserve(mahip_ctx *c, size_t nbytes, void **d_text);
+void fx_text_loaded(mahip_ctx *c);
 void clean_free(mahip_ctx *c);
 void ug_free(mahip_ctx *c);
 void useq_free(mahip_ctx *c);

@@ -957,6 +957,9 @@ static int paf_reserve_text(mahip_ctx *c, size_t nbytes)
 	return 0;
 }
 
+int paf_text_reserve(mahip_ctx *c, size_t nbytes, void **d_text) { CHK(paf_reserve_text(c, nbytes)); *d_text = paf_of(c)->text.p; return 0; }
+void paf_text_loaded(mahip_ctx *c) { paf_of(c)->loaded = true; }
+
 extern "C" int mahip_paf_load_mem(mahip_ctx_t *c, const void *text, size_t nbytes)
 {
 	HIPCHK(hipSetDevice(c->dev));

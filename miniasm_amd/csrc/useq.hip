@@ -327,6 +327,8 @@ static int fx_reserve_text(mahip_ctx *c, size_t nbytes)
 	b->fx_n = nbytes;
 	return 0;
 }
+int fx_text_reserve(mahip_ctx *c, size_t nbytes, void **d_text) { CHK(fx_reserve_text(c, nbytes)); *d_text = useq_bufs(c)->fx_text.p; return 0; }
+void fx_text_loaded(mahip_ctx *c) { useq_bufs(c)->fx_loaded = true; }
 extern "C" int mahip_fastx_load_mem(mahip_ctx_t *c, const void *text, size_t nbytes)
 {
 	HIPCHK(hipSetDevice(c->dev));

@@ -1,8 +1,8 @@
 /* ingest_gpu.c -- the text part of ma_hit_read (reference hit.c:70-101, paf.c, sdict.c) on the device.
  *
  * The host only moves bytes: a plain file goes from the page cache straight into pinned staging slots and on to
- * HBM (mahip_paf_load_fd); gzip / stdin input is inflated into memory first (zlib, as the reference does through
- * gzread) and uploaded.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
+ * HBM (mahip_paf_load_fd); a bgzip-compressed (BGZF) file goes to HBM as it is and is inflated there, one wave per block (mahip_bgzf_load_fd; the walk over
+ * its member chain is below); plain gzip / stdin input is inflated into memory first (zlib, as the reference does through gzread) and uploaded.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
  * first-appearance ids and the (mirrored) hit records are all produced by csrc/paf.hip; what comes back is the
  * dictionary (names + first-seen lengths, R entries) and, only for the per-symbol ABI, the records.
  * The -R pre-filter (ma_hit_no_cont, hit.c:38-68) rides in the same parse: the exclusion is a flag per name.
@@ -35,6 +35,98 @@ static char *slurp_gz(gzFile fp, size_t *len)
 	}
 	*len = n;
 	return buf;
+}
+
+/* ---- BGZF: the member chain of a bgzip-compressed file -> the block table of include/mahip.h (RFC 1952 + the BGZF convention of the SAM specification).
+ * The walk is a dependent chain: a member's size stands in its own header.  One read of BG_READ bytes at a member's last 8 bytes yields its trailer (CRC32,
+ * ISIZE) AND the next member's header, so the chain costs one small read per member.  src: an open regular file (fd >= 0) or an image in memory. */
+#define BG_READ 96
+typedef struct { int fd; const unsigned char *mem; uint64_t n, woff, wlen; unsigned char w[BG_READ]; } bg_src_t;
+/* bytes [off, off + len) of the source, len <= BG_READ, off + len <= n; 0 ok, -1 read error */
+static int bg_get(bg_src_t *s, uint64_t off, unsigned len, unsigned char *out)
+{
+	if (s->mem) { memcpy(out, s->mem + off, len); return 0; }
+	if (off < s->woff || off + len > s->woff + s->wlen) {
+		uint64_t want = s->n - off < BG_READ ? s->n - off : BG_READ, got = 0;
+		while (got < want) {
+			ssize_t r = pread(s->fd, s->w + got, (size_t)(want - got), (off_t)(off + got));
+			if (r <= 0) return -1;
+			got += (uint64_t)r;
+		}
+		s->woff = off; s->wlen = want;
+	}
+	memcpy(out, s->w + (off - s->woff), len);
+	return 0;
+}
+static uint32_t bg_le32(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+/* returns a MAHIP_BGZF_* reason (MAHIP_BGZF_OK: *tab holds *n_members rows, malloc'ed; otherwise *bad = the member the walk stopped at and *tab = 0), -1 on a
+ * read error.  out_off is the 64-bit exclusive prefix sum of ISIZE. */
+int ma_bgzf_walk(int fd, const void *mem, uint64_t nbytes, mahip_bgzf_member_t **tab, uint64_t *n_members, uint64_t *n_empty, uint64_t *text_bytes, int64_t *bad)
+{
+	bg_src_t src;
+	mahip_bgzf_member_t *t = 0;
+	uint64_t n = 0, m = 0, p = 0, text = 0, empty = 0;
+	int reason = MAHIP_BGZF_OK;
+	memset(&src, 0, sizeof(src));
+	src.fd = fd; src.mem = (const unsigned char*)mem; src.n = nbytes;
+	*tab = 0; *n_members = *n_empty = *text_bytes = 0; *bad = -1;
+	while (p < nbytes) {
+		unsigned char h[12], sf[4], tr[8];
+		uint64_t total = 0, x, xend;
+		uint32_t xlen, isize;
+		int have_bc = 0;
+#define BG_STOP(r) { reason = (r); break; }
+		if (nbytes - p < 12) BG_STOP(n ? MAHIP_BGZF_TRAILING : MAHIP_BGZF_NOT_BGZF)
+		if (bg_get(&src, p, 12, h) != 0) { free(t); return -1; }
+		if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8) BG_STOP(n ? MAHIP_BGZF_TRAILING : MAHIP_BGZF_NOT_BGZF)
+		if (!(h[3] & 4)) BG_STOP(n ? MAHIP_BGZF_NO_BC : MAHIP_BGZF_NOT_BGZF) /* no extra field */
+		if (h[3] & ~(4 | 1)) BG_STOP(MAHIP_BGZF_BAD_FLG)                      /* FTEXT adds no field; FHCRC, FNAME, FCOMMENT and the reserved bits are not handled */
+		xlen = (uint32_t)h[10] | (uint32_t)h[11] << 8;
+		x = p + 12; xend = x + xlen;
+		if (xend > nbytes) BG_STOP(MAHIP_BGZF_PAST_END)
+		while (xend - x >= 4) { /* subfields SI1 SI2 SLEN data; `BC` may stand behind others */
+			uint32_t slen;
+			if (bg_get(&src, x, 4, sf) != 0) { free(t); return -1; }
+			slen = (uint32_t)sf[2] | (uint32_t)sf[3] << 8;
+			if (xend - x - 4 < slen) break; /* a subfield that runs out of the extra field */
+			if (sf[0] == 'B' && sf[1] == 'C' && slen == 2) {
+				unsigned char bs[2];
+				if (bg_get(&src, x + 4, 2, bs) != 0) { free(t); return -1; }
+				total = ((uint64_t)bs[0] | (uint64_t)bs[1] << 8) + 1; /* BSIZE + 1: the whole member */
+				have_bc = 1;
+				break;
+			}
+			x += 4 + slen;
+		}
+		if (!have_bc) BG_STOP(n ? MAHIP_BGZF_NO_BC : MAHIP_BGZF_NOT_BGZF)
+		if (total > nbytes - p || total < 12 + (uint64_t)xlen + 8) BG_STOP(MAHIP_BGZF_PAST_END)
+		if (bg_get(&src, p + total - 8, 8, tr) != 0) { free(t); return -1; }
+		isize = bg_le32(tr + 4);
+		if (isize > 65536) BG_STOP(MAHIP_BGZF_ISIZE)
+#undef BG_STOP
+		if (n == m) {
+			mahip_bgzf_member_t *t2;
+			m = m ? m + (m >> 1) : (nbytes >> 14) + 16; /* bgzip's members hold 64 KiB of text: a quarter of that compressed is a fair first guess */
+			t2 = (mahip_bgzf_member_t*)realloc(t, (size_t)m * sizeof(*t));
+			if (t2 == 0) { free(t); return -1; }
+			t = t2;
+		}
+		t[n].in_off = xend; t[n].in_len = (uint32_t)(total - 12 - xlen - 8);
+		t[n].out_off = text; t[n].isize = isize; t[n].crc = bg_le32(tr); t[n].pad = 0;
+		text += isize; empty += isize == 0;
+		++n; p += total;
+	}
+	if (reason == MAHIP_BGZF_OK && n == 0) reason = MAHIP_BGZF_NOT_BGZF; /* an empty source */
+	if (reason != MAHIP_BGZF_OK) { *bad = (int64_t)n; free(t); return reason; }
+	*tab = t; *n_members = n; *n_empty = empty; *text_bytes = text;
+	return MAHIP_BGZF_OK;
+}
+
+int ma_bgzf_enabled(void)
+{
+	const char *s = getenv("MA_BGZF_HOST");
+	return !(s && atoi(s) != 0);
 }
 
 int ma_gpu_parse_enabled(void)
@@ -90,7 +182,7 @@ int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict
 /* file -> HBM; 0 ok, -1 = could not open */
 int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 {
-	int fd = -1, is_plain = 0;
+	int fd = -1, is_plain = 0, is_reg = 0;
 	struct stat st;
 	if (fn && strcmp(fn, "-") != 0) {
 		unsigned char magic[2] = { 0, 0 };
@@ -98,6 +190,7 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 		if (fd < 0) return -1;
 		if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
 			ssize_t r = pread(fd, magic, 2, 0);
+			is_reg = 1;
 			is_plain = !(r == 2 && magic[0] == 0x1f && magic[1] == 0x8b);
 		}
 	}
@@ -105,7 +198,19 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 		if (mahip_paf_load_fd(c, fd, (size_t)st.st_size) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
 		close(fd);
 	} else {
-		gzFile fp = fd >= 0 ? gzdopen(fd, "r") : gzdopen(fileno(stdin), "r");
+		gzFile fp;
+		if (is_reg) { /* bgzip's blocks are inflated on the device (include/mahip.h); whatever keeps it from that leaves the file to zlib, as before */
+			mahip_bgzf_info_t bi;
+			if (!ma_bgzf_enabled()) {
+				memset(&bi, 0, sizeof(bi));
+				bi.reader = MAHIP_BGZF_HOST; bi.reason = MAHIP_BGZF_FORCED; bi.first_bad_member = -1; bi.comp_bytes = (uint64_t)st.st_size;
+				mahip_bgzf_note(c, &bi);
+			} else {
+				if (mahip_bgzf_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, &bi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
+				if (bi.reason == MAHIP_BGZF_OK) { close(fd); return 0; }
+			}
+		}
+		fp = fd >= 0 ? gzdopen(fd, "r") : gzdopen(fileno(stdin), "r");
 		size_t len = 0;
 		char *buf;
 		if (fp == 0) { if (fd >= 0) close(fd); return -1; }

@@ -434,13 +434,28 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	ui->reason = MAHIP_FASTX_NOT_PLAIN;
 	if (fn == 0 || strcmp(fn, "-") == 0) return 0;
 	if ((fd = open(fn, O_RDONLY)) < 0) return 0; /* the host reader reports it */
-	if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0 || pread(fd, magic, 2, 0) < 1 || (magic[0] == 0x1f && magic[1] == 0x8b)) { close(fd); return 0; }
+	if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0 || pread(fd, magic, 2, 0) < 1) { close(fd); return 0; }
 	t0 = sys_realtime();
 	mahip_mem_trim(c, 0); /* what the passes before left idle in the pool: the text may need it */
-	rc = mahip_fastx_load_fd(c, fd, (size_t)st.st_size);
-	close(fd);
-	if (rc < 0) { mahip_fastx_release(c); return -1; } /* a read error, a HIP error */
-	if (rc > 0) { ui->reason = MAHIP_FASTX_NOMEM; mahip_fastx_release(c); return 0; } /* no room for the text */
+	if (magic[0] == 0x1f && magic[1] == 0x8b) { /* compressed: bgzip's blocks are inflated on the device into the same text buffer (include/mahip.h); anything else is NOT_PLAIN, as ever */
+		mahip_bgzf_info_t bi;
+		if (!ma_bgzf_enabled()) {
+			memset(&bi, 0, sizeof(bi));
+			bi.reader = MAHIP_BGZF_HOST; bi.reason = MAHIP_BGZF_FORCED; bi.first_bad_member = -1; bi.comp_bytes = (uint64_t)st.st_size;
+			mahip_bgzf_note(c, &bi);
+			close(fd);
+			return 0;
+		}
+		rc = mahip_bgzf_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_FASTX, &bi);
+		close(fd);
+		if (rc != 0) { mahip_fastx_release(c); return -1; }
+		if (bi.reason != MAHIP_BGZF_OK) return 0;
+	} else {
+		rc = mahip_fastx_load_fd(c, fd, (size_t)st.st_size);
+		close(fd);
+		if (rc < 0) { mahip_fastx_release(c); return -1; } /* a read error, a HIP error */
+		if (rc > 0) { ui->reason = MAHIP_FASTX_NOMEM; mahip_fastx_release(c); return 0; } /* no room for the text */
+	}
 	laps[LAP_LOAD] = (sys_realtime() - t0) * 1e3; t0 = sys_realtime();
 	if (mahip_fastx_index(c, &fi) != 0) { mahip_fastx_release(c); return -1; }
 	laps[LAP_INDEX] = (sys_realtime() - t0) * 1e3;

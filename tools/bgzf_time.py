@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""Wall time of `miniasm x.paf` on a bgzip-compressed (BGZF) overlap file inflated on the device, against the same command on the plain file, on a plain gzip
+file and -- the yardstick -- on the BGZF file with MA_BGZF_HOST=1, which is the parent commit's road (zlib on one host thread; --parent path/to/its/miniasm
+checks once that the two agree).  Input: pafgen text of --lines lines (10 M), written as plain gzip and as BGZF by Python's zlib (no bgzip needed).  Every
+GPU step runs under its own `timeout -k 10`; the first one that fails ends the script.  Result: one JSON line with the walls of --reps runs each, the
+[T::bgzf] laps and the kernel's GB/s of text; also written to --out.  The new road counts as faster only if the SLOWEST of its runs beats the FASTEST of the
+yardstick's.
+
+  python tools/bgzf_time.py --out profiles/bgzf_time.json"""
+import argparse
+import json
+import os
+import re
+import struct
+import subprocess
+import sys
+import time
+import zlib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BIN = os.path.join(ROOT, "miniasm_amd", "bin")
+EOF_MARKER = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def write_compressed(src, gz, bgz, level):
+    """one pass over the text: plain gzip (one stream) and BGZF (members of 65280 bytes of text, as bgzip makes them)"""
+    co = zlib.compressobj(level, zlib.DEFLATED, 31)
+    with open(src, "rb") as f, open(gz, "wb") as g, open(bgz, "wb") as b:
+        while True:
+            part = f.read(65280)
+            if not part:
+                break
+            g.write(co.compress(part))
+            c = zlib.compressobj(level, zlib.DEFLATED, -15)
+            d = c.compress(part) + c.flush()
+            b.write(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(d) + 25) + d + struct.pack("<II", zlib.crc32(part), len(part)))
+        g.write(co.flush())
+        b.write(EOF_MARKER)
+
+
+def timed(cmd, env=None, limit=900):
+    """one GPU step under its own time limit; anything but exit 0 ends the script (nothing more is started on the GPU)"""
+    e = dict(os.environ, MA_PIPE_TIMING="1")
+    e.pop("MA_BGZF_HOST", None)
+    e.update(env or {})
+    t0 = time.time()
+    r = subprocess.run(["timeout", "-k", "10", str(limit)] + cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=e)
+    dt = time.time() - t0
+    log = r.stderr.decode(errors="replace")
+    if r.returncode != 0:
+        sys.exit("%s: exit %d after %.1f s\n%s" % (" ".join(cmd), r.returncode, dt, log[-3000:]))
+    return dt, log, zlib.crc32(r.stdout)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lines", type=int, default=10000000)
+    ap.add_argument("--reads", type=int, default=300000)
+    ap.add_argument("--level", type=int, default=6)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--miniasm", default=os.path.join(BIN, "miniasm"), help="the binary under test (tests/emu/_build/miniasm tries the script without a GPU)")
+    ap.add_argument("--parent", default=None, help="the parent commit's miniasm binary: one run on the BGZF file, to check that MA_BGZF_HOST=1 is its road")
+    ap.add_argument("--tmp", default="/tmp")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    paf = os.path.join(a.tmp, "bgzf_time_%d.paf" % os.getpid())
+    files = {"plain": paf, "gzip": paf + ".plain.gz", "bgzf": paf + ".gz"}
+    try:
+        subprocess.run([os.path.join(BIN, "pafgen"), "-r", str(a.reads), "-n", str(a.lines), "-s", "4", "-o", paf], check=True, stderr=subprocess.DEVNULL)
+        write_compressed(paf, files["gzip"], files["bgzf"], a.level)
+        res = {"lines": a.lines, "bytes": {k: os.path.getsize(v) for k, v in files.items()}, "wall_s": {}, "laps_ms": [], "inflate_gbps": []}
+        out_crc = set()
+        for name, fn, env in (("plain", files["plain"], None), ("gzip", files["gzip"], None), ("bgzf", files["bgzf"], None), ("bgzf_host", files["bgzf"], {"MA_BGZF_HOST": "1"})):
+            walls = []
+            for _ in range(a.reps):
+                dt, log, crc = timed([a.miniasm, fn], env)
+                walls.append(round(dt, 4))
+                out_crc.add(crc)
+                m = re.search(r"^\[T::bgzf\] reader=(\w+).*", log, re.M)
+                if name == "bgzf":
+                    if not m or m.group(1) != "device":
+                        sys.exit("the BGZF file was not inflated on the device:\n" + log[-2000:])
+                    lap = re.search(r"walk ([\d.]+) upload ([\d.]+) inflate ([\d.]+) crc ([\d.]+) ms \(inflate ([\d.]+) GB/s", m.group(0))
+                    res["laps_ms"].append(dict(zip(("walk", "upload", "inflate", "crc"), map(float, lap.groups()[:4]))))
+                    res["inflate_gbps"].append(float(lap.group(5)))
+            res["wall_s"][name] = walls
+        res["same_output"] = len(out_crc) == 1
+        if a.parent:
+            dt, _, crc = timed([a.parent, files["bgzf"]])
+            res["wall_s"]["parent_bgzf"] = [round(dt, 4)]
+            res["same_output"] = res["same_output"] and crc in out_crc
+        res["ratio_slowest_new_over_fastest_yardstick"] = round(max(res["wall_s"]["bgzf"]) / min(res["wall_s"]["bgzf_host"]), 4)
+        res["faster_beyond_spread"] = max(res["wall_s"]["bgzf"]) < min(res["wall_s"]["bgzf_host"])
+        line = json.dumps(res)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+    finally:
+        for v in files.values():
+            if os.path.exists(v):
+                os.remove(v)
+
+
+if __name__ == "__main__":
+    main()
