@@ -33,7 +33,7 @@ lib: $(LIB)
 $(B) $(PKG)/lib $(PKG)/bin:
 	mkdir -p $@
 
-$(B)/%.hip.o: $(CSRC)/%.hip $(CSRC)/mahip_internal.hpp $(CSRC)/ma_core.h $(CSRC)/clean_core.h $(CSRC)/ug_core.h $(CSRC)/inflate_core.h include/mahip.h include/miniasm_amd.h | $(B)
+$(B)/%.hip.o: $(CSRC)/%.hip $(CSRC)/mahip_internal.hpp $(CSRC)/ma_core.h $(CSRC)/clean_core.h $(CSRC)/ug_core.h $(CSRC)/inflate_core.h $(CSRC)/gzip_core.h include/mahip.h include/miniasm_amd.h | $(B)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(B)/%.o: $(HOST)/%.c $(HOST)/ma_host.h $(HOST)/refsort_body.h include/mahip.h include/miniasm_amd.h | $(B)

@@ -354,6 +354,50 @@ int mahip_bgzf_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, void 
 int mahip_bgzf_last(mahip_ctx_t *c, mahip_bgzf_info_t *out); /* what the context's last BGZF load (or mahip_bgzf_note) decided */
 void mahip_bgzf_note(mahip_ctx_t *c, const mahip_bgzf_info_t *in); /* a caller that did not get as far as a load (MA_BGZF_HOST) says so */
 const char *mahip_bgzf_reason_name(int reason);
+/* ---- plain gzip input (one member, one deflate stream: what `gzip -1` writes) inflated on the device (csrc/xfer.hip: k_gz_*, csrc/gzip_core.h).
+ * The host reads the member's header and trailer; the compressed file goes to HBM as it is; its payload is cut into chunks of `chunk` bytes.  k_gz_sync_count:
+ * one wave per chunk looks in its own bits for the first dynamic-block header that holds and that a trial decode of the block confirms (chunk 0 starts at bit
+ * 0), then decodes on WITHOUT output, summing the output length, to the first dynamic block start in a later chunk, or to the end of the stream: one row per
+ * chunk.  The host follows the rows from chunk 0 (`end_bit` of one must be `sync_bit` of the chunk it falls into): the chain's items, their output offsets,
+ * the text size.  k_gz_decode: one wave per item writes 16-bit symbols (a byte, or a cell of the unknown 32 KiB in front of the item); k_gz_windows: one
+ * workgroup makes every item's window from the one before it; k_gz_resolve writes the text, k_gz_crc checks it against the trailer.  Every refusal is a
+ * `reason`, not an error: nothing is loaded and the caller inflates with zlib.
+ *   BAD_HEADER: not a gzip member, CM != 8, a reserved flag, an extra field with a `BC` subfield, or too short for header and trailer;
+ *   MULTI_MEMBER: the stream's final block does not end 8 bytes in front of the end of the file (a second member, trailing bytes);
+ *   NO_SYNC: an item ran over more than GZ_SPAN_MAX (16) whole chunks without reaching its end; SYNC_MISMATCH: an item ends in a chunk whose own first
+ *   block start is another bit (a false candidate stood in front of the true one); ISIZE: the items' total is not the trailer's ISIZE (mod 2^32);
+ *   BAD_BTYPE .. OUT_SHORT: the status of an item on the chain, as for BGZF; CRC; NOMEM, NOT_SEEKABLE, FORCED (the switch is off), EMPTY: as for BGZF. */
+enum { MAHIP_GZIP_OK = 0, MAHIP_GZIP_BAD_HEADER, MAHIP_GZIP_MULTI_MEMBER, MAHIP_GZIP_NO_SYNC, MAHIP_GZIP_SYNC_MISMATCH, MAHIP_GZIP_ISIZE,
+       MAHIP_GZIP_BAD_BTYPE, MAHIP_GZIP_STORED_LEN, MAHIP_GZIP_BAD_LENGTHS, MAHIP_GZIP_BAD_SYMBOL, MAHIP_GZIP_DIST_TOO_FAR, MAHIP_GZIP_OUT_OVERFLOW, MAHIP_GZIP_IN_EXHAUSTED,
+       MAHIP_GZIP_OUT_SHORT, MAHIP_GZIP_CRC, MAHIP_GZIP_NOMEM, MAHIP_GZIP_NOT_SEEKABLE, MAHIP_GZIP_FORCED, MAHIP_GZIP_EMPTY };
+#define MAHIP_GZIP_CHUNK_DEFAULT ((size_t)1 << 20) /* bytes of payload per chunk; MA_GZIP_CHUNK (a power of two, 1024 .. 16 MiB) overrides it */
+typedef struct {
+	uint64_t comp_bytes, text_bytes;       /* the file; the items' total output */
+	uint64_t chunk, n_chunks, n_synced, n_items; /* chunk size; chunks; those that found a start (chunk 0 included); items on the chain */
+	uint64_t n_stored, n_fixed, n_dynamic; /* deflate blocks by type over the chain (counted by k_gz_decode: 0 when it did not run) */
+	int reader, reason;                    /* MAHIP_BGZF_HOST | MAHIP_BGZF_DEVICE; MAHIP_BGZF_DEVICE <=> reason == MAHIP_GZIP_OK */
+	int64_t first_bad_item;                /* the chain item (its number on the chain) the reason is about, else -1 */
+	double laps_ms[6];                     /* upload, sync + count, decode, windows, resolve, CRC */
+} mahip_gzip_info_t;
+/* one row per chunk, as k_gz_sync_count leaves it; bits count from the first bit of the payload */
+#define MAHIP_GZIP_SAW_FINAL 1u
+#define MAHIP_GZIP_ON_CHAIN 2u
+typedef struct {
+	int64_t sync_bit;          /* where the chunk's item starts; -1: no start found (no item) */
+	uint64_t end_bit, out_len; /* where it stopped; the bytes it inflates to */
+	uint32_t status, flags;    /* 0 or the item's status as a MAHIP_GZIP_* reason; MAHIP_GZIP_SAW_FINAL, MAHIP_GZIP_ON_CHAIN */
+} mahip_gzip_item_t;
+/* target MAHIP_BGZF_PAF | MAHIP_BGZF_FASTX, return values and what is left loaded: as mahip_bgzf_load_fd.  chunk 0: MA_GZIP_CHUNK, else the default. */
+int mahip_gzip_load_fd(mahip_ctx_t *c, int fd, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info);
+int mahip_gzip_load_mem(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info);
+/* for stage tests: image in host memory -> text in host memory (out_cap >= info->text_bytes, else -1); nothing stays loaded */
+int mahip_gzip_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info);
+int mahip_gzip_last(mahip_ctx_t *c, mahip_gzip_info_t *out);
+void mahip_gzip_note(mahip_ctx_t *c, const mahip_gzip_info_t *in);
+const char *mahip_gzip_reason_name(int reason);
+/* the rows of the context's last plain-gzip load (n_chunks of them; none when it stopped at the header); valid until the next load.  Returns the number
+ * of rows copied (at most cap). */
+uint64_t mahip_gzip_items_download(mahip_ctx_t *c, mahip_gzip_item_t *out, uint64_t cap);
 uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
 /* how many device-wide scans (csrc/scan.hip) of this context, since it was created, took each form: one tile (k_scan_down alone, n <= 2048), the chained
  * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */

@@ -107,6 +107,27 @@ def _bgzf_dict(b):
                 reader=BGZF_READERS[b.reader], reason=BGZF_REASONS[b.reason], first_bad_member=b.first_bad_member, laps_ms=dict(zip(("walk", "upload", "inflate", "crc"), b.laps_ms)))
 
 
+class GzipInfo(C.Structure):  # include/mahip.h: mahip_gzip_info_t
+    _fields_ = [("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("chunk", C.c_uint64), ("n_chunks", C.c_uint64), ("n_synced", C.c_uint64), ("n_items", C.c_uint64),
+                ("n_stored", C.c_uint64), ("n_fixed", C.c_uint64), ("n_dynamic", C.c_uint64), ("reader", C.c_int), ("reason", C.c_int), ("first_bad_item", C.c_int64),
+                ("laps_ms", C.c_double * 6)]
+
+
+class GzipItem(C.Structure):  # include/mahip.h: mahip_gzip_item_t
+    _fields_ = [("sync_bit", C.c_int64), ("end_bit", C.c_uint64), ("out_len", C.c_uint64), ("status", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# include/mahip.h: MAHIP_GZIP_* reasons
+GZIP_REASONS = ["OK", "BAD_HEADER", "MULTI_MEMBER", "NO_SYNC", "SYNC_MISMATCH", "ISIZE", "BAD_BTYPE", "STORED_LEN", "BAD_LENGTHS", "BAD_SYMBOL", "DIST_TOO_FAR", "OUT_OVERFLOW",
+                "IN_EXHAUSTED", "OUT_SHORT", "CRC", "NOMEM", "NOT_SEEKABLE", "FORCED", "EMPTY"]
+
+
+def _gzip_dict(g):
+    return dict(comp_bytes=g.comp_bytes, text_bytes=g.text_bytes, chunk=g.chunk, n_chunks=g.n_chunks, n_synced=g.n_synced, n_items=g.n_items, n_stored=g.n_stored, n_fixed=g.n_fixed,
+                n_dynamic=g.n_dynamic, reader=BGZF_READERS[g.reader], reason=GZIP_REASONS[g.reason], first_bad_item=g.first_bad_item,
+                laps_ms=dict(zip(("upload", "sync_count", "decode", "windows", "resolve", "crc"), g.laps_ms)))
+
+
 class PafInfo(C.Structure):  # include/mahip.h: mahip_paf_info_t
     _fields_ = [("n_lines", C.c_uint64), ("n_records", C.c_uint64), ("n_stored_lines", C.c_uint64), ("n_hits", C.c_uint64), ("name_bytes", C.c_uint64),
                 ("n_seq", C.c_uint32), ("max_qs", C.c_uint32), ("n_excl", C.c_uint32)]
@@ -220,6 +241,14 @@ def lib():
         L.mahip_bgzf_last.argtypes = [vp, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_reason_name.restype = C.c_char_p
         L.mahip_bgzf_reason_name.argtypes = [i32]
+        L.mahip_gzip_load_fd.argtypes = [vp, i32, sz, i32, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_load_mem.argtypes = [vp, vp, sz, i32, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_inflate_mem.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_last.argtypes = [vp, C.POINTER(GzipInfo)]
+        L.mahip_gzip_reason_name.restype = C.c_char_p
+        L.mahip_gzip_reason_name.argtypes = [i32]
+        L.mahip_gzip_items_download.restype = C.c_uint64
+        L.mahip_gzip_items_download.argtypes = [vp, C.POINTER(GzipItem), C.c_uint64]
         L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
         L.mahip_scan_forms.restype = None
         L.ma_opt_init.argtypes = [C.POINTER(MaOpt)]
@@ -474,6 +503,37 @@ class Ctx:
         bi = BgzfInfo()
         _chk(lib().mahip_bgzf_last(self.h, C.byref(bi)), "bgzf_last")
         return _bgzf_dict(bi)
+
+    # ---- plain gzip input inflated on the device (csrc/xfer.hip: k_gz_*, csrc/gzip_core.h)
+    def gzip_inflate(self, comp, chunk=None, out_cap=None):
+        """a gzip image (bytes) -> (text, info dict); text is None when the device refused it (info["reason"] says why); chunk: bytes of payload per chunk (None:
+        MA_GZIP_CHUNK or the default) -- nothing stays loaded either way"""
+        gi = GzipInfo()
+        cap = out_cap if out_cap is not None else 1032 * len(comp) + 64  # deflate's best ratio
+        out = C.create_string_buffer(max(cap, 1))
+        _chk(lib().mahip_gzip_inflate_mem(self.h, comp, len(comp), chunk or 0, out, cap, C.byref(gi)), "gzip_inflate_mem")
+        info = _gzip_dict(gi)
+        return (out.raw[:gi.text_bytes] if info["reason"] == "OK" else None), info
+
+    def gzip_load(self, comp, target="paf", chunk=None):
+        """a gzip image into the text buffer of the PAF reader or of the reads-file reader, as mahip_paf_load_mem / mahip_fastx_load_mem leave it -> info dict"""
+        gi = GzipInfo()
+        _chk(lib().mahip_gzip_load_mem(self.h, comp, len(comp), BGZF_TARGETS[target], chunk or 0, C.byref(gi)), "gzip_load_mem")
+        return _gzip_dict(gi)
+
+    def gzip_last(self):
+        """what the context's last plain-gzip load decided"""
+        gi = GzipInfo()
+        _chk(lib().mahip_gzip_last(self.h, C.byref(gi)), "gzip_last")
+        return _gzip_dict(gi)
+
+    def gzip_items(self):
+        """one row per chunk of the last plain-gzip load: dict(sync_bit (None: the chunk found no start), end_bit, out_len, status (a GZIP_REASONS name), saw_final, on_chain)"""
+        n = self.gzip_last()["n_chunks"]
+        rows = (GzipItem * max(n, 1))()
+        n = lib().mahip_gzip_items_download(self.h, rows, n)
+        return [dict(sync_bit=None if r.sync_bit < 0 else r.sync_bit, end_bit=r.end_bit, out_len=r.out_len, status=GZIP_REASONS[r.status], saw_final=bool(r.flags & 1), on_chain=bool(r.flags & 2))
+                for r in rows[:n]]
 
     def scan_forms(self):
         """device-wide scans of this context so far by form: (one tile, chained, three-phase)"""

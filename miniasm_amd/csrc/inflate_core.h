@@ -36,14 +36,17 @@ enum { INF_OK = 0, INF_BAD_BTYPE, INF_STORED_LEN, INF_BAD_LENGTHS, INF_BAD_SYMBO
 #define INF_DBITS 8
 #define INF_NOSYM 0xffffffffu
 
-struct InfLds {
-	uint8_t ring[INF_RING];
+/* what the bit reader and the code tables need; the decoders add their output history (InfLds here, GzLds in gzip_core.h) */
+struct InfTabs {
 	uint8_t win[INF_WIN];
 	uint16_t lfast[1 << INF_LBITS], dfast[1 << INF_DBITS];
 	uint16_t lcount[16], dcount[16], offs[16];
 	uint16_t lsym[288], dsym[32];
 	uint8_t lens[320];
 	uint32_t brc[4]; /* what lane 0 found while building: lit/len result, its longest code, distance result, its longest code */
+};
+struct InfLds : InfTabs {
+	uint8_t ring[INF_RING];
 };
 
 struct InfState {
@@ -61,7 +64,7 @@ struct InfState {
 #define INF_ORD_A (16ull | 17ull << 5 | 18ull << 10 | 0ull << 15 | 8ull << 20 | 7ull << 25 | 9ull << 30 | 6ull << 35 | 10ull << 40 | 5ull << 45 | 11ull << 50 | 4ull << 55)
 #define INF_ORD_B (12ull | 3ull << 5 | 13ull << 10 | 2ull << 15 | 14ull << 20 | 1ull << 25 | 15ull << 30)
 
-__device__ __forceinline__ void inf_fetch(InfState &s, InfLds &L)
+__device__ __forceinline__ void inf_fetch(InfState &s, InfTabs &L)
 {
 	wv_sync();
 	for (uint32_t k = 0; k < INF_FETCH; k += 64) {
@@ -73,7 +76,7 @@ __device__ __forceinline__ void inf_fetch(InfState &s, InfLds &L)
 }
 
 /* afterwards the bit buffer holds at least 32 bits, or all that is left of the input */
-__device__ __forceinline__ void inf_refill(InfState &s, InfLds &L)
+__device__ __forceinline__ void inf_refill(InfState &s, InfTabs &L)
 {
 	if (s.bitcnt >= 32) return;
 	if (s.lp - s.ip < 8 && s.lp < s.in_len) inf_fetch(s, L);
@@ -85,7 +88,7 @@ __device__ __forceinline__ void inf_refill(InfState &s, InfLds &L)
 }
 
 /* n <= 16 bits, least significant first */
-__device__ __forceinline__ uint32_t inf_bits(InfState &s, InfLds &L, uint32_t n)
+__device__ __forceinline__ uint32_t inf_bits(InfState &s, InfTabs &L, uint32_t n)
 {
 	inf_refill(s, L);
 	if (s.bitcnt < n) { s.err = INF_IN_EXHAUSTED; return 0; }
@@ -107,7 +110,7 @@ __device__ __forceinline__ uint32_t inf_canon(const uint16_t *count, const uint1
 	return INF_NOSYM;
 }
 
-__device__ __forceinline__ uint32_t inf_sym(InfState &s, InfLds &L, const uint16_t *fast, uint32_t fast_bits, const uint16_t *count, const uint16_t *symbol)
+__device__ __forceinline__ uint32_t inf_sym(InfState &s, InfTabs &L, const uint16_t *fast, uint32_t fast_bits, const uint16_t *count, const uint16_t *symbol)
 {
 	inf_refill(s, L);
 	const uint32_t b = (uint32_t)s.bitbuf & 0x7fffu, e = fast[b & ((1u << fast_bits) - 1u)];
@@ -124,7 +127,7 @@ __device__ __forceinline__ uint32_t inf_sym(InfState &s, InfLds &L, const uint16
 }
 
 /* ONE lane: lens[0 .. n) -> codes per length and symbols in code order.  0: complete, 1: over-subscribed, 2: incomplete; *maxlen: the longest code (0: none) */
-__device__ __forceinline__ uint32_t inf_build(InfLds &L, const uint8_t *lens, uint32_t n, uint16_t *count, uint16_t *symbol, uint32_t *maxlen)
+__device__ __forceinline__ uint32_t inf_build(InfTabs &L, const uint8_t *lens, uint32_t n, uint16_t *count, uint16_t *symbol, uint32_t *maxlen)
 {
 	for (uint32_t l = 0; l < 16; ++l) count[l] = 0;
 	for (uint32_t i = 0; i < n; ++i) ++count[lens[i] & 15u];
@@ -153,7 +156,7 @@ __device__ __forceinline__ void inf_fill_fast(InfState &s, uint16_t *fast, uint3
 
 /* lens[0 .. nl) and lens[nl .. nl + nd) are written (and visible): both codes and their tables, with zlib's rules for what is acceptable (inftrees.c: an
  * over-subscribed set never, an incomplete one only when it is a single code of one bit; no distance code at all is fine as long as no match turns up) */
-__device__ __forceinline__ void inf_tables(InfState &s, InfLds &L, uint32_t nl, uint32_t nd)
+__device__ __forceinline__ void inf_tables(InfState &s, InfTabs &L, uint32_t nl, uint32_t nd)
 {
 	if (s.lane == 0) {
 		uint32_t ml = 0, md = 0;
@@ -194,7 +197,7 @@ __device__ __forceinline__ void inf_stored(InfState &s, InfLds &L)
 	if (s.lp < s.ip) s.lp = s.ip; /* the window starts again behind the block */
 }
 
-__device__ __forceinline__ void inf_fixed(InfState &s, InfLds &L)
+__device__ __forceinline__ void inf_fixed(InfState &s, InfTabs &L)
 {
 	if (s.fixed) return;
 	for (uint32_t i = s.lane; i < 320; i += 64) L.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5; /* 288 literal/length codes, 32 distance codes of 5 bits */
@@ -203,7 +206,7 @@ __device__ __forceinline__ void inf_fixed(InfState &s, InfLds &L)
 	s.fixed = 1;
 }
 
-__device__ __forceinline__ void inf_dynamic(InfState &s, InfLds &L)
+__device__ __forceinline__ void inf_dynamic(InfState &s, InfTabs &L)
 {
 	s.fixed = 0;
 	const uint32_t hlit = inf_bits(s, L, 5) + 257, hdist = inf_bits(s, L, 5) + 1, hclen = inf_bits(s, L, 4) + 4;
@@ -327,6 +330,16 @@ __device__ __forceinline__ uint32_t inf_mulmod(uint32_t a, uint32_t b)
 __device__ __forceinline__ uint32_t inf_xpow8(uint32_t n)
 {
 	uint32_t p = 0x80000000u, sq = 0x00800000u; /* x^0, x^8 */
+	for (; n; n >>= 1) {
+		if (n & 1u) p = inf_mulmod(p, sq);
+		sq = inf_mulmod(sq, sq);
+	}
+	return p;
+}
+/* the same for a text of more than 4 GiB */
+__device__ __forceinline__ uint32_t inf_xpow8_64(uint64_t n)
+{
+	uint32_t p = 0x80000000u, sq = 0x00800000u;
 	for (; n; n >>= 1) {
 		if (n & 1u) p = inf_mulmod(p, sq);
 		sq = inf_mulmod(sq, sq);

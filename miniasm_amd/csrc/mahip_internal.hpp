@@ -127,6 +127,9 @@ struct mahip_ctx {
 	void *paf = nullptr;       // text-ingest buffers (paf.hip)
 	bool paf_keep_odd = false; // mahip_paf_keep_odd: the next parses keep a host snapshot of the lines left to the byte-wise parser (tests)
 	mahip_bgzf_info_t bgzf_last = {}; // what the last BGZF load decided (xfer.hip: mahip_bgzf_last)
+	mahip_gzip_info_t gzip_last = {}; // the same for plain gzip, and its rows (host memory; xfer.hip: mahip_gzip_items_download)
+	mahip_gzip_item_t *gzip_rows = nullptr;
+	uint64_t gzip_n_rows = 0;
 
 	hipEvent_t mark_ev[64] = {}; // phase marks (mahip_mark)
 	hipStream_t sub_side[2] = {}; hipEvent_t sub_ev[3] = {}; // side streams of the coverage passes' size classes (hits.hip: SubFork)

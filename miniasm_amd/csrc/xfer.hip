@@ -321,3 +321,355 @@ extern "C" const char *mahip_bgzf_reason_name(int reason)
 	                                 "more output than ISIZE", "the deflate bytes end early", "less output than ISIZE", "CRC mismatch", "not enough device memory", "not a regular file", "MA_BGZF_HOST is set", "no text"};
 	return reason >= 0 && reason < (int)(sizeof(nm) / sizeof(nm[0])) ? nm[reason] : "?";
 }
+
+// ================================================================================================ plain gzip input, inflated on the device
+// One member, ONE deflate stream: what BGZF's headers give away -- where a block starts, how many bytes a piece inflates to, what the 32 KiB in front of a
+// piece held -- is found here.  include/mahip.h has the scheme; gzip_core.h the per-lane header test and the wave's decode loop in its two forms.
+#include "gzip_core.h"
+
+#define GZ_CNT_WAVES 4u    // k_gz_sync_count: chunks per workgroup (tables only: 4 x 5.6 KiB of LDS)
+#define GZ_DEC_WAVES 2u    // k_gz_decode: items per workgroup (2 x sizeof(GzLds) = 137 KiB of the CU's 160 KiB)
+#define GZ_TILE 4096u      // k_gz_resolve: text bytes per workgroup
+#define GZ_CRC_PIECE 65536u
+#define GZ_CHUNK_MAX ((size_t)16 << 20) // (GZ_SPAN_MAX + 2) chunks + GZ_BLOCK_MAX stay below 2^32 / 8: a wave's local BIT positions fit 32 bits with room
+struct gz_chain_t { uint64_t sync_bit, end_bit, out_off, out_len; }; // one item of the chain; bits of the payload
+
+// the input a wave whose chunk starts at byte0 of the payload may read
+__device__ __forceinline__ uint32_t gz_in_len(uint64_t payload_len, uint64_t byte0, uint64_t C)
+{
+	const uint64_t rest = payload_len - byte0, cap = (uint64_t)(GZ_SPAN_MAX + 2) * C + GZ_BLOCK_MAX;
+	return (uint32_t)(rest < cap ? rest : cap);
+}
+__device__ __forceinline__ void gz_state(InfState &s, const uint8_t *in, uint32_t in_len, unsigned lane)
+{
+	s.in = in; s.out = nullptr; s.in_len = in_len; s.isize = 0; s.ip = s.lp = s.op = s.fp = 0; s.bitbuf = 0; s.bitcnt = 0; s.err = INF_OK; s.fixed = 0; s.lane = lane;
+	s.nblk[0] = s.nblk[1] = s.nblk[2] = 0;
+}
+__device__ __forceinline__ uint32_t gz_reason(uint32_t st) { return st == GZ_NO_SYNC ? (uint32_t)MAHIP_GZIP_NO_SYNC : (uint32_t)MAHIP_GZIP_BAD_BTYPE + st - 1; }
+
+// One wave per chunk.  Chunk 0 starts at bit 0.  Every other chunk tries its own bits, 64 consecutive ones a round (one a lane: gz_holds), and the whole wave
+// confirms the survivors in ascending order by decoding the block (gz_item); the first confirmed one is the chunk's start, and the decode goes on from there,
+// counting, to the item's end.  TERMINATION: the search visits each of the chunk's <= 8 C bits once, each candidate's trial and the item's decode consume
+// input that is bounded by gz_in_len.  BOUNDS: the payload is read below byte0 + in_len <= payload_len only; one row is written, rows[k], k < n_chunks.
+__global__ __launch_bounds__(256) void k_gz_sync_count(const uint8_t *__restrict__ payload, uint64_t payload_len, uint64_t C, uint64_t n_chunks, mahip_gzip_item_t *__restrict__ rows)
+{
+	__shared__ InfTabs s_tab[GZ_CNT_WAVES];
+	__shared__ GzCand s_cand[GZ_CNT_WAVES];
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint64_t k = (uint64_t)blockIdx.x * GZ_CNT_WAVES + wave;
+	if (k >= n_chunks) return; // the whole wave; nothing below waits for another wave
+	const uint64_t byte0 = k * C, CB = C * 8;
+	InfState s;
+	gz_state(s, payload + byte0, gz_in_len(payload_len, byte0, C), lane);
+	const uint64_t own_bits = payload_len - byte0 < C ? (payload_len - byte0) * 8 : CB;
+	GzOut o;
+	o.op = o.fp = o.lim = o.before = 0; o.out = nullptr;
+	uint64_t start = 0, end = 0;
+	uint32_t st = GZ_UNCONFIRMED, fin = 0, nblk[3] = {0, 0, 0};
+	if (k == 0) st = gz_item<false>(s, s_tab[wave], nullptr, o, 0, CB, 0, false, &end, &fin, nblk);
+	else {
+		for (uint64_t base = 0; base < own_bits && st == GZ_UNCONFIRMED; base += 64) {
+			const uint64_t bit = base + lane;
+			uint64_t m = wv_ballot(bit < own_bits && gz_holds(s.in, s.in_len, bit, s_cand[wave].cnt[lane], s_cand[wave].sym[lane]));
+			while (m) {
+				start = base + (uint64_t)(__ffsll((long long)m) - 1);
+				m &= m - 1;
+				o.op = 0;
+				st = gz_item<false>(s, s_tab[wave], nullptr, o, start, CB, 0, true, &end, &fin, nblk);
+				if (st != GZ_UNCONFIRMED) break;
+			}
+		}
+	}
+	if (lane == 0) {
+		mahip_gzip_item_t r;
+		if (st == GZ_UNCONFIRMED) { r.sync_bit = -1; r.end_bit = 0; r.out_len = 0; r.status = 0; r.flags = 0; }
+		else { r.sync_bit = (int64_t)(byte0 * 8 + start); r.end_bit = byte0 * 8 + end; r.out_len = o.op; r.status = st ? gz_reason(st) : 0u; r.flags = fin ? MAHIP_GZIP_SAW_FINAL : 0u; }
+		rows[k] = r;
+	}
+}
+
+enum { GZ_RES_BAD = 0, GZ_RES_STORED, GZ_RES_FIXED, GZ_RES_DYNAMIC, GZ_RES_WORDS = 8 }; // res[GZ_RES_BAD] = min over the items with a status of item << 8 | status
+
+// One wave per chain item: the decode of the count pass again, now writing 16-bit symbols at sym[out_off ..] through the LDS ring of the last 32768 symbols.
+// It stops where the count pass stopped (end_bit) after as many symbols (out_len): anything else is a status.  BOUNDS: sym is written at out_off + p, p <
+// out_len, only (gz_codes / gz_stored check before they write, gz_flush writes what they produced).
+__global__ __launch_bounds__(128) void k_gz_decode(const uint8_t *__restrict__ payload, uint64_t payload_len, uint64_t C, const gz_chain_t *__restrict__ chain, uint64_t n_items,
+                                                   uint16_t *__restrict__ sym, unsigned long long *__restrict__ res)
+{
+	__shared__ GzLds s_lds[GZ_DEC_WAVES];
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint64_t j = (uint64_t)blockIdx.x * GZ_DEC_WAVES + wave;
+	if (j >= n_items) return;
+	const gz_chain_t it = chain[j];
+	const uint64_t CB = C * 8, k = it.sync_bit / CB, byte0 = k * C;
+	InfState s;
+	gz_state(s, payload + byte0, gz_in_len(payload_len, byte0, C), lane);
+	GzOut o;
+	o.op = o.fp = 0; o.lim = it.out_len; o.before = it.out_off; o.out = sym + it.out_off;
+	uint64_t end = 0;
+	uint32_t fin = 0, nblk[3] = {0, 0, 0};
+	uint32_t st = gz_item<true>(s, s_lds[wave], s_lds[wave].ring, o, it.sync_bit - k * CB, CB, it.end_bit - k * CB, false, &end, &fin, nblk);
+	if (!st && (o.op != it.out_len || end != it.end_bit - k * CB)) st = INF_OUT_SHORT;
+	gz_flush(s, s_lds[wave].ring, o);
+	if (lane == 0) {
+		if (st) atomicMin(res + GZ_RES_BAD, (unsigned long long)(j << 8 | gz_reason(st)));
+		if (nblk[0]) atomicAdd(res + GZ_RES_STORED, (unsigned long long)nblk[0]);
+		if (nblk[1]) atomicAdd(res + GZ_RES_FIXED, (unsigned long long)nblk[1]);
+		if (nblk[2]) atomicAdd(res + GZ_RES_DYNAMIC, (unsigned long long)nblk[2]);
+	}
+}
+
+// ONE workgroup, the only serial step: W[0] is the window in front of the stream (never referenced: k_gz_decode refuses a reach in front of the stream, it
+// knows out_off), W[j + 1] = the last 32768 cells of W[j] followed by item j's resolved symbols.  An item of fewer than 32768 bytes passes older cells on.
+// BOUNDS: W holds n_items windows; sym is read at out_off + [out_len - 32768, out_len) clipped to the item.
+__global__ __launch_bounds__(256) void k_gz_windows(const gz_chain_t *__restrict__ chain, uint64_t n_items, const uint16_t *__restrict__ sym, uint8_t *W)
+{
+	for (uint64_t j = 0; j + 1 < n_items; ++j) {
+		const uint64_t off = chain[j].out_off, n = chain[j].out_len;
+		const uint8_t *w0 = W + j * GZ_WIN;
+		uint8_t *w1 = W + (j + 1) * GZ_WIN;
+		for (uint32_t i = threadIdx.x; i < GZ_WIN; i += 256) {
+			uint8_t v;
+			if (n + i >= GZ_WIN) { const uint16_t sy = sym[off + (n + i - GZ_WIN)]; v = sy < 256 ? (uint8_t)sy : w0[sy & (GZ_WIN - 1)]; }
+			else v = w0[i + n];
+			w1[i] = v;
+		}
+		__syncthreads(); // W[j + 1] is complete (and visible to this workgroup) before it is read
+	}
+}
+
+// text[p] = the symbol at p, or the cell it names in its item's window.  A workgroup takes GZ_TILE consecutive bytes; the item of a byte is the LAST one whose
+// out_off is not behind it (items without output share their successor's offset).
+__global__ __launch_bounds__(256) void k_gz_resolve(const gz_chain_t *__restrict__ chain, uint64_t n_items, const uint16_t *__restrict__ sym, const uint8_t *__restrict__ W,
+                                                    uint8_t *__restrict__ text, uint64_t total)
+{
+	const uint64_t t0 = (uint64_t)blockIdx.x * GZ_TILE;
+	if (t0 >= total) return;
+	uint64_t lo = 0, hi = n_items; // chain[lo].out_off <= t0 < chain[hi].out_off (chain[n_items].out_off = total)
+	while (hi - lo > 1) { const uint64_t mid = lo + (hi - lo) / 2; if (chain[mid].out_off <= t0) lo = mid; else hi = mid; }
+	uint64_t j = lo;
+	for (uint32_t k = threadIdx.x; k < GZ_TILE; k += 256) {
+		const uint64_t p = t0 + k;
+		if (p >= total) break;
+		while (j + 1 < n_items && chain[j + 1].out_off <= p) ++j;
+		const uint16_t sy = sym[p];
+		text[p] = sy < 256 ? (uint8_t)sy : W[j * GZ_WIN + (sy & (GZ_WIN - 1))];
+	}
+}
+
+// one wave per GZ_CRC_PIECE bytes of text, as k_bgzf_crc per member; pc[piece] = the piece's CRC moved in front of ALL the text behind it (x^(8 n) with a 64-bit
+// n): the XOR of pc[] is the CRC of the text
+__global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text, uint64_t total, uint64_t n_pieces, uint32_t *__restrict__ pc)
+{
+	__shared__ uint32_t s_crc[256];
+	{
+		uint32_t v = threadIdx.x;
+		for (int k = 0; k < 8; ++k) v = v & 1u ? (v >> 1) ^ INF_CRC_POLY : v >> 1;
+		s_crc[threadIdx.x] = v;
+	}
+	__syncthreads();
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint64_t m = (uint64_t)blockIdx.x * 4 + wave;
+	if (m >= n_pieces) return;
+	const uint64_t p0 = m * GZ_CRC_PIECE;
+	const uint32_t size = total - p0 < GZ_CRC_PIECE ? (uint32_t)(total - p0) : GZ_CRC_PIECE;
+	const uint8_t *t = text + p0;
+	const uint32_t piece = (size + 63u) / 64u;
+	const uint32_t b = lane * piece < size ? lane * piece : size, e = b + piece < size ? b + piece : size;
+	uint32_t crc = 0xffffffffu;
+	for (uint32_t p = b; p < e; ++p) crc = s_crc[(crc ^ t[p]) & 255u] ^ (crc >> 8);
+	crc = ~crc;
+	crc = inf_mulmod(crc, inf_xpow8(size - e));
+	for (int o = 32; o > 0; o >>= 1) crc ^= __shfl_xor(crc, o, 64);
+	if (lane == 0) pc[m] = inf_mulmod(crc, inf_xpow8_64(total - p0 - size));
+}
+
+extern "C" int ma_gzip_head(int fd, const void *mem, uint64_t nbytes, uint64_t *hdr_len, uint32_t *crc, uint32_t *isize);
+extern "C" size_t ma_gzip_chunk(void);
+
+static void gzip_report(mahip_ctx *c, const mahip_gzip_info_t *info)
+{
+	c->gzip_last = *info;
+	if (ma_timing_level() < 1) return;
+	fprintf(stderr, "[T::gzip] reader=%s reason=%d (%s) item=%lld chunks=%llu (%llu B each, %llu synced) items=%llu %.1f MB -> %.1f MB: upload %.3f sync+count %.3f decode %.3f windows %.3f resolve %.3f crc %.3f ms\n",
+	        info->reader == MAHIP_BGZF_DEVICE ? "device" : "host", info->reason, mahip_gzip_reason_name(info->reason), (long long)info->first_bad_item, (unsigned long long)info->n_chunks,
+	        (unsigned long long)info->chunk, (unsigned long long)info->n_synced, (unsigned long long)info->n_items, (double)info->comp_bytes / 1e6, (double)info->text_bytes / 1e6, info->laps_ms[0],
+	        info->laps_ms[1], info->laps_ms[2], info->laps_ms[3], info->laps_ms[4], info->laps_ms[5]);
+}
+
+// the rows -> the chain (host; a few thousand rows).  Follows end_bit from chunk 0; returns the reason, *bad = the chain item it is about.
+static int gzip_chain(mahip_gzip_item_t *rows, uint64_t n_chunks, uint64_t CB, uint64_t hdr_len, uint64_t nbytes, uint32_t isize, gz_chain_t *chain, uint64_t *n_items, uint64_t *total, int64_t *bad)
+{
+	uint64_t cur = 0, n = 0, tot = 0;
+	int reason = MAHIP_GZIP_OK;
+	*bad = -1;
+	for (;;) {
+		mahip_gzip_item_t &r = rows[cur];
+		r.flags |= MAHIP_GZIP_ON_CHAIN;
+		chain[n].sync_bit = (uint64_t)r.sync_bit; chain[n].end_bit = r.end_bit; chain[n].out_off = tot; chain[n].out_len = r.out_len;
+		++n;
+		if (r.status) { reason = (int)r.status; *bad = (int64_t)n - 1; break; }
+		tot += r.out_len;
+		if (r.flags & MAHIP_GZIP_SAW_FINAL) {
+			if (hdr_len + (r.end_bit + 7) / 8 + 8 != nbytes) { reason = MAHIP_GZIP_MULTI_MEMBER; *bad = (int64_t)n - 1; }
+			break;
+		}
+		const uint64_t next = r.end_bit / CB;
+		if (next <= cur || next >= n_chunks || rows[next].sync_bit != (int64_t)r.end_bit) { reason = MAHIP_GZIP_SYNC_MISMATCH; *bad = (int64_t)n; break; } // (the first two cannot be: an item ends at a block start in a later chunk)
+		cur = next;
+	}
+	if (reason == MAHIP_GZIP_OK && (uint32_t)tot != isize) reason = MAHIP_GZIP_ISIZE;
+	*n_items = n; *total = tot;
+	return reason;
+}
+
+// as bgzf_run.  chunk 0: MA_GZIP_CHUNK or the default.
+static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int target, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	memset(info, 0, sizeof(*info));
+	info->reader = MAHIP_BGZF_HOST; info->first_bad_item = -1; info->comp_bytes = nbytes;
+	if (chunk == 0) chunk = ma_gzip_chunk();
+	if (chunk < 1024 || chunk > GZ_CHUNK_MAX || (chunk & (chunk - 1))) { mahip_set_error("mahip_gzip_load: chunk size %zu is not a power of two in 1024 .. %zu", chunk, GZ_CHUNK_MAX); return -1; }
+	info->chunk = chunk;
+	free(c->gzip_rows); c->gzip_rows = nullptr; c->gzip_n_rows = 0;
+	uint64_t hdr_len = 0;
+	uint32_t crc = 0, isize = 0;
+	double t0 = bg_now(), t1;
+	const int hr = ma_gzip_head(fd, mem, nbytes, &hdr_len, &crc, &isize);
+	if (hr < 0) { mahip_set_error("mahip_gzip_load: cannot read the compressed input"); return -1; }
+	info->reason = hr;
+	if (hr != MAHIP_GZIP_OK) { gzip_report(c, info); return 0; }
+	const uint64_t payload_len = nbytes - hdr_len - 8, n_chunks = payload_len ? (payload_len + chunk - 1) / chunk : 1, CB = (uint64_t)chunk * 8;
+	info->n_chunks = n_chunks;
+	DevBuf d_comp, d_rows, d_chain, d_sym, d_W, d_pc, d_res, d_own;
+	void *d_text = nullptr;
+	mahip_gzip_item_t *rows = (mahip_gzip_item_t*)malloc((size_t)n_chunks * sizeof(*rows));
+	gz_chain_t *chain = (gz_chain_t*)malloc((size_t)(n_chunks + 1) * sizeof(*chain));
+	uint32_t *h_pc = nullptr;
+	uint64_t n_items = 0, total = 0, n_pieces = 0;
+	int rc = 0;
+	bool said = false; // the error message is set
+	if (rows == nullptr || chain == nullptr) { free(rows); free(chain); mahip_set_error("mahip_gzip_load: out of host memory"); return -1; }
+	if (dev_reserve(c, d_comp, nbytes + 64) != 0 || dev_reserve(c, d_rows, (size_t)n_chunks * sizeof(*rows)) != 0 || dev_reserve(c, d_res, GZ_RES_WORDS * 8) != 0) info->reason = MAHIP_GZIP_NOMEM;
+	do { // (one pass; `break` with rc = -1: a real error; with rc = 0: done, info->reason says how)
+		if (info->reason != MAHIP_GZIP_OK) break;
+		const uint8_t *payload = (const uint8_t*)d_comp.p + hdr_len;
+		rc = -1;
+		if ((fd >= 0 ? xfer_from_fd(c, d_comp.p, fd, nbytes) : xfer_copy(c, d_comp.p, (void*)mem, nbytes, 1)) != 0) break;
+		if (hipMemsetAsync(d_res.p, 0, GZ_RES_WORDS * 8, c->st) != hipSuccess || hipMemsetAsync(d_res.p, 0xff, 8, c->st) != hipSuccess) break;
+		if (hipStreamSynchronize(c->st) != hipSuccess) break;
+		info->laps_ms[0] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		{
+			ProfScope ps(c, "k_gz_sync_count", (double)payload_len);
+			hipLaunchKernelGGL(k_gz_sync_count, dim3((unsigned)((n_chunks + GZ_CNT_WAVES - 1) / GZ_CNT_WAVES)), dim3(256), 0, c->st, payload, payload_len, (uint64_t)chunk, n_chunks, (mahip_gzip_item_t*)d_rows.p);
+			if (hipGetLastError() != hipSuccess) break;
+		}
+		if (hipMemcpyAsync(rows, d_rows.p, (size_t)n_chunks * sizeof(*rows), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+		for (uint64_t k = 0; k < n_chunks; ++k) info->n_synced += rows[k].sync_bit >= 0;
+		info->reason = gzip_chain(rows, n_chunks, CB, hdr_len, nbytes, isize, chain, &n_items, &total, &info->first_bad_item);
+		chain[n_items].sync_bit = chain[n_items].end_bit = 0; chain[n_items].out_off = total; chain[n_items].out_len = 0;
+		info->n_items = n_items; info->text_bytes = total;
+		info->laps_ms[1] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		rc = 0;
+		if (info->reason != MAHIP_GZIP_OK) break;
+		// the text, the way the reader it is for reserves it (the PAF reader's cap, MA_PAF_MAX_BYTES, counts the inflated bytes)
+		if (target == MAHIP_BGZF_PAF) { if (paf_text_reserve(c, (size_t)total, &d_text) != 0) { rc = -1; said = true; break; } }
+		else if (target == MAHIP_BGZF_FASTX) {
+			if (total == 0) { info->reason = MAHIP_GZIP_EMPTY; break; }
+			if (fx_text_reserve(c, (size_t)total, &d_text) != 0) { info->reason = MAHIP_GZIP_NOMEM; break; }
+		} else {
+			if (out_cap < total) { mahip_set_error("mahip_gzip_inflate_mem: %llu bytes of text, room for %zu", (unsigned long long)total, out_cap); rc = -1; said = true; break; }
+			if (dev_reserve(c, d_own, (size_t)total + 64) != 0) { info->reason = MAHIP_GZIP_NOMEM; break; }
+			d_text = d_own.p;
+		}
+		n_pieces = (total + GZ_CRC_PIECE - 1) / GZ_CRC_PIECE;
+		if (dev_reserve(c, d_chain, (size_t)(n_items + 1) * sizeof(*chain)) != 0 || dev_reserve(c, d_sym, 2 * (size_t)total + 64) != 0 || dev_reserve(c, d_W, (size_t)n_items * GZ_WIN) != 0 ||
+		    dev_reserve(c, d_pc, (size_t)n_pieces * 4 + 64) != 0) { info->reason = MAHIP_GZIP_NOMEM; break; }
+		h_pc = (uint32_t*)malloc((size_t)n_pieces * 4 + 4);
+		rc = -1;
+		if (h_pc == nullptr) break;
+		if (hipMemcpyAsync(d_chain.p, chain, (size_t)(n_items + 1) * sizeof(*chain), hipMemcpyHostToDevice, c->st) != hipSuccess) break;
+		if (hipMemsetAsync(d_W.p, 0, GZ_WIN, c->st) != hipSuccess) break;
+		unsigned long long h_res[GZ_RES_WORDS];
+		{
+			ProfScope ps(c, "k_gz_decode", (double)payload_len + 2.0 * (double)total);
+			hipLaunchKernelGGL(k_gz_decode, dim3((unsigned)((n_items + GZ_DEC_WAVES - 1) / GZ_DEC_WAVES)), dim3(128), 0, c->st, payload, payload_len, (uint64_t)chunk, (const gz_chain_t*)d_chain.p, n_items,
+			                   (uint16_t*)d_sym.p, P<unsigned long long>(d_res));
+			if (hipGetLastError() != hipSuccess) break;
+		}
+		if (hipMemcpyAsync(h_res, d_res.p, GZ_RES_WORDS * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+		info->laps_ms[2] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		info->n_stored = h_res[GZ_RES_STORED]; info->n_fixed = h_res[GZ_RES_FIXED]; info->n_dynamic = h_res[GZ_RES_DYNAMIC];
+		if (h_res[GZ_RES_BAD] != ~0ull) { info->reason = (int)(h_res[GZ_RES_BAD] & 255u); info->first_bad_item = (int64_t)(h_res[GZ_RES_BAD] >> 8); rc = 0; break; }
+		{
+			ProfScope ps(c, "k_gz_windows", 3.0 * (double)n_items * GZ_WIN);
+			hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(256), 0, c->st, (const gz_chain_t*)d_chain.p, n_items, (const uint16_t*)d_sym.p, (uint8_t*)d_W.p);
+			if (hipGetLastError() != hipSuccess) break;
+		}
+		if (hipStreamSynchronize(c->st) != hipSuccess) break;
+		info->laps_ms[3] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		if (total) {
+			ProfScope ps(c, "k_gz_resolve", 3.0 * (double)total);
+			hipLaunchKernelGGL(k_gz_resolve, dim3((unsigned)((total + GZ_TILE - 1) / GZ_TILE)), dim3(256), 0, c->st, (const gz_chain_t*)d_chain.p, n_items, (const uint16_t*)d_sym.p, (const uint8_t*)d_W.p,
+			                   (uint8_t*)d_text, total);
+			if (hipGetLastError() != hipSuccess) break;
+		}
+		if (hipStreamSynchronize(c->st) != hipSuccess) break;
+		info->laps_ms[4] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		uint32_t got = 0;
+		if (n_pieces) {
+			{
+				ProfScope ps(c, "k_gz_crc", (double)total);
+				hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, c->st, (const uint8_t*)d_text, total, n_pieces, (uint32_t*)d_pc.p);
+				if (hipGetLastError() != hipSuccess) break;
+			}
+			if (hipMemcpyAsync(h_pc, d_pc.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+			for (uint64_t m = 0; m < n_pieces; ++m) got ^= h_pc[m];
+		}
+		info->laps_ms[5] = (bg_now() - t0) * 1e3;
+		rc = 0;
+		if (got != crc) { info->reason = MAHIP_GZIP_CRC; break; }
+		if (target == 0 && total) rc = xfer_copy(c, d_text, out, (size_t)total, 0);
+	} while (0);
+	if (rc != 0 && !said) mahip_set_error("mahip_gzip_load: upload, launch or copy failed (%s)", hipGetErrorString(hipGetLastError()));
+	(void)hipStreamSynchronize(c->st);
+	dev_free(c, d_comp); dev_free(c, d_rows); dev_free(c, d_chain); dev_free(c, d_sym); dev_free(c, d_W); dev_free(c, d_pc); dev_free(c, d_res); dev_free(c, d_own);
+	free(chain); free(h_pc);
+	c->gzip_rows = rows; c->gzip_n_rows = info->laps_ms[1] > 0 ? n_chunks : 0; // (rows that were never downloaded are not rows)
+	if (rc == 0 && info->reason == MAHIP_GZIP_OK) {
+		info->reader = MAHIP_BGZF_DEVICE;
+		if (target == MAHIP_BGZF_PAF) paf_text_loaded(c); else if (target == MAHIP_BGZF_FASTX) fx_text_loaded(c);
+	} else { // nothing stays loaded: the caller inflates with zlib
+		if (target == MAHIP_BGZF_PAF) (void)mahip_paf_release(c); else if (target == MAHIP_BGZF_FASTX) (void)mahip_fastx_release(c);
+	}
+	if (rc == 0) gzip_report(c, info); else c->gzip_last = *info;
+	return rc;
+}
+
+extern "C" int mahip_gzip_load_fd(mahip_ctx_t *c, int fd, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
+{
+	if (target != MAHIP_BGZF_PAF && target != MAHIP_BGZF_FASTX) { mahip_set_error("mahip_gzip_load_fd: target %d", target); return -1; }
+	return gzip_run(c, fd, nullptr, nbytes, target, chunk, nullptr, 0, info);
+}
+extern "C" int mahip_gzip_load_mem(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
+{
+	if (target != MAHIP_BGZF_PAF && target != MAHIP_BGZF_FASTX) { mahip_set_error("mahip_gzip_load_mem: target %d", target); return -1; }
+	return gzip_run(c, -1, comp, nbytes, target, chunk, nullptr, 0, info);
+}
+extern "C" int mahip_gzip_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info) { return gzip_run(c, -1, comp, ncomp, 0, chunk, out, out_cap, info); }
+extern "C" int mahip_gzip_last(mahip_ctx_t *c, mahip_gzip_info_t *out) { *out = c->gzip_last; return 0; }
+extern "C" void mahip_gzip_note(mahip_ctx_t *c, const mahip_gzip_info_t *in) { c->gzip_last = *in; }
+extern "C" uint64_t mahip_gzip_items_download(mahip_ctx_t *c, mahip_gzip_item_t *out, uint64_t cap)
+{
+	const uint64_t n = c->gzip_n_rows < cap ? c->gzip_n_rows : cap;
+	if (n) memcpy(out, c->gzip_rows, (size_t)n * sizeof(*out));
+	return n;
+}
+extern "C" const char *mahip_gzip_reason_name(int reason)
+{
+	static const char *const nm[] = {"ok", "not a gzip header this reader takes", "more than one member, or trailing bytes", "no block start within the span", "an item ends where the next does not start",
+	                                 "the items' total is not ISIZE", "block type 3", "stored block: LEN does not match NLEN", "invalid code lengths", "invalid symbol", "a distance reaches in front of the stream",
+	                                 "more output than counted", "the deflate bytes end early", "less output than counted", "CRC mismatch", "not enough device memory", "not a regular file", "MA_GZIP_DEVICE is off", "no text"};
+	return reason >= 0 && reason < (int)(sizeof(nm) / sizeof(nm[0])) ? nm[reason] : "?";
+}

@@ -2,7 +2,8 @@
  *
  * The host only moves bytes: a plain file goes from the page cache straight into pinned staging slots and on to
  * HBM (mahip_paf_load_fd); a bgzip-compressed (BGZF) file goes to HBM as it is and is inflated there, one wave per block (mahip_bgzf_load_fd; the walk over
- * its member chain is below); plain gzip / stdin input is inflated into memory first (zlib, as the reference does through gzread) and uploaded.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
+ * its member chain is below); a plain gzip file can be cut into chunks and inflated there too (MA_GZIP_DEVICE=1: mahip_gzip_load_fd; its header and trailer are
+ * read below); otherwise gzip / stdin input is inflated into memory first (zlib, as the reference does through gzread) and uploaded.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
  * first-appearance ids and the (mirrored) hit records are all produced by csrc/paf.hip; what comes back is the
  * dictionary (names + first-seen lengths, R entries) and, only for the per-symbol ABI, the records.
  * The -R pre-filter (ma_hit_no_cont, hit.c:38-68) rides in the same parse: the exclusion is a flag per name.
@@ -123,6 +124,69 @@ int ma_bgzf_walk(int fd, const void *mem, uint64_t nbytes, mahip_bgzf_member_t *
 	return MAHIP_BGZF_OK;
 }
 
+/* ---- plain gzip: the header and the trailer of the FIRST member (RFC 1952); whether it is the only one the device finds out (include/mahip.h).
+ * returns MAHIP_GZIP_OK (*hdr_len = where the deflate stream starts; the trailer's CRC32 and ISIZE) or MAHIP_GZIP_BAD_HEADER; -1 on a read error */
+int ma_gzip_head(int fd, const void *mem, uint64_t nbytes, uint64_t *hdr_len, uint32_t *crc, uint32_t *isize)
+{
+	bg_src_t src;
+	unsigned char h[12], b[8];
+	uint64_t p = 10;
+	int k;
+	memset(&src, 0, sizeof(src));
+	src.fd = fd; src.mem = (const unsigned char*)mem; src.n = nbytes;
+	*hdr_len = 0; *crc = *isize = 0;
+	if (nbytes < 10 + 8) return MAHIP_GZIP_BAD_HEADER;
+	if (bg_get(&src, 0, 10, h) != 0) return -1;
+	if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xe0)) return MAHIP_GZIP_BAD_HEADER; /* CM 8; FLG bits 5..7 are reserved */
+	if (h[3] & 4) { /* FEXTRA: skipped, unless a `BC` subfield says that this is BGZF's business */
+		uint64_t x, xend;
+		if (nbytes - p < 2) return MAHIP_GZIP_BAD_HEADER;
+		if (bg_get(&src, p, 2, b) != 0) return -1;
+		x = p + 2; xend = x + ((uint64_t)b[0] | (uint64_t)b[1] << 8);
+		if (xend > nbytes) return MAHIP_GZIP_BAD_HEADER;
+		while (xend - x >= 4) {
+			uint32_t slen;
+			if (bg_get(&src, x, 4, b) != 0) return -1;
+			slen = (uint32_t)b[2] | (uint32_t)b[3] << 8;
+			if (xend - x - 4 < slen) break;
+			if (b[0] == 'B' && b[1] == 'C' && slen == 2) return MAHIP_GZIP_BAD_HEADER;
+			x += 4 + slen;
+		}
+		p = xend;
+	}
+	for (k = 0; k < 2; ++k) /* FNAME, FCOMMENT: zero-terminated */
+		if (h[3] & (k == 0 ? 8 : 16)) {
+			for (;;) {
+				if (p >= nbytes) return MAHIP_GZIP_BAD_HEADER;
+				if (bg_get(&src, p, 1, b) != 0) return -1;
+				++p;
+				if (b[0] == 0) break;
+			}
+		}
+	if (h[3] & 2) p += 2; /* FHCRC */
+	if (p > nbytes || nbytes - p < 8) return MAHIP_GZIP_BAD_HEADER;
+	if (bg_get(&src, nbytes - 8, 8, b) != 0) return -1;
+	*hdr_len = p; *crc = bg_le32(b); *isize = bg_le32(b + 4);
+	return MAHIP_GZIP_OK;
+}
+
+/* MA_GZIP_CHUNK: bytes of payload per chunk, a power of two in 1024 .. 16 MiB; anything else is the default */
+size_t ma_gzip_chunk(void)
+{
+	const char *s = getenv("MA_GZIP_CHUNK");
+	long long v = s ? atoll(s) : 0;
+	if (v >= 1024 && v <= (16ll << 20) && (v & (v - 1)) == 0) return (size_t)v;
+	return MAHIP_GZIP_CHUNK_DEFAULT;
+}
+
+/* MA_GZIP_DEVICE=0|1: plain gzip files on the device road; unset: MA_GZIP_DEVICE_DEFAULT (DESIGN 7 has the measurement it follows from) */
+#define MA_GZIP_DEVICE_DEFAULT 0
+int ma_gzip_device_enabled(void)
+{
+	const char *s = getenv("MA_GZIP_DEVICE");
+	return s && *s ? atoi(s) != 0 : MA_GZIP_DEVICE_DEFAULT;
+}
+
 int ma_bgzf_enabled(void)
 {
 	const char *s = getenv("MA_BGZF_HOST");
@@ -208,6 +272,18 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 			} else {
 				if (mahip_bgzf_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, &bi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
 				if (bi.reason == MAHIP_BGZF_OK) { close(fd); return 0; }
+				if (bi.reason == MAHIP_BGZF_NOT_BGZF) { /* plain gzip: one deflate stream, cut into chunks on the device (include/mahip.h); any reason leaves it to zlib */
+					mahip_gzip_info_t gi;
+					if (!ma_gzip_device_enabled()) {
+						memset(&gi, 0, sizeof(gi));
+						gi.reader = MAHIP_BGZF_HOST; gi.reason = MAHIP_GZIP_FORCED; gi.first_bad_item = -1; gi.comp_bytes = (uint64_t)st.st_size;
+						mahip_gzip_note(c, &gi);
+						if (ma_timing_level() >= 1) fprintf(stderr, "[T::gzip] reader=host reason=%d (%s) item=-1 chunks=0 items=0\n", gi.reason, mahip_gzip_reason_name(gi.reason));
+					} else {
+						if (mahip_gzip_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, 0, &gi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
+						if (gi.reason == MAHIP_GZIP_OK) { close(fd); return 0; }
+					}
+				}
 			}
 		}
 		fp = fd >= 0 ? gzdopen(fd, "r") : gzdopen(fileno(stdin), "r");

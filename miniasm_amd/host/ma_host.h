@@ -75,6 +75,8 @@ int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict
 int ma_paf_load_file(mahip_ctx_t *c, const char *fn); /* plain / gzip / "-": text into HBM */
 int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release);
 int ma_gpu_parse_enabled(void); /* 0 when MA_HOST_PARSE=1 */
+int ma_gzip_device_enabled(void); /* MA_GZIP_DEVICE: plain gzip files are cut into chunks and inflated on the device (ingest_gpu.c) */
+size_t ma_gzip_chunk(void);       /* MA_GZIP_CHUNK or the default */
 int ma_bgzf_enabled(void);      /* 0 when MA_BGZF_HOST=1: bgzip'ed input is inflated by zlib on the host */
 /* the member chain of a BGZF file (fd >= 0) or image (mem) -> the block table of include/mahip.h; returns a MAHIP_BGZF_* reason, -1 on a read error */
 int ma_bgzf_walk(int fd, const void *mem, uint64_t nbytes, mahip_bgzf_member_t **tab, uint64_t *n_members, uint64_t *n_empty, uint64_t *text_bytes, int64_t *bad);

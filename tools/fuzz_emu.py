@@ -11,7 +11,9 @@ import random
 import re
 import subprocess
 import sys
+import struct
 import tempfile
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "miniasm_ref")
@@ -186,8 +188,31 @@ def write_reads(rng, paf, path):
         open(path, "wb").write(data)
 
 
+def write_gzip(rng, data, path):
+    """`data` as ONE plain gzip member the way no single tool writes it: random level, memLevel, strategy, sync / full flush points and header fields"""
+    flg = rng.choice([0, 0, 8, 1, 2, 4, 16, 8 | 16, 2 | 4 | 8 | 16])
+    h = b"\x1f\x8b\x08" + bytes([flg]) + struct.pack("<I", rng.choice([0, 1700000000])) + b"\x00\x03"
+    if flg & 4:
+        h += struct.pack("<H", 9) + b"XY" + struct.pack("<H", 5) + b"abcde"
+    if flg & 8:
+        h += b"f.paf\0"
+    if flg & 16:
+        h += b"made by fuzz_emu\0"
+    if flg & 2:
+        h += struct.pack("<H", zlib.crc32(h) & 0xffff)
+    co = zlib.compressobj(rng.randint(0, 9), zlib.DEFLATED, -15, rng.randint(1, 9), rng.choice([zlib.Z_DEFAULT_STRATEGY, zlib.Z_DEFAULT_STRATEGY, zlib.Z_FIXED, zlib.Z_HUFFMAN_ONLY, zlib.Z_RLE]))
+    cuts = sorted(rng.randrange(len(data) + 1) for _ in range(rng.choice([0, 0, 1, 3, 10])))
+    body, last = b"", 0
+    for c in cuts:
+        body += co.compress(data[last:c]) + co.flush(rng.choice([zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH]))
+        last = c
+    body += co.compress(data[last:]) + co.flush()
+    open(path, "wb").write(h + body + struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gzip", action="store_true", help="every case also runs on its PAF text as a plain gzip file (random level, memLevel, strategy, flush points, header fields) with MA_GZIP_DEVICE=1 and a random MA_GZIP_CHUNK: the chunked device inflater; the road taken is tallied by reason")
     ap.add_argument("--seq", action="store_true", help="unitig sequences: every case also gets a random reads file and runs with -f (ma_ug_seq; the device byte gather)")
     ap.add_argument("--text", action="store_true", help="damage the PAF text (reader / dictionary semantics) instead of varying the options")
     ap.add_argument("--cases", type=int, default=100)
@@ -231,6 +256,9 @@ def main():
             skipped += 1
             continue
         runs = [("emu", {})]
+        if a.gzip:
+            write_gzip(rng, open(paf, "rb").read(), paf + ".gz")
+            runs.append(("emu gzip", {"MA_GZIP_DEVICE": "1", "MA_GZIP_CHUNK": str(1024 << rng.randint(0, 6)), "FILE": paf + ".gz"}))
         if a.seq:  # the same case with the host reader of the reads file: both must equal the reference
             runs.append(("emu host reader", {"MA_FASTX_HOST": "1"}))
         if a.ranks > 1:  # requests the sharded head does not serve fall back to one GPU: the bytes must be the same either way
@@ -238,8 +266,12 @@ def main():
         for name, env in runs:
             env = dict(env, MA_PIPE_TIMING="1")  # the [T::ties] line: which tie path the run took
             env.update(kv.split("=", 1) for kv in a.env)
-            rc1, out1, err1 = run(EMU, args, paf, env)
+            rc1, out1, err1 = run(EMU, args, env.pop("FILE", paf), env)
             for ln in err1.decode(errors="replace").splitlines():
+                if ln.startswith("[T::gzip]"):
+                    mm = re.search(r"reader=(\w+) reason=\d+ \(([^)]*)\)", ln)
+                    key = "gzip: %s (%s)" % (mm.group(1), mm.group(2))
+                    readers[key] = readers.get(key, 0) + 1
                 if ln.startswith("[T::ug_seq]") and name == "emu":  # which reader the reads file took (and why the host reader ran)
                     mm = re.search(r"reader=(\w+)(?: reason=(\d+))?", ln)
                     key = "reads file: %s%s" % (mm.group(1), " (reason %s)" % mm.group(2) if mm.group(2) else "")
@@ -263,8 +295,8 @@ def main():
         if (k + 1) % 20 == 0:
             print("%d cases, %d mismatches" % (k + 1, bad), flush=True)
     print("tie paths taken:", paths)
-    if a.seq:
-        print("reads-file readers taken:", readers)
+    if a.seq or a.gzip:
+        print("readers taken:", readers)
     print("done: %d cases, %d mismatches, %d skipped (reference crashed)" % (a.cases, bad, skipped))
     sys.exit(1 if bad else 0)
 
