@@ -145,6 +145,16 @@ int mahip_hits_layout_download(mahip_ctx_t *c, uint32_t *sidx, uint32_t *goff);
  * Synchronous; ordered after the work already queued on the context's stream.  MA_XFER_THREADS sets the workers. */
 int mahip_memcpy_h2d(mahip_ctx_t *c, void *d_dst, const void *h_src, size_t bytes);
 int mahip_memcpy_d2h(mahip_ctx_t *c, void *h_dst, const void *d_src, size_t bytes);
+/* for stage tests: bytes [off, off + nbytes) of an open file -> device memory at d_dst, the road the PAF / reads-file loaders take (pread into the workers'
+ * pinned slots; staged at every size).  -1 when the file ends early; what d_dst holds then is undefined, nothing of the copy is still in flight. */
+int mahip_memcpy_fd2d(mahip_ctx_t *c, void *d_dst, int fd, size_t off, size_t nbytes);
+/* for stage tests: what the LAST bulk copy of this context did (host bookkeeping, read-only; any copy the library made through the staged-copy code counts,
+ * its own uploads and downloads included).  road: the runtime's own hipMemcpyAsync (memory to memory below 8 MiB), or staged through the workers' pinned 4 MiB
+ * slots from memory / from a file.  slices: 4 MiB slices (0 on the runtime road); workers: threads that dealt them (0 on the runtime road).  A copy of 0 bytes
+ * does nothing and is not recorded. */
+enum { MAHIP_XFER_NONE = 0, MAHIP_XFER_RUNTIME = 1, MAHIP_XFER_STAGED_MEM = 2, MAHIP_XFER_STAGED_FILE = 3 };
+typedef struct { int road, to_device; uint64_t bytes, slices; int workers; } mahip_xfer_info_t;
+int mahip_xfer_last(mahip_ctx_t *c, mahip_xfer_info_t *out);
 /* Tie order.  The reference's two sorts (ksort.h:134-183, used at hit.c:21 and asg.c:24) are an in-place MSD radix sort that
  * leaves records with equal keys in an order that is a sequential function of the whole input; the device sorts are stable.
  * The difference is only observable through arcs with equal (u,len) keys, so:
@@ -403,6 +413,10 @@ uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
  * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */
 enum { MAHIP_SCAN_ONE_TILE = 0, MAHIP_SCAN_CHAINED = 1, MAHIP_SCAN_THREE_PHASE = 2 };
 void mahip_scan_forms(mahip_ctx_t *c, uint64_t out[3]);
+/* for stage tests: the device-wide exclusive prefix sum (mod 2^32) of d_in[0 .. n) -> d_out[0 .. n), queued on the context's stream.  d_out may equal d_in
+ * (in place; no other overlap); d_total may be NULL, else the sum of all n elements is written there (0 for n = 0).  PRECONDITION: d_in and d_out are 16-byte
+ * aligned (full groups of eight elements are moved as two 16-byte words).  Nothing at or behind element n is written. */
+int mahip_scan_u32(mahip_ctx_t *c, const uint32_t *d_in, uint32_t *d_out, size_t n, uint32_t *d_total);
 /* iterations of the inner loop of asg_arc_del_trans (asg.c:169) in the last reduction this context ran, counted on the device: SURVEY 8(d) prices the
  * reduction at 16 (A + I) bytes (bench.py: roofline.reduce_group) */
 uint64_t mahip_asg_trans_inner(mahip_ctx_t *c);

@@ -144,6 +144,13 @@ PAF_DICT_FORMS = {0: None, 1: "short", 2: "text"}  # MAHIP_PAF_DICT_*
 PAF_TAB_ENDS = {0: "ok", 1: "load", 2: "probes"}   # MAHIP_PAF_TAB_*
 
 
+class XferInfo(C.Structure):  # include/mahip.h: mahip_xfer_info_t
+    _fields_ = [("road", C.c_int), ("to_device", C.c_int), ("bytes", C.c_uint64), ("slices", C.c_uint64), ("workers", C.c_int)]
+
+
+XFER_ROADS = {0: None, 1: "runtime", 2: "staged_mem", 3: "staged_file"}  # MAHIP_XFER_*
+
+
 class ProfRec(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -184,6 +191,9 @@ def lib():
         L.mahip_tie_stats.argtypes = [vp, C.POINTER(TieInfo)]
         L.mahip_memcpy_h2d.argtypes = [vp, vp, vp, sz]
         L.mahip_memcpy_d2h.argtypes = [vp, vp, vp, sz]
+        L.mahip_memcpy_fd2d.argtypes = [vp, vp, i32, sz, sz]
+        L.mahip_xfer_last.argtypes = [vp, C.POINTER(XferInfo)]
+        L.mahip_scan_u32.argtypes = [vp, vp, vp, sz, vp]
         L.mahip_paf_release.argtypes = [vp]
         L.mahip_hits_sorted_runs.restype = C.c_uint64
         L.mahip_hits_sorted_runs.argtypes = [vp]
@@ -540,6 +550,27 @@ class Ctx:
         out = (C.c_uint64 * 3)()
         lib().mahip_scan_forms(self.h, C.byref(out))
         return tuple(out)
+
+    def scan_u32(self, d_in, d_out, n, d_total=None):
+        """for stage tests: the device-wide exclusive scan on device addresses (ints); d_out may equal d_in, d_total may be None.  Queued, not waited for."""
+        _chk(lib().mahip_scan_u32(self.h, d_in, d_out, n, d_total), "scan_u32")
+
+    # ---- bulk copies (csrc/xfer.hip): for stage tests
+    def memcpy_h2d(self, dptr, host_addr, nbytes):
+        return lib().mahip_memcpy_h2d(self.h, dptr, host_addr, nbytes)
+
+    def memcpy_d2h(self, host_addr, dptr, nbytes):
+        return lib().mahip_memcpy_d2h(self.h, host_addr, dptr, nbytes)
+
+    def memcpy_fd2d(self, dptr, fd, off, nbytes):
+        """bytes [off, off + nbytes) of an open file -> device memory; returns the C return code (-1: the file ended early)"""
+        return lib().mahip_memcpy_fd2d(self.h, dptr, fd, off, nbytes)
+
+    def xfer_last(self):
+        """what the context's last bulk copy did: dict(road, to_device, bytes, slices, workers)"""
+        x = XferInfo()
+        _chk(lib().mahip_xfer_last(self.h, C.byref(x)), "xfer_last")
+        return dict(road=XFER_ROADS[x.road], to_device=bool(x.to_device), bytes=x.bytes, slices=x.slices, workers=x.workers)
 
     # ---- instrumentation
     def prof_enable(self, on=True):

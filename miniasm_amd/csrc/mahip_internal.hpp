@@ -124,6 +124,7 @@ struct mahip_ctx {
 	unsigned long long ctr_seq = 0;
 	uint32_t scan_ticket = 0, scan_epoch = 0; // scan.hip: tickets handed out so far, launch number
 	void *xfer = nullptr;      // staged-copy worker pool (xfer.hip)
+	mahip_xfer_info_t xfer_last = {}; // what the last bulk copy did (xfer.hip: mahip_xfer_last)
 	void *paf = nullptr;       // text-ingest buffers (paf.hip)
 	bool paf_keep_odd = false; // mahip_paf_keep_odd: the next parses keep a host snapshot of the lines left to the byte-wise parser (tests)
 	mahip_bgzf_info_t bgzf_last = {}; // what the last BGZF load decided (xfer.hip: mahip_bgzf_last)

@@ -195,3 +195,8 @@ int scan_exclusive_u32(mahip_ctx *c, const uint32_t *in, uint32_t *out, size_t n
 }
 
 extern "C" void mahip_scan_forms(mahip_ctx_t *c, uint64_t out[3]) { for (int k = 0; k < 3; ++k) out[k] = c->scan_forms[k]; } // tests: which form did a size take?
+extern "C" int mahip_scan_u32(mahip_ctx_t *c, const uint32_t *d_in, uint32_t *d_out, size_t n, uint32_t *d_total) // for stage tests: the scan on a caller's pointers
+{
+	HIPCHK(hipSetDevice(c->dev));
+	return scan_exclusive_u32(c, d_in, d_out, n, d_total);
+}

@@ -112,6 +112,7 @@ static int xfer_run(mahip_ctx *c, void *dev_ptr, void *host_ptr, int fd, size_t 
 	if (bytes == 0) return 0;
 	HIPCHK(hipSetDevice(c->dev));
 	if (fd < 0 && bytes < (8u << 20)) { // small: the runtime's own path
+		c->xfer_last = { MAHIP_XFER_RUNTIME, to_device, (uint64_t)bytes, 0, 0 };
 		HIPCHK(hipMemcpyAsync(to_device ? dev_ptr : host_ptr, to_device ? host_ptr : dev_ptr, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, c->st));
 		HIPCHK(hipStreamSynchronize(c->st));
 		return 0;
@@ -119,6 +120,7 @@ static int xfer_run(mahip_ctx *c, void *dev_ptr, void *host_ptr, int fd, size_t 
 	int W = xfer_workers(to_device);
 	const size_t n_slices = (bytes + XF_SLOT - 1) / XF_SLOT;
 	if ((size_t)W > n_slices) W = (int)n_slices;
+	c->xfer_last = { fd >= 0 ? MAHIP_XFER_STAGED_FILE : MAHIP_XFER_STAGED_MEM, to_device, (uint64_t)bytes, (uint64_t)n_slices, W };
 	CHK(xfer_pool_init(c, W));
 	XferJob job[XF_MAX_WORKERS];
 	pthread_t th[XF_MAX_WORKERS];
@@ -142,7 +144,13 @@ static int xfer_run(mahip_ctx *c, void *dev_ptr, void *host_ptr, int fd, size_t 
 		double dt = (double)(ts1.tv_sec - ts0.tv_sec) + 1e-9 * (double)(ts1.tv_nsec - ts0.tv_nsec);
 		fprintf(stderr, "[T::xfer] %s %.0f MB, %d workers: %.3f s (%.1f GB/s)\n", fd >= 0 ? "file->HBM" : to_device ? "host->HBM" : "HBM->host", (double)bytes / 1e6, W, dt, (double)bytes / dt / 1e9);
 	}
-	if (rc) { mahip_set_error("xfer_copy: staged copy failed (%s)", hipGetErrorString(hipGetLastError())); return -1; }
+	if (rc) {
+		mahip_set_error("xfer_copy: staged copy failed (%s)", hipGetErrorString(hipGetLastError()));
+		// a worker that failed returned without its final wait, and the others may have waited before it queued its last DMA: that DMA may still be reading a
+		// pinned slot, which the next copy's first two slices per worker refill without looking at the slot's event
+		(void)hipStreamSynchronize(c->st);
+		return -1;
+	}
 	return 0;
 }
 
@@ -154,6 +162,8 @@ int xfer_from_fd_at(mahip_ctx *c, void *dev_ptr, int fd, size_t off, size_t byte
 
 extern "C" int mahip_memcpy_h2d(mahip_ctx_t *c, void *d_dst, const void *h_src, size_t bytes) { return xfer_copy(c, d_dst, (void*)h_src, bytes, 1); }
 extern "C" int mahip_memcpy_d2h(mahip_ctx_t *c, void *h_dst, const void *d_src, size_t bytes) { return xfer_copy(c, (void*)d_src, h_dst, bytes, 0); }
+extern "C" int mahip_memcpy_fd2d(mahip_ctx_t *c, void *d_dst, int fd, size_t off, size_t nbytes) { return xfer_from_fd_at(c, d_dst, fd, off, nbytes); } // for stage tests
+extern "C" int mahip_xfer_last(mahip_ctx_t *c, mahip_xfer_info_t *out) { *out = c->xfer_last; return 0; }                                                // for stage tests
 
 // ================================================================================================ bgzip-compressed input, inflated on the device
 // A BGZF file goes to HBM as it is (xfer_from_fd), the host's block table follows (host/ingest_gpu.c: ma_bgzf_walk), ONE WAVE inflates ONE member into its

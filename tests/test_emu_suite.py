@@ -18,7 +18,10 @@ tests/test_gpu_ingest_edges.py adds about two minutes: 45 s in normal order for 
 4 s together, so none is held back for MA_EMU_FULL) and 58 s reversed with guard pages, both measured while other builds were using the box.
 tests/test_gpu_shard_edges.py adds about three minutes: 71 s in normal order for its 60 tests (about 90 walks of the sharded head on up to eight contexts; the slowest
 test, four walks over the 56 000-record input, takes 7 s, so none is held back for MA_EMU_FULL) and 100 s reversed with guard pages, the latter measured while other
-builds were using the box."""
+builds were using the box.
+tests/test_gpu_xfer_edges.py and tests/test_gpu_scan_edges.py (run by tests/test_xfer_scan_emu.py) add about two minutes: 23 s + 26 s in normal order (70 + 25
+tests; the 132 MiB round trips take about a second each, the three 2048 x 2048-element scan cases 5 to 6 s each, so nothing is held back for MA_EMU_FULL), 43 s
+together reversed with guard pages, and 10 s of build + 13 s of run for the copy workers under the thread sanitizer."""
 import os
 import subprocess
 import sys
