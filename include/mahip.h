@@ -116,6 +116,10 @@ int mahip_hits_raw_extract_pos(mahip_ctx_t *c, uint32_t q_beg, uint32_t q_end, v
  * the hints it describes one upload/adopt.  Without positions such a context leaves tied hits in the stable order and reports `unrepaired`. */
 int mahip_hits_set_positions(mahip_ctx_t *c, const uint32_t *pos, int on_device, uint64_t n_total);
 int mahip_hits_have_positions(mahip_ctx_t *c);
+/* for stage tests: the positions the context holds (one word per record it was handed: as many as mahip_hits_raw_download writes right after the upload /
+ * adopt / route) into out (host, may be NULL), *n_total = what mahip_hits_set_positions or mahip_hits_route said the ranks hold together.  Read-only; fails
+ * when no positions are set. */
+int mahip_hits_positions_download(mahip_ctx_t *c, uint32_t *out, uint64_t *n_total);
 
 /* optional: an upper bound of the query starts (e.g. the longest read) lets the on-demand (qid,qs) sorts (hit dumps, push order
  * of the arcs) plan their digits without a sweep over the records; 0 = unknown */

@@ -201,6 +201,7 @@ def lib():
         L.mahip_paf_load_fd.argtypes = [vp, i32, sz]
         L.mahip_paf_load_mem.argtypes = [vp, vp, sz]
         L.mahip_hits_raw_download.argtypes = [vp, vp]
+        L.mahip_hits_positions_download.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
         L.mahip_paf_parse_excl.argtypes = [vp, i32, i32, i32, i32, i32, C.c_float, C.POINTER(PafInfo)]
         L.mahip_paf_names.argtypes = [vp, vp, vp]
         L.mahip_paf_last.argtypes = [vp, C.POINTER(PafReport)]

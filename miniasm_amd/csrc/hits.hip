@@ -1298,6 +1298,15 @@ extern "C" int mahip_hits_set_positions(mahip_ctx_t *c, const uint32_t *pos, int
 	return 0;
 }
 extern "C" int mahip_hits_have_positions(mahip_ctx_t *c) { return c->n_total != 0; }
+// for stage tests: the positions as the context holds them (n_in words), and what they count up to
+extern "C" int mahip_hits_positions_download(mahip_ctx_t *c, uint32_t *out, uint64_t *n_total)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (c->n_total == 0) { mahip_set_error("mahip_hits_positions_download: no positions set (mahip_hits_set_positions / mahip_hits_route)"); return -1; }
+	if (n_total) *n_total = c->n_total;
+	if (c->n_in == 0 || !out) return 0;
+	return xfer_copy(c, c->gpos.p, out, c->n_in * 4, 0);
+}
 
 extern "C" int mahip_set_hints(mahip_ctx_t *c, uint32_t max_qs)
 {

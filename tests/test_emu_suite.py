@@ -21,7 +21,10 @@ test, four walks over the 56 000-record input, takes 7 s, so none is held back f
 builds were using the box.
 tests/test_gpu_xfer_edges.py and tests/test_gpu_scan_edges.py (run by tests/test_xfer_scan_emu.py) add about two minutes: 23 s + 26 s in normal order (70 + 25
 tests; the 132 MiB round trips take about a second each, the three 2048 x 2048-element scan cases 5 to 6 s each, so nothing is held back for MA_EMU_FULL), 43 s
-together reversed with guard pages, and 10 s of build + 13 s of run for the copy workers under the thread sanitizer."""
+together reversed with guard pages, and 10 s of build + 13 s of run for the copy workers under the thread sanitizer.
+tests/test_gpu_ingest_shard_edges.py adds about three quarters of a minute: 16 s in normal order for its 141 tests (five runs of 2, 3, 5, 8 and 3 child processes, 139
+cases in all: 2.3 s, 2.2 s, 3.0 s, 5.8 s and 0.3 s of wall time, most of it process start-up, so nothing is held back for MA_EMU_FULL) and 26 s reversed with guard
+pages (2.8 s, 2.9 s, 4.9 s, 13.0 s and 0.4 s), both on 16 cores."""
 import os
 import subprocess
 import sys
@@ -90,6 +93,7 @@ def test_kernels_with_reversed_schedule_and_guard_pages(emu_built):
     run_gpu_tests(["tests/test_gpu_ingest_edges.py"], 3000, env)  # the staged over-read in front of a tile, the n + 64 padding of the text, s_lend[256], lstart[L], cnt[n_gran]
     run_gpu_tests(["tests/test_gpu_sort_edges.py"], 3000, env)  # rkey[r00 - 1], the n + 128 padding of sidx, the rows / chunk sums / totals of the radix histograms and the tile minima of the group starts
     run_gpu_tests(["tests/test_gpu_shard_edges.py"], 3000, env)  # the Rr-sized grids of the coverage sweeps and of the arc sort on a read range, goff[q_hi], the stride-padded row blocks of the imports
+    run_gpu_tests(["tests/test_gpu_ingest_shard_edges.py"], 3000, env)  # the stride-padded row and name blocks of the merged dictionary, keep[] / pos[] of the route's extraction, the send and receive buffers of the exchange
 
 
 def test_kernels_graph_api_on_cpu(emu_built):
@@ -115,6 +119,12 @@ def test_shard_edges_on_cpu(emu_built):
     read-range tables with borders at the deep and the many-arc reads, empty ranges, one rank owning every read, a world larger than the dictionary; against
     the oracle, the one-context chain and the reference library"""
     run_gpu_tests(["tests/test_gpu_shard_edges.py"], 1800)
+
+
+def test_ingest_shard_edges_on_cpu(emu_built):
+    """tests/test_gpu_ingest_shard_edges.py: the sharded PAF ingest and the record routing rank by rank -- 2, 3, 5 and 8 child processes over the shared-memory
+    double, each with a context of the CPU build -- against tests/pafmodel.py on the whole text and the stated balance rule; a quarter of a minute"""
+    run_gpu_tests(["tests/test_gpu_ingest_shard_edges.py"], 1800)
 
 
 CLEAN_EDGES_SEL = [] if FULL else ["-k", "not border[3]"]  # the 196 608 / 196 609-entry probes (tiers 3 and 4): MA_EMU_FULL=1

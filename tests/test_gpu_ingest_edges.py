@@ -7,7 +7,7 @@ tests/pafmodel.py, a plain Python model of the reader that also states what the 
 through the host reader (ma.Ingest / ma_hit_no_cont) and, where oracle/_ref is built, through the reference library's ma_hit_read.  All integers: equality
 everywhere.  Every case asserts, from the report or the downloaded arrays, that the edge it names was met.
 
-Out of scope: the sharded merge kernels (k_dict_merge and its kin need ranks: tests/test_gpu_sharded.py), texts over 4 GiB, more than 2^31 lines."""
+Out of scope: the sharded merge kernels (k_dict_merge and its kin need ranks: tests/test_gpu_ingest_shard_edges.py), texts over 4 GiB, more than 2^31 lines."""
 import contextlib
 import ctypes as C
 import os

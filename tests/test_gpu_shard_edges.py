@@ -22,8 +22,11 @@ hits and the reads with 64 / 65 / 511 / 512 arcs (lane 0 of a shifted chunk of k
 than the dictionary; equal read counts with a remainder; world 1; the tables mahip_hits_balance itself makes when one read has all the hits.  Every table
 asserts that it has the shape it was written for.
 
-NOT covered: csrc/comm.hip, mahip_hits_route, mahip_paf_parse_sharded and the tie repair of own-record shards with positions -- they run collectives inside and
-need real ranks (tests/test_gpu_sharded.py, tests/test_dist_gloo.py)."""
+Covered elsewhere, because they run collectives inside and need real ranks: mahip_paf_parse_sharded, mahip_hits_route and the shared-memory collectives of
+csrc/comm.hip they go through (the word gather in chunks of 32, the personalised exchange in slot-sized rounds) are checked rank by rank, stage by stage, at
+their size edges by tests/test_gpu_ingest_shard_edges.py (worlds 1, 2, 3, 5 and 8, against tests/pafmodel.py and stages.balance_model).
+NOT covered stage by stage: the RCCL and caller-transport paths of csrc/comm.hip and the tie repair of own-record shards with positions -- end to end only
+(tests/test_gpu_sharded.py, tests/test_dist_gloo.py)."""
 import ctypes as C
 
 import numpy as np
