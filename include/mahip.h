@@ -65,7 +65,8 @@ int mahip_paf_parse_excl(mahip_ctx_t *c, int min_span, int min_match, int bi_dir
 /* Sharded ingest ("ingest routing option B"; host/ingest_sharded.c): every rank loads and parses ITS byte range of the text (ranges in rank order,
  * cut at line starts) and the ranks exchange what the reference's sequential reader carries across a range border: line counts (occurrence numbers count lines
  * of the whole file), the `bl` a 10-column line inherits (paf.c:54), and the distinct names of every range with their first appearances, merged into ONE
- * dictionary with the reference's ids on every rank (sdict.c:27-45).  Afterwards the context holds the records of its own lines (global ids); info: line /
+ * dictionary with the reference's ids on every rank (sdict.c:27-45).  A bgzip-compressed file: mahip_bgzf_load_fd_range (below) in the place of
+ * mahip_paf_load_fd_range; plain gzip, stdin and -R are ingested whole on every rank, and every rank walks a bgzip file's whole member chain.  Afterwards the context holds the records of its own lines (global ids); info: line /
  * record counts are totals over the ranks, n_hits is this rank's.  Collective: needs a communicator (mahip_comm_init*); -R is not served in this mode. */
 int mahip_paf_load_fd_range(mahip_ctx_t *c, int fd, size_t off, size_t nbytes);
 int mahip_paf_parse_sharded(mahip_ctx_t *c, int min_span, int min_match, int bi_dir, mahip_paf_info_t *info);
@@ -365,6 +366,38 @@ int mahip_bgzf_load_fd(mahip_ctx_t *c, int fd, size_t nbytes, int target, mahip_
 int mahip_bgzf_load_mem(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, mahip_bgzf_info_t *info);
 /* for stage tests: a BGZF image in host memory -> its text in host memory (out_cap >= info->text_bytes, else -1); nothing stays loaded */
 int mahip_bgzf_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, void *out, size_t out_cap, mahip_bgzf_info_t *info);
+/* Sharded ingest of a BGZF overlap file (host/ingest_sharded.c): rank `rank` of `world` inflates only the members that hold ITS range of the text,
+ * the same range host/ingest_sharded.c cuts out of a plain file.  With T = the chain's text_bytes and nom(g) = T g / world (64-bit), the range is [beg, end) =
+ * [ls(nom(rank)), ls(nom(rank + 1))), end = T on the last rank, where ls(a) = 0 for a <= 0, T for a >= T, else the byte behind the first '\n' at a position
+ * >= a - 1 (T when there is none): a function of the text alone, so two ranks compute the border between them independently and agree.  The host walks the
+ * WHOLE chain (the table is what makes a member range addressable: that lap does not shrink with `world`); uploaded and inflated are the members from the one
+ * that holds byte max(nom(rank) - 1, 0) (first_member; empty members in front of it are skipped) through the one that holds byte nom(rank + 1) - 1, plus
+ * MAHIP_BGZF_RANGE_AHEAD members; k_text_first_nl finds both borders in the inflated text.  A border whose newline is not there (a line that runs across more
+ * members than the look-ahead) is looked for again after the next batch of members has been inflated and checked: MAHIP_BGZF_RANGE_AHEAD members, twice as many
+ * each further round, to the end of the chain (where the border is T): n_rounds <= log2(n_members) + 1 launches' worth, no wait inside a kernel.
+ * MAHIP_BGZF_RANGE_AHEAD = 1: a PAF line is a few hundred bytes and a member holds up to 64 KiB of text, so a border's newline lies in the member of its
+ * nominal position or, when that member ends inside the line, in the next one; one member more costs a rank about 16 KiB of upload and one wave, a round
+ * costs an upload, two launches and three waits for the stream.  Only a line of more than a member's text needs a round. */
+#define MAHIP_BGZF_RANGE_AHEAD 1
+typedef struct {
+	uint64_t text_bytes;                       /* T: the inflated size of the whole file */
+	uint64_t beg, end;                         /* this rank's text, positions in the inflated file */
+	uint64_t first_member, n_members_inflated; /* members [first_member, first_member + n_members_inflated) of the chain were uploaded, inflated and CRC-checked
+	                                            * (none when nom(rank + 1) = 0); first_member = n_members when no member holds byte max(nom(rank) - 1, 0) (T = 0) */
+	uint64_t comp_bytes_uploaded;              /* from the first of them's deflate bytes to the last one's */
+	int n_rounds;                              /* extension rounds */
+} mahip_bgzf_range_t;
+/* target PAF; NOT collective (the range is a function of the file, rank and world alone).  0 with info->reason == MAHIP_BGZF_OK: the context is in the state
+ * mahip_paf_load_fd_range(c, plain, range->beg, range->end - range->beg) leaves on the inflated file (the reservation of end - beg bytes, which is what
+ * MA_PAF_MAX_BYTES counts, the padding), everything but the text is back in the pool.  info as for mahip_bgzf_load_fd: n_members, n_empty, text_bytes and
+ * comp_bytes are the whole chain's, the block counts and laps_ms (walk, upload, inflate, CRC; the last three summed over the rounds) this rank's,
+ * first_bad_member counts in the whole chain.  Other return values as mahip_bgzf_load_fd: another reason is no error, nothing stays loaded.  Prints nothing. */
+int mahip_bgzf_load_fd_range(mahip_ctx_t *c, int fd, size_t nbytes, int rank, int world, mahip_bgzf_range_t *range, mahip_bgzf_info_t *info);
+/* for stage tests: a BGZF image in host memory -> the rank's text in host memory (out_cap >= range->end - range->beg, else -1) and its range; nothing stays loaded */
+int mahip_bgzf_range_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, int rank, int world, void *out, size_t out_cap, mahip_bgzf_range_t *range, mahip_bgzf_info_t *info);
+/* for stage tests: the search alone (csrc/xfer.hip: k_text_first_nl).  *pos = the position of the first '\n' among the bytes [from, to) of the DEVICE text
+ * d_text, or all ones when there is none (or to <= from).  Any byte positions: nothing outside [from, to) is read.  Waits for the stream. */
+int mahip_text_first_nl(mahip_ctx_t *c, const void *d_text, uint64_t from, uint64_t to, uint64_t *pos);
 int mahip_bgzf_last(mahip_ctx_t *c, mahip_bgzf_info_t *out); /* what the context's last BGZF load (or mahip_bgzf_note) decided */
 void mahip_bgzf_note(mahip_ctx_t *c, const mahip_bgzf_info_t *in); /* a caller that did not get as far as a load (MA_BGZF_HOST) says so */
 const char *mahip_bgzf_reason_name(int reason);

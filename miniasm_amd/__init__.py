@@ -107,6 +107,19 @@ def _bgzf_dict(b):
                 reader=BGZF_READERS[b.reader], reason=BGZF_REASONS[b.reason], first_bad_member=b.first_bad_member, laps_ms=dict(zip(("walk", "upload", "inflate", "crc"), b.laps_ms)))
 
 
+class BgzfRange(C.Structure):  # include/mahip.h: mahip_bgzf_range_t
+    _fields_ = [("text_bytes", C.c_uint64), ("beg", C.c_uint64), ("end", C.c_uint64), ("first_member", C.c_uint64), ("n_members_inflated", C.c_uint64),
+                ("comp_bytes_uploaded", C.c_uint64), ("n_rounds", C.c_int)]
+
+
+BGZF_RANGE_AHEAD = 1  # include/mahip.h: MAHIP_BGZF_RANGE_AHEAD
+
+
+def _bgzf_range_dict(r):
+    return dict(text_bytes=r.text_bytes, beg=r.beg, end=r.end, first_member=r.first_member, n_members_inflated=r.n_members_inflated, comp_bytes_uploaded=r.comp_bytes_uploaded,
+                n_rounds=r.n_rounds)
+
+
 class GzipInfo(C.Structure):  # include/mahip.h: mahip_gzip_info_t
     _fields_ = [("comp_bytes", C.c_uint64), ("text_bytes", C.c_uint64), ("chunk", C.c_uint64), ("n_chunks", C.c_uint64), ("n_synced", C.c_uint64), ("n_items", C.c_uint64),
                 ("n_stored", C.c_uint64), ("n_fixed", C.c_uint64), ("n_dynamic", C.c_uint64), ("reader", C.c_int), ("reason", C.c_int), ("first_bad_item", C.c_int64),
@@ -250,6 +263,9 @@ def lib():
         L.mahip_bgzf_load_mem.argtypes = [vp, vp, sz, i32, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_inflate_mem.argtypes = [vp, vp, sz, vp, sz, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_last.argtypes = [vp, C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_load_fd_range.argtypes = [vp, i32, sz, i32, i32, C.POINTER(BgzfRange), C.POINTER(BgzfInfo)]
+        L.mahip_bgzf_range_mem.argtypes = [vp, vp, sz, i32, i32, vp, sz, C.POINTER(BgzfRange), C.POINTER(BgzfInfo)]
+        L.mahip_text_first_nl.argtypes = [vp, vp, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
         L.mahip_bgzf_reason_name.restype = C.c_char_p
         L.mahip_bgzf_reason_name.argtypes = [i32]
         L.mahip_gzip_load_fd.argtypes = [vp, i32, sz, i32, sz, C.POINTER(GzipInfo)]
@@ -508,6 +524,29 @@ class Ctx:
         bi = BgzfInfo()
         _chk(lib().mahip_bgzf_load_mem(self.h, comp, len(comp), BGZF_TARGETS[target], C.byref(bi)), "bgzf_load_mem")
         return _bgzf_dict(bi)
+
+    def bgzf_range(self, comp, rank, world, out_cap=None):
+        """a BGZF image (bytes) -> (the text of rank `rank` of `world`, range dict, info dict): only the members that hold the rank's range are inflated; text is
+        None when the device refused them -- nothing stays loaded either way"""
+        bi, rg = BgzfInfo(), BgzfRange()
+        cap = out_cap if out_cap is not None else 65536 * (len(comp) // 28 + 1)
+        out = C.create_string_buffer(max(cap, 1))
+        _chk(lib().mahip_bgzf_range_mem(self.h, comp, len(comp), rank, world, out, cap, C.byref(rg), C.byref(bi)), "bgzf_range_mem")
+        info = _bgzf_dict(bi)
+        return (out.raw[:rg.end - rg.beg] if info["reason"] == "OK" else None), _bgzf_range_dict(rg), info
+
+    def bgzf_load_range(self, fd, nbytes, rank, world):
+        """the rank's range of an open BGZF overlap file into the text buffer of the PAF reader, as mahip_paf_load_fd_range leaves it on the inflated file
+        -> (range dict, info dict)"""
+        bi, rg = BgzfInfo(), BgzfRange()
+        _chk(lib().mahip_bgzf_load_fd_range(self.h, fd, nbytes, rank, world, C.byref(rg), C.byref(bi)), "bgzf_load_fd_range")
+        return _bgzf_range_dict(rg), _bgzf_dict(bi)
+
+    def text_first_nl(self, dptr, lo, hi):
+        """for stage tests: the position of the first newline among the bytes [lo, hi) of the device text at dptr (an int), None when there is none"""
+        pos = C.c_uint64(0)
+        _chk(lib().mahip_text_first_nl(self.h, dptr, lo, hi, C.byref(pos)), "text_first_nl")
+        return None if pos.value == 2 ** 64 - 1 else pos.value
 
     def bgzf_last(self):
         """what the context's last BGZF load decided"""

@@ -322,6 +322,253 @@ extern "C" int mahip_bgzf_load_mem(mahip_ctx_t *c, const void *comp, size_t nbyt
 	return bgzf_run(c, -1, comp, nbytes, target, nullptr, 0, info);
 }
 extern "C" int mahip_bgzf_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, void *out, size_t out_cap, mahip_bgzf_info_t *info) { return bgzf_run(c, -1, comp, ncomp, 0, out, out_cap, info); }
+
+// ---- a rank's own range of a BGZF overlap file (include/mahip.h: mahip_bgzf_load_fd_range)
+// bit 7 of every byte of w that is '\n' (useq.hip: fx_eq)
+__device__ __forceinline__ uint32_t tx_nl(uint32_t w) { const uint32_t x = w ^ 0x0a0a0a0au; return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
+
+#define TX_WAVE_BYTES 1024u // 64 lanes x 16 bytes: what a wave looks at in one step
+
+// *res (preset to all ones) = min(*res, position of the first '\n' among t[from .. to)).  The bytes between the first and the last 16-byte boundary of the
+// ADDRESS range are read as 16-byte words, a wave taking TX_WAVE_BYTES consecutive ones a step; waves go up through the text, so a wave's first step with a
+// newline holds its smallest one, and a wave stops as soon as *res lies in front of it.  BOUNDS: words are read at a0 <= w, w + 16 <= a1 with from <= a0 and
+// a1 <= to; the fewer than 16 bytes in front of a0 and behind a1 are read one by one, by block 0.
+__global__ __launch_bounds__(256) void k_text_first_nl(const uint8_t *__restrict__ t, uint64_t from, uint64_t to, unsigned long long *res)
+{
+	const uint64_t mis = (uint64_t)(uintptr_t)(t + from) & 15u;
+	uint64_t a0 = from + (mis ? 16u - mis : 0u);
+	if (a0 > to) a0 = to;
+	const uint64_t a1 = a0 + ((to - a0) & ~(uint64_t)15);
+	if (blockIdx.x == 0 && threadIdx.x < 32) { // [from, a0) and [a1, to)
+		const unsigned k = threadIdx.x & 15u;
+		const uint64_t p = (threadIdx.x < 16 ? from : a1) + k, lim = threadIdx.x < 16 ? a0 : to;
+		if (p < lim && t[p] == '\n') atomicMin(res, (unsigned long long)p);
+	}
+	const unsigned lane = threadIdx.x & 63;
+	const uint64_t wave = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6), n_waves = (uint64_t)gridDim.x * 4u;
+	uint64_t best = ~0ull;
+	for (uint64_t base = a0 + wave * TX_WAVE_BYTES; base < a1; base += n_waves * TX_WAVE_BYTES) { // the whole wave
+		if (wv_ballot(*(volatile const unsigned long long*)res < base)) break; // the whole wave, whichever lane saw it (a stale value only costs steps)
+		const uint64_t w = base + lane * 16u;
+		if (w < a1) {
+			const uint4 v = *(const uint4*)(t + w);
+			const uint32_t m[4] = {tx_nl(v.x), tx_nl(v.y), tx_nl(v.z), tx_nl(v.w)};
+			for (int k = 3; k >= 0; --k) if (m[k]) best = w + 4u * (unsigned)k + ((unsigned)__builtin_ctz(m[k]) >> 3);
+		}
+		if (wv_ballot(best != ~0ull)) break;
+	}
+	best = ~wv_max_u64(~best);
+	if (lane == 0 && best != ~0ull) atomicMin(res, (unsigned long long)best);
+}
+
+// queued: d_word <- all ones, the search.  The caller fetches the word.
+static int text_first_nl_launch(mahip_ctx *c, const void *d_text, uint64_t from, uint64_t to, DevBuf &d_word)
+{
+	HIPCHK(hipMemsetAsync(d_word.p, 0xff, 8, c->st));
+	if (to <= from) return 0;
+	ProfScope ps(c, "k_text_first_nl", (double)(to - from));
+	hipLaunchKernelGGL(k_text_first_nl, dim3(grid_for((size_t)(to - from), 4 * TX_WAVE_BYTES, 1024)), dim3(256), 0, c->st, (const uint8_t*)d_text, from, to, P<unsigned long long>(d_word));
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+extern "C" int mahip_text_first_nl(mahip_ctx_t *c, const void *d_text, uint64_t from, uint64_t to, uint64_t *pos)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	DevBuf d_word;
+	unsigned long long h = ~0ull;
+	CHK(dev_reserve(c, d_word, 64));
+	int rc = text_first_nl_launch(c, d_text, from, to, d_word);
+	if (rc == 0 && (hipMemcpyAsync(&h, d_word.p, 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) {
+		mahip_set_error("mahip_text_first_nl: %s", hipGetErrorString(hipGetLastError()));
+		rc = -1;
+	}
+	(void)hipStreamSynchronize(c->st);
+	dev_free(c, d_word);
+	*pos = h;
+	return rc;
+}
+
+// members [m0, m1) of the chain, inflated into a buffer of their own: bytes [t0, t1) of the inflated file
+struct BgBatch { DevBuf text; uint64_t m0, m1, t0, t1; };
+struct BgRange { // one mahip_bgzf_load_fd_range / mahip_bgzf_range_mem
+	int fd; const uint8_t *mem;
+	const mahip_bgzf_member_t *tab; uint64_t n, T;
+	std::vector<BgBatch> bs;
+	DevBuf d_res; // BG_RES_WORDS words of the two kernels + the word of the search
+	mahip_bgzf_range_t *range; mahip_bgzf_info_t *info;
+};
+
+// Upload, inflate and CRC-check members [m0, m1), m0 < m1 <= n.  The table rows are rebased on the host: in_off counts from the first member's deflate bytes
+// (the upload starts there and ends with the last member's), out_off from the first member's text; both stay 64-bit.  0 with info->reason set (a status, with
+// the member's number in the WHOLE chain, or NOMEM), -1: a real error.
+static int bgzf_range_batch(mahip_ctx *c, BgRange &r, uint64_t m0, uint64_t m1)
+{
+	mahip_bgzf_info_t *info = r.info;
+	const mahip_bgzf_member_t *tab = r.tab;
+	const uint64_t nm = m1 - m0, c0 = tab[m0].in_off, span = tab[m1 - 1].in_off + tab[m1 - 1].in_len - c0, t0 = tab[m0].out_off, t1 = m1 < r.n ? tab[m1].out_off : r.T;
+	DevBuf d_comp, d_tab;
+	BgBatch b;
+	b.m0 = m0; b.m1 = m1; b.t0 = t0; b.t1 = t1;
+	mahip_bgzf_member_t *rows = (mahip_bgzf_member_t*)malloc((size_t)nm * sizeof(*rows));
+	if (rows == nullptr) { mahip_set_error("mahip_bgzf_load_fd_range: out of host memory"); return -1; }
+	for (uint64_t k = 0; k < nm; ++k) { rows[k] = tab[m0 + k]; rows[k].in_off -= c0; rows[k].out_off -= t0; }
+	int rc = 0;
+	if (dev_reserve(c, b.text, (size_t)(t1 - t0) + 64) != 0 || dev_reserve(c, d_comp, (size_t)span + 64) != 0 || dev_reserve(c, d_tab, (size_t)nm * sizeof(*rows)) != 0) info->reason = MAHIP_BGZF_NOMEM;
+	else {
+		unsigned long long h_res[BG_RES_WORDS];
+		const unsigned grid = (unsigned)((nm + BGZF_WAVES - 1) / BGZF_WAVES);
+		double t = bg_now(), u;
+		do { // (one pass; `break` = a real error)
+			rc = -1;
+			if ((r.fd >= 0 ? xfer_from_fd_at(c, d_comp.p, r.fd, (size_t)c0, (size_t)span) : xfer_copy(c, d_comp.p, (void*)(r.mem + c0), (size_t)span, 1)) != 0) break;
+			if (hipMemcpyAsync(d_tab.p, rows, (size_t)nm * sizeof(*rows), hipMemcpyHostToDevice, c->st) != hipSuccess) break;
+			if (hipMemsetAsync(r.d_res.p, 0, BG_RES_WORDS * 8, c->st) != hipSuccess || hipMemsetAsync(r.d_res.p, 0xff, 8, c->st) != hipSuccess) break;
+			if (hipStreamSynchronize(c->st) != hipSuccess) break;
+			info->laps_ms[1] += ((u = bg_now()) - t) * 1e3; t = u;
+			{
+				ProfScope ps(c, "k_bgzf_inflate", (double)span + (double)(t1 - t0));
+				hipLaunchKernelGGL(k_bgzf_inflate, dim3(grid), dim3(256), 0, c->st, (const uint8_t*)d_comp.p, (const mahip_bgzf_member_t*)d_tab.p, nm, (uint8_t*)b.text.p, P<unsigned long long>(r.d_res));
+				if (hipGetLastError() != hipSuccess) break;
+			}
+			if (hipStreamSynchronize(c->st) != hipSuccess) break;
+			info->laps_ms[2] += ((u = bg_now()) - t) * 1e3; t = u;
+			{
+				ProfScope ps(c, "k_bgzf_crc", (double)(t1 - t0));
+				hipLaunchKernelGGL(k_bgzf_crc, dim3(grid), dim3(256), 0, c->st, (const uint8_t*)b.text.p, (const mahip_bgzf_member_t*)d_tab.p, nm, P<unsigned long long>(r.d_res));
+				if (hipGetLastError() != hipSuccess) break;
+			}
+			if (hipMemcpyAsync(h_res, r.d_res.p, BG_RES_WORDS * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+			info->laps_ms[3] += (bg_now() - t) * 1e3;
+			rc = 0;
+			info->n_stored += h_res[BG_RES_STORED]; info->n_fixed += h_res[BG_RES_FIXED]; info->n_dynamic += h_res[BG_RES_DYNAMIC];
+			if (h_res[BG_RES_BAD] != ~0ull) {
+				info->reason = MAHIP_BGZF_BAD_BTYPE + (int)(h_res[BG_RES_BAD] & 255u) - 1;
+				info->first_bad_member = (int64_t)(m0 + (h_res[BG_RES_BAD] >> 8));
+			}
+		} while (0);
+		if (rc != 0) mahip_set_error("mahip_bgzf_load_fd_range: upload, launch or copy failed (%s)", hipGetErrorString(hipGetLastError()));
+		r.range->comp_bytes_uploaded += span;
+	}
+	(void)hipStreamSynchronize(c->st);
+	dev_free(c, d_comp); dev_free(c, d_tab);
+	free(rows);
+	r.bs.push_back(b); // (the caller frees the text with the others)
+	return rc;
+}
+
+// ls(a) for 0 < a < T: the byte behind the first '\n' at a position >= from (from >= a - 1, nothing in [a - 1, from) is one), T when the chain ends without
+// one.  Members [.., *hi) are inflated; what the search needs beyond them is inflated here, *batch members and twice as many each further round.
+static int bgzf_range_border(mahip_ctx *c, BgRange &r, uint64_t from, uint64_t *hi, uint64_t *batch, uint64_t *ls)
+{
+	for (;;) {
+		for (size_t k = 0; k < r.bs.size(); ++k) {
+			const BgBatch &b = r.bs[k];
+			if (b.t1 <= from) continue;
+			const uint64_t f = from > b.t0 ? from : b.t0;
+			unsigned long long h = ~0ull;
+			CHK(text_first_nl_launch(c, b.text.p, f - b.t0, b.t1 - b.t0, r.d_res));
+			HIPCHK(hipMemcpyAsync(&h, r.d_res.p, 8, hipMemcpyDeviceToHost, c->st));
+			HIPCHK(hipStreamSynchronize(c->st));
+			if (h != ~0ull) { *ls = b.t0 + h + 1; return 0; }
+			from = b.t1;
+		}
+		if (*hi == r.n) { *ls = r.T; return 0; }
+		const uint64_t m1 = r.n - *hi < *batch ? r.n : *hi + *batch;
+		CHK(bgzf_range_batch(c, r, *hi, m1));
+		*hi = m1; *batch *= 2; ++r.range->n_rounds;
+		if (r.info->reason != MAHIP_BGZF_OK) return 0;
+	}
+}
+
+// fd >= 0: an open regular file of nbytes, the text stays loaded in the PAF reader; else an image in host memory, the text goes to `out` (host, out_cap bytes)
+static int bgzf_range_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int rank, int world, void *out, size_t out_cap, mahip_bgzf_range_t *range, mahip_bgzf_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (world < 1 || rank < 0 || rank >= world) { mahip_set_error("mahip_bgzf_load_fd_range: rank %d of %d", rank, world); return -1; }
+	const bool keep = fd >= 0;
+	memset(info, 0, sizeof(*info));
+	memset(range, 0, sizeof(*range));
+	info->reader = MAHIP_BGZF_HOST; info->first_bad_member = -1; info->comp_bytes = nbytes;
+	mahip_bgzf_member_t *tab = nullptr;
+	uint64_t n = 0;
+	const double t0 = bg_now();
+	const int wr = ma_bgzf_walk(fd, mem, nbytes, &tab, &n, &info->n_empty, &info->text_bytes, &info->first_bad_member);
+	if (wr < 0) { mahip_set_error("mahip_bgzf_load_fd_range: cannot read the compressed input"); return -1; }
+	info->laps_ms[0] = (bg_now() - t0) * 1e3;
+	info->reason = wr; info->n_members = n;
+	if (wr != MAHIP_BGZF_OK) { if (keep) (void)mahip_paf_release(c); c->bgzf_last = *info; return 0; }
+	const uint64_t T = info->text_bytes, nom_b = T * (uint64_t)rank / (uint64_t)world, nom_e = rank + 1 == world ? T : T * (uint64_t)(rank + 1) / (uint64_t)world;
+	range->text_bytes = T;
+	BgRange r;
+	r.fd = fd; r.mem = (const uint8_t*)mem; r.tab = tab; r.n = n; r.T = T; r.range = range; r.info = info;
+	auto member_of = [&](uint64_t byte) { // the first member whose text ends behind `byte`; n: none
+		uint64_t lo = 0, hi = n;
+		while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (tab[mid].out_off + tab[mid].isize > byte) hi = mid; else lo = mid + 1; }
+		return lo;
+	};
+	range->first_member = member_of(nom_b ? nom_b - 1 : 0);
+	DevBuf d_own;
+	void *d_text = nullptr;
+	uint64_t beg = 0, end = 0;
+	int rc = 0;
+	bool said = false; // the error message is set
+	do { // (one pass; `break` with rc = -1: a real error; with rc = 0: done, info->reason says how)
+		if (nom_e > 0) { // (else: T < world and the rank's nominal range ends at byte 0 -- nothing in front of it to own)
+			if (dev_reserve(c, r.d_res, (BG_RES_WORDS + 8) * 8) != 0) { info->reason = MAHIP_BGZF_NOMEM; break; }
+			uint64_t hi = member_of(nom_e - 1) + 1 + MAHIP_BGZF_RANGE_AHEAD, batch = MAHIP_BGZF_RANGE_AHEAD;
+			if (hi > n) hi = n;
+			said = true;
+			if ((rc = bgzf_range_batch(c, r, range->first_member, hi)) != 0 || info->reason != MAHIP_BGZF_OK) break;
+			if (nom_b > 0 && ((rc = bgzf_range_border(c, r, nom_b - 1, &hi, &batch, &beg)) != 0 || info->reason != MAHIP_BGZF_OK)) break;
+			if (nom_e >= T) end = T;
+			else if ((rc = bgzf_range_border(c, r, nom_e > beg ? nom_e - 1 : beg - 1, &hi, &batch, &end)) != 0 || info->reason != MAHIP_BGZF_OK) break; // (no newline in [nom_b - 1, beg - 1))
+			said = false;
+			if (end < beg) end = beg;
+			range->n_members_inflated = hi - range->first_member;
+		}
+		range->beg = beg; range->end = end;
+		// the text, the way mahip_paf_load_fd_range reserves it (the PAF reader's cap, MA_PAF_MAX_BYTES, counts the rank's own bytes)
+		if (keep) { if (paf_text_reserve(c, (size_t)(end - beg), &d_text) != 0) { rc = -1; said = true; break; } }
+		else {
+			if (out_cap < end - beg) { mahip_set_error("mahip_bgzf_range_mem: %llu bytes of text, room for %zu", (unsigned long long)(end - beg), out_cap); rc = -1; said = true; break; }
+			if (dev_reserve(c, d_own, (size_t)(end - beg) + 64) != 0) { info->reason = MAHIP_BGZF_NOMEM; break; }
+			d_text = d_own.p;
+		}
+		rc = -1;
+		bool ok = true;
+		for (size_t k = 0; k < r.bs.size() && ok; ++k) { // bytes [beg, end) of the batches -> the text, one copy a batch
+			const BgBatch &b = r.bs[k];
+			const uint64_t lo = beg > b.t0 ? beg : b.t0, hi = end < b.t1 ? end : b.t1;
+			if (lo < hi) ok = hipMemcpyAsync((uint8_t*)d_text + (lo - beg), (const uint8_t*)b.text.p + (lo - b.t0), (size_t)(hi - lo), hipMemcpyDeviceToDevice, c->st) == hipSuccess;
+		}
+		if (!ok || hipStreamSynchronize(c->st) != hipSuccess) break;
+		rc = !keep && end > beg ? xfer_copy(c, d_text, out, (size_t)(end - beg), 0) : 0;
+		said = rc != 0;
+	} while (0);
+	if (rc != 0 && !said) mahip_set_error("mahip_bgzf_load_fd_range: launch or copy failed (%s)", hipGetErrorString(hipGetLastError()));
+	(void)hipStreamSynchronize(c->st);
+	if (info->reason != MAHIP_BGZF_OK || rc != 0) { range->beg = range->end = 0; range->n_members_inflated = r.bs.empty() ? 0 : r.bs.back().m1 - range->first_member; }
+	for (size_t k = 0; k < r.bs.size(); ++k) dev_free(c, r.bs[k].text);
+	dev_free(c, r.d_res); dev_free(c, d_own);
+	free(tab);
+	if (rc == 0 && info->reason == MAHIP_BGZF_OK) {
+		info->reader = MAHIP_BGZF_DEVICE;
+		if (keep) paf_text_loaded(c);
+	} else if (keep) (void)mahip_paf_release(c); // nothing stays loaded
+	c->bgzf_last = *info;
+	return rc;
+}
+
+extern "C" int mahip_bgzf_load_fd_range(mahip_ctx_t *c, int fd, size_t nbytes, int rank, int world, mahip_bgzf_range_t *range, mahip_bgzf_info_t *info)
+{
+	if (fd < 0) { mahip_set_error("mahip_bgzf_load_fd_range: no file"); return -1; }
+	return bgzf_range_run(c, fd, nullptr, nbytes, rank, world, nullptr, 0, range, info);
+}
+extern "C" int mahip_bgzf_range_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, int rank, int world, void *out, size_t out_cap, mahip_bgzf_range_t *range, mahip_bgzf_info_t *info)
+{
+	return bgzf_range_run(c, -1, comp, ncomp, rank, world, out, out_cap, range, info);
+}
 extern "C" int mahip_bgzf_last(mahip_ctx_t *c, mahip_bgzf_info_t *out) { *out = c->bgzf_last; return 0; }
 extern "C" void mahip_bgzf_note(mahip_ctx_t *c, const mahip_bgzf_info_t *in) { c->bgzf_last = *in; }
 extern "C" const char *mahip_bgzf_reason_name(int reason)

@@ -8,8 +8,16 @@
  * (csrc/paf.hip: paf_cross_counts, paf_stale_bl, paf_dict_merged): line counts, the inherited `bl` of 10-column lines, the distinct names of each range with their first
  * appearances -- merged into one dictionary, the reference's ids, on every rank.  The records then travel to the ranks that own their query reads
  * in one personalised exchange (csrc/hits.hip: mahip_hits_route), each with its position in the input's record sequence, and the sharded head
- * (sharded.c) runs on ranks that hold their own records only.  Plain files only (a byte range of a gzip stream is not a text range); -R needs
- * the whole text on one rank: both fall back to the whole-text form.
+ * (sharded.c) runs on ranks that hold their own records only.
+ *
+ * A bgzip-compressed (BGZF) file is ingested by ranges too: its member table says where every member's text lies in the inflated file, so rank g uploads and
+ * inflates only the members that hold ITS range of the inflated text, cut by the same rule (mahip_bgzf_load_fd_range, include/mahip.h), and goes
+ * on from there as on a plain file.  Every rank walks the whole member chain for that (one small read per member): that lap does not shrink with N.  What
+ * keeps one rank's device from inflating its members (a bad block, a CRC, no memory) the other ranks cannot know, so the ranks agree on one outcome before
+ * anybody parses: one reason anywhere and every rank drops its text and takes the whole-text form through zlib, as before.
+ *
+ * Still ingested whole on every rank: plain gzip (a byte range of ONE deflate stream is not a text range), stdin, MA_BGZF_HOST=1, MA_INGEST_WHOLE=1, and -R
+ * (it needs the whole text on one rank).  The reads file (-f) is read by rank 0 alone.
  */
 #define _GNU_SOURCE
 #include <fcntl.h>
@@ -39,16 +47,42 @@ static off_t line_start_at(int fd, off_t at, off_t size)
 	return size;
 }
 
-/* 1 if `fn` can be ingested by ranges (a plain regular file), else 0 */
+/* what the first bytes of a regular file say: 0 plain text, 1 a BGZF member (a gzip member with an extra field that holds a `BC` subfield of two bytes: what
+ * ma_bgzf_walk takes for one), 2 another gzip stream */
+static int file_form(int fd, off_t size)
+{
+	unsigned char h[12], *x;
+	size_t xlen, p;
+	int form = 2;
+	if (size < 2 || pread(fd, h, 2, 0) != 2 || h[0] != 0x1f || h[1] != 0x8b) return 0;
+	if (size < 12 || pread(fd, h, 12, 0) != 12 || h[2] != 8 || !(h[3] & 4)) return 2;
+	xlen = (size_t)h[10] | (size_t)h[11] << 8;
+	if ((off_t)(12 + xlen) > size || xlen < 6) return 2;
+	x = (unsigned char*)malloc(xlen);
+	if (x == 0) return 2;
+	if (pread(fd, x, xlen, 12) == (ssize_t)xlen)
+		for (p = 0; xlen - p >= 4; ) {
+			const size_t slen = (size_t)x[p + 2] | (size_t)x[p + 3] << 8;
+			if (xlen - p - 4 < slen) break;
+			if (x[p] == 'B' && x[p + 1] == 'C' && slen == 2) { form = 1; break; }
+			p += 4 + slen;
+		}
+	free(x);
+	return form;
+}
+
+/* 1 if `fn` can be ingested by ranges (a regular file: plain, or one that begins with a BGZF member while MA_BGZF_HOST is not set), else 0 */
 int ma_ingest_sharded_possible(const char *fn)
 {
 	struct stat st;
-	unsigned char magic[2] = { 0, 0 };
-	int fd, ok;
+	int fd, ok = 0;
 	if (fn == 0 || strcmp(fn, "-") == 0) return 0;
 	fd = open(fn, O_RDONLY);
 	if (fd < 0) return 0;
-	ok = fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && !(pread(fd, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b);
+	if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) {
+		const int form = file_form(fd, st.st_size);
+		ok = form == 0 || (form == 1 && ma_bgzf_enabled());
+	}
 	close(fd);
 	return ok;
 }
@@ -56,7 +90,8 @@ int ma_ingest_sharded_possible(const char *fn)
 /* Collective over the context's communicator.  Afterwards: c holds this rank's OWN records (query read in its range) in input order with their positions,
  * the shard bounds are set, d holds the whole dictionary (every rank: the tail runs on rank 0, but the squeeze bookkeeping of the head wants n_seq
  * everywhere and the dictionary is two plain copies).  *n_hits_total / *n_lines: over all ranks.  Returns 0, -1 (cannot open), -2 (not possible: caller
- * falls back to the whole-text form on every rank -- decided from the file alone, so all ranks decide alike). */
+ * falls back to the whole-text form on every rank -- decided from the file alone, or, for a BGZF file, agreed between the ranks: all ranks return it
+ * together, before any of them has entered mahip_paf_parse_sharded). */
 int ma_hit_ingest_sharded(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits_total, int bi_dir, ma_ingest_shard_info_t *si)
 {
 	const int world = mahip_comm_world(c), rank = mahip_comm_rank(c);
@@ -64,18 +99,45 @@ int ma_hit_ingest_sharded(mahip_ctx_t *c, const char *fn, int min_span, int min_
 	double t0 = sys_realtime(), t1, t2, t3;
 	mahip_paf_info_t info;
 	struct stat st;
-	off_t beg, end;
+	off_t beg, end, size;
 	uint64_t n_total = 0, sent = 0, sums[2];
 	int fd;
 	if (!ma_ingest_sharded_possible(fn)) return -2;
 	fd = open(fn, O_RDONLY);
 	if (fd < 0 || fstat(fd, &st) != 0) { if (fd >= 0) close(fd); return -1; }
-	beg = line_start_at(fd, (off_t)((unsigned long long)st.st_size * (unsigned)rank / (unsigned)world), st.st_size);
-	end = rank + 1 == world ? st.st_size : line_start_at(fd, (off_t)((unsigned long long)st.st_size * (unsigned)(rank + 1) / (unsigned)world), st.st_size);
-	if (end < beg) end = beg;
+	size = st.st_size;
 	GPU(mahip_set_shard(c, 0, 0xffffffffu));
-	GPU(mahip_paf_load_fd_range(c, fd, (size_t)beg, (size_t)(end - beg)));
-	close(fd);
+	if (file_form(fd, st.st_size) == 1) { /* BGZF: the members that hold this rank's range of the inflated text */
+		mahip_bgzf_range_t rg;
+		mahip_bgzf_info_t bi;
+		uint64_t mine, *all = (uint64_t*)calloc((size_t)world, sizeof(uint64_t));
+		int g, refused = -1;
+		GPU(mahip_bgzf_load_fd_range(c, fd, (size_t)st.st_size, rank, world, &rg, &bi));
+		close(fd);
+		/* a refusal of the walk every rank has, a status of the kernels or a lack of memory maybe this one alone: one outcome for all, before anybody parses */
+		mine = (uint64_t)bi.reason;
+		GPU(mahip_comm_all_gather_u64(c, &mine, 1, all));
+		for (g = world - 1; g >= 0; --g) if (all[g] != MAHIP_BGZF_OK) refused = g;
+		if (refused >= 0) {
+			if (timing) fprintf(stderr, "[T::ingest_gpu] rank %d of %d: no member ranges (rank %d: %s); every rank ingests the whole text\n", rank, world, refused, mahip_bgzf_reason_name((int)all[refused]));
+			free(all);
+			if (bi.reason == MAHIP_BGZF_OK) GPU(mahip_paf_release(c));
+			return -2;
+		}
+		free(all);
+		if (timing)
+			fprintf(stderr, "[T::bgzf] reader=device rank %d of %d: members [%llu, %llu) of %llu (%llu empty) inflated, %llu of %llu compressed bytes uploaded, %d extension rounds: "
+			        "walk %.3f (the whole chain) upload %.3f inflate %.3f crc %.3f ms\n", rank, world, (unsigned long long)rg.first_member, (unsigned long long)(rg.first_member + rg.n_members_inflated),
+			        (unsigned long long)bi.n_members, (unsigned long long)bi.n_empty, (unsigned long long)rg.comp_bytes_uploaded, (unsigned long long)bi.comp_bytes, rg.n_rounds,
+			        bi.laps_ms[0], bi.laps_ms[1], bi.laps_ms[2], bi.laps_ms[3]);
+		beg = (off_t)rg.beg; end = (off_t)rg.end; size = (off_t)rg.text_bytes;
+	} else {
+		beg = line_start_at(fd, (off_t)((unsigned long long)st.st_size * (unsigned)rank / (unsigned)world), st.st_size);
+		end = rank + 1 == world ? st.st_size : line_start_at(fd, (off_t)((unsigned long long)st.st_size * (unsigned)(rank + 1) / (unsigned)world), st.st_size);
+		if (end < beg) end = beg;
+		GPU(mahip_paf_load_fd_range(c, fd, (size_t)beg, (size_t)(end - beg)));
+		close(fd);
+	}
 	t1 = sys_realtime();
 	GPU(mahip_paf_parse_sharded(c, min_span, min_match, bi_dir, &info));
 	t2 = sys_realtime();
@@ -92,11 +154,11 @@ int ma_hit_ingest_sharded(mahip_ctx_t *c, const char *fn, int min_span, int min_
 	t3 = sys_realtime();
 	sums[0] = (uint64_t)(end - beg); sums[1] = sent;
 	if (si) {
-		si->bytes_own = (uint64_t)(end - beg); si->bytes_file = (uint64_t)st.st_size; si->n_lines = info.n_lines; si->n_records = info.n_records;
+		si->bytes_own = (uint64_t)(end - beg); si->bytes_file = (uint64_t)size; si->n_lines = info.n_lines; si->n_records = info.n_records;
 		si->n_hits_total = n_total; si->bytes_routed = sent; si->max_qs = info.max_qs;
 	}
 	if (timing) fprintf(stderr, "[T::ingest_gpu] rank %d of %d: bytes [%lld, %lld) of %lld; load %.3f  parse+merge %.3f  dictionary+route %.3f s (%lu lines in all, %lu of %lu records sent on)\n",
-	                    rank, world, (long long)beg, (long long)end, (long long)st.st_size, t1 - t0, t2 - t1, t3 - t2, (unsigned long)info.n_lines, (unsigned long)(sent / 36), (unsigned long)info.n_hits);
+	                    rank, world, (long long)beg, (long long)end, (long long)size, t1 - t0, t2 - t1, t3 - t2, (unsigned long)info.n_lines, (unsigned long)(sent / 36), (unsigned long)info.n_hits);
 	*n_hits_total = (size_t)n_total;
 	(void)sums;
 	return 0;

@@ -249,19 +249,23 @@ int ma_pipeline_run_rank(mahip_ctx_t *c, const ma_opt_t *opt, const char *fn, co
 	FILE *lg;
 	lg = MA_LOG;
 	fprintf(lg, "[M::%s] ===> Step %d: %s <===\n", "main", (flags & 8) ? 0 : 1, (flags & 8) ? "removing contained reads" : "reading read mappings");
-	/* Ingest.  A plain file without -R: every rank loads and parses its own byte range, the ranks merge their name tables and route the records to the owners
-	 * of their query reads (ingest_sharded.c) -- 1/N of the text per rank.  Otherwise (gzip, stdin, -R, MA_INGEST_WHOLE=1): every rank parses the whole text
-	 * and keeps the hits of its read range, as in round 3.  The choice depends on the file and the options alone: every rank makes the same one. */
+	/* Ingest.  A plain or a bgzip-compressed file without -R: every rank loads (inflates) and parses its own byte range of the text, the ranks merge their name
+	 * tables and route the records to the owners of their query reads (ingest_sharded.c) -- 1/N of the text per rank.  Otherwise (plain gzip, stdin, -R,
+	 * MA_BGZF_HOST=1, MA_INGEST_WHOLE=1): every rank parses the whole text and keeps the hits of its read range, as in round 3.  The choice depends on the file
+	 * and the options alone: every rank makes the same one.  A bgzip file that some rank's device could not inflate comes back as -2 on EVERY rank (they agree
+	 * in there): the whole-text form, through zlib. */
 	own_records = !(flags & 8) && !(getenv("MA_INGEST_WHOLE") && atoi(getenv("MA_INGEST_WHOLE"))) && ma_ingest_sharded_possible(fn);
 	if (own_records) {
 		ma_ingest_shard_info_t si;
 		memset(&si, 0, sizeof(si));
 		r = ma_hit_ingest_sharded(c, fn, opt->min_span, opt->min_match, d, &n_hits, !(flags & 4), &si);
 		if (r == -1) { fprintf(stderr, "[E::%s] could not open PAF file %s\n", "ma_hit_read", fn); exit(1); }
-		if (r != 0) { fprintf(stderr, "[E::%s] rank %d: the ranges of the text could not be ingested\n", "ma_pipeline_run_sharded", rank); exit(1); }
-		if (ma_verbose >= 3)
+		if (r == -2) own_records = 0;
+		else if (r != 0) { fprintf(stderr, "[E::%s] rank %d: the ranges of the text could not be ingested\n", "ma_pipeline_run_sharded", rank); exit(1); }
+		else if (ma_verbose >= 3)
 			fprintf(lg, "[M::%s::%s] read %ld hits; stored %ld hits and %d sequences (%ld bp)\n", "ma_hit_read", sys_timestamp(), (long)si.n_records, (long)si.n_hits_total, d->n_seq, (long)si.tot_len);
-	} else {
+	}
+	if (!own_records) {
 	r = ma_hit_ingest_gpu_excl(c, fn, opt->min_span, opt->min_match, d, &n_hits, !(flags & 4), (flags & 8) != 0, opt->max_hang, opt->int_frac);
 	if (r == -1) { fprintf(stderr, "[E::%s] could not open PAF file %s\n", "ma_hit_read", fn); exit(1); }
 	if (r != 0) { fprintf(stderr, "[E::%s] the text does not fit the device stage; MA_GPUS > 1 needs the device parser\n", "ma_pipeline_run_sharded"); exit(1); }
