@@ -104,6 +104,38 @@ int mahip_paf_cols_download(mahip_ctx_t *c, uint8_t *flags, uint8_t *odd, uint32
  * flags: for tests, not for production runs).  Off by default. */
 int mahip_paf_keep_odd(mahip_ctx_t *c, int on);
 uint32_t mahip_paf_max_qs(mahip_ctx_t *c);                                  /* info.max_qs of the last parse (a sort hint for later mahip_hits_adopt calls) */
+/* ---- the same ingest, piece by piece (what the reference's reader does by streaming: paf.c:9-20 paf_open over kseq.h:59-157, one line at a time through a
+ * 16-KiB buffer).  The pieces of one text arrive in order; the context never holds more text than one piece.  begin ... piece* ... end leaves the context as
+ * mahip_paf_parse leaves it on the concatenated text: the same records in the same order (hit.c:70-101), the same ids and first-seen lengths (sdict.c:27-45
+ * sd_put), the same mahip_paf_info_t; mahip_paf_names, mahip_paf_seqs, mahip_paf_release, mahip_hits_sort and what follows work as after a whole parse (records
+ * are a line's record and its mirror side by side: the run stride is set to 2, or to 1 without bi_dir).  mahip_paf_last and mahip_paf_cols_download describe the
+ * LAST PIECE THAT HAD TEXT (zeros when none had).  Not served: -R (hit.c:38-68 needs every line before any id is given out; the reference reads the file twice
+ * for it) -- use mahip_paf_parse_excl --, and contexts with a communicator.
+ * mahip_paf_stream_begin (hit.c:76-79: the dictionary and the record array start empty): a stream the context still holds is dropped.
+ * mahip_paf_stream_piece_mem (hit.c:80-100 on the lines of the piece): a piece is WHOLE LINES -- one that is not the last, has bytes and does not end with '\n'
+ * is an error; the last piece (last != 0) may end without a newline and gets the virtual one a whole parse gives its text (kseq.h:139-144: the rest of the
+ * stream is a line); pieces of 0 bytes are legal anywhere; nothing may follow the last piece.  MA_PAF_MAX_BYTES counts the piece's own bytes.  A 10-column
+ * line takes the `bl` of the last 11-column line of this or ANY earlier piece (paf.c:54 leaves the field alone).  After an error: mahip_paf_stream_abort.
+ * mahip_paf_stream_end (hit.c:101-102): adopts the records and hands over the dictionary; legal without any piece (everything zero).
+ * mahip_paf_stream_abort: everything the stream holds goes back to the pool (legal without a stream).
+ * MA_STREAM_DICT_CAP_LOG2 / MA_STREAM_REC_CAP: the first capacity of the name table (slots, log2) and of the record buffer (records); both grow (tests). */
+typedef struct {
+	uint64_t n_pieces, n_empty;       /* pieces seen; of them, pieces of 0 bytes */
+	uint64_t n_short, n_text;         /* pieces whose local name table took MAHIP_PAF_DICT_SHORT / MAHIP_PAF_DICT_TEXT */
+	uint64_t n_inherited;             /* pieces whose FIRST line is a 10-column line that took its bl from an earlier piece */
+	uint32_t tab_cap, n_rebuilds;     /* slots of the persistent name table now; times it was rebuilt larger from the names so far */
+	uint32_t n_fold_repeats;          /* folds repeated on a rebuilt table because a probe sequence had run out */
+	uint32_t n_rec_grow;              /* times the record buffer was replaced by a larger one */
+	uint32_t last_local, last_new;    /* the last piece with text: its distinct names; of them, names no earlier piece had */
+	uint32_t last_before;             /* ... the bl its 10-column lines in front of its first 11-column line inherit */
+	int last_form;                    /* ... its MAHIP_PAF_DICT_* */
+	double t_upload, t_parse, t_fold; /* seconds so far: text to the device; the stages of the parse; the fold into the persistent dictionary */
+} mahip_paf_stream_report_t;
+int mahip_paf_stream_begin(mahip_ctx_t *c, int min_span, int min_match, int bi_dir);
+int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, int last);
+int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info);
+int mahip_paf_stream_abort(mahip_ctx_t *c);
+int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *out);   /* valid from begin until the next begin, abort or mahip_paf_release */
 int mahip_hits_raw_download(mahip_ctx_t *c, ma_hit_t *out);                 /* the unsorted records held by the context (n_hits of them) */
 /* device-to-device: the unsorted records whose query id lies in [q_beg,q_end), in input order, into d_dst (NULL: only count
  * them); *n_out = their number.  Lets a caller keep the records of one read-range shard (bench.py, multi-GPU set-up). */

@@ -153,6 +153,13 @@ class PafReport(C.Structure):  # include/mahip.h: mahip_paf_report_t
                 ("cap", C.c_uint32 * 4), ("end", C.c_int * 4)]
 
 
+class PafStreamReport(C.Structure):  # include/mahip.h: mahip_paf_stream_report_t
+    _fields_ = [("n_pieces", C.c_uint64), ("n_empty", C.c_uint64), ("n_short", C.c_uint64), ("n_text", C.c_uint64), ("n_inherited", C.c_uint64),
+                ("tab_cap", C.c_uint32), ("n_rebuilds", C.c_uint32), ("n_fold_repeats", C.c_uint32), ("n_rec_grow", C.c_uint32),
+                ("last_local", C.c_uint32), ("last_new", C.c_uint32), ("last_before", C.c_uint32), ("last_form", C.c_int),
+                ("t_upload", C.c_double), ("t_parse", C.c_double), ("t_fold", C.c_double)]
+
+
 PAF_DICT_FORMS = {0: None, 1: "short", 2: "text"}  # MAHIP_PAF_DICT_*
 PAF_TAB_ENDS = {0: "ok", 1: "load", 2: "probes"}   # MAHIP_PAF_TAB_*
 
@@ -220,6 +227,11 @@ def lib():
         L.mahip_paf_last.argtypes = [vp, C.POINTER(PafReport)]
         L.mahip_paf_cols_download.argtypes = [vp] + [vp] * 8
         L.mahip_paf_keep_odd.argtypes = [vp, i32]
+        L.mahip_paf_stream_begin.argtypes = [vp, i32, i32, i32]
+        L.mahip_paf_stream_piece_mem.argtypes = [vp, vp, sz, i32]
+        L.mahip_paf_stream_end.argtypes = [vp, C.POINTER(PafInfo)]
+        L.mahip_paf_stream_abort.argtypes = [vp]
+        L.mahip_paf_stream_last.argtypes = [vp, C.POINTER(PafStreamReport)]
         L.mahip_hits_sort.argtypes = [vp]
         L.mahip_hits_index.argtypes = [vp]
         L.mahip_hits_sub.argtypes = [vp, i32, C.c_float, i32, i32, C.POINTER(sz)]
@@ -349,6 +361,31 @@ class Ctx:
 
     def hits_adopt(self, dptr, n, n_seq):
         _chk(lib().mahip_hits_adopt(self.h, dptr, n, n_seq), "hits_adopt")
+
+    def paf_stream_last(self):
+        r = PafStreamReport()
+        _chk(lib().mahip_paf_stream_last(self.h, C.byref(r)), "paf_stream_last")
+        return r
+
+    def paf_stream(self, pieces, min_span, min_match, bi_dir, each=None):
+        """pieces (bytes objects, whole lines each; only the last may end without a newline) through the streamed ingest: begin, a piece at a time, end.
+        Returns (PafInfo, PafStreamReport); the context is left as after mahip_paf_parse on the concatenated text.  each(k, report): called behind piece k.
+        An error aborts the stream before it is raised."""
+        L = lib()
+        pieces = list(pieces)
+        _chk(L.mahip_paf_stream_begin(self.h, min_span, min_match, 1 if bi_dir else 0), "paf_stream_begin")
+        info = PafInfo()
+        try:
+            for k, p in enumerate(pieces):
+                buf = C.create_string_buffer(bytes(p), len(p)) if len(p) else None
+                _chk(L.mahip_paf_stream_piece_mem(self.h, buf, len(p), 1 if k + 1 == len(pieces) else 0), "paf_stream_piece_mem")
+                if each is not None:
+                    each(k, self.paf_stream_last())
+            _chk(L.mahip_paf_stream_end(self.h, C.byref(info)), "paf_stream_end")
+        except Exception:
+            L.mahip_paf_stream_abort(self.h)
+            raise
+        return info, self.paf_stream_last()
 
     def sort(self):
         _chk(lib().mahip_hits_sort(self.h), "hits_sort")

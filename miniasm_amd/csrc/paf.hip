@@ -35,6 +35,7 @@ struct PafBufs {
 	DevBuf flags, num[8], tnoff, qlen, tlen, hq, ht, qslot, tslot;
 	DevBuf tab, tmin, slot_id, blv, scal, excl;
 	DevBuf name_off, name_len, name_pos, seq_len, names;
+	struct PafStream *stream = nullptr; // a streamed ingest in progress, or the report of the last one (mahip_paf_stream_*)
 	size_t nbytes = 0, name_bytes = 0;
 	uint32_t n_seq = 0;
 	bool loaded = false;
@@ -58,10 +59,12 @@ static PafBufs *paf_of(mahip_ctx *c)
 	return (PafBufs*)c->paf;
 }
 
+static void paf_stream_free(mahip_ctx *c, PafBufs *b);
 void paf_free(mahip_ctx *c)
 {
 	PafBufs *b = (PafBufs*)c->paf;
 	if (!b) return;
+	paf_stream_free(c, b);
 	DevBuf *all[] = { &b->text, &b->lstart, &b->tile, &b->glast, &b->gmax, &b->tfirst, &b->flags, &b->tnoff, &b->qlen, &b->tlen, &b->hq, &b->ht, &b->qslot, &b->tslot, &b->tab, &b->tmin,
 		&b->slot_id, &b->blv, &b->scal, &b->excl, &b->name_off, &b->name_len, &b->name_pos, &b->seq_len, &b->names };
 	for (DevBuf *d : all) dev_free(c, *d);
@@ -1144,11 +1147,12 @@ static int paf_cross_counts(mahip_ctx *c, PafParse &ps)
 // ---- stale bl: rare (PAF writers emit 12+ columns).  The bl of the lines that have one, compacted; a line without takes the one in front of it.
 // exchange (a collective: every rank comes here when ANY rank has a 10-column line): every range says what `bl` it leaves behind (the bl of its last 11-column
 // line), and a line in front of a range's first 11-column line inherits from the nearest range before it that has one (paf.c:54: the field is simply not written)
-static int paf_stale_bl(mahip_ctx *c, PafBufs *b, PafParse &ps, bool exchange)
+// before0 (without the exchange): what the ranges in front of this text leave behind, known to the caller -- the pieces of a stream arrive in order (mahip_paf_stream_piece_mem)
+static int paf_stale_bl(mahip_ctx *c, PafBufs *b, PafParse &ps, bool exchange, uint32_t before0 = 0)
 {
 	const uint32_t L = ps.L;
 	uint32_t *has = P<uint32_t>(c->keep), *pos = P<uint32_t>(c->pos);
-	uint32_t n_has = 0, last_bl = 0, before = 0;
+	uint32_t n_has = 0, last_bl = 0, before = before0;
 	if (L) {
 		CHK(dev_reserve(c, b->blv, ((size_t)L + 4) * 4));
 		hipLaunchKernelGGL(k_paf_hasbl, dim3(grid_for(L, 256)), dim3(256), 0, c->st, (const uint8_t*)ps.o.flags, L, has);
@@ -1345,18 +1349,19 @@ static int paf_dict_merged(mahip_ctx *c, PafBufs *b, PafParse &ps)
 }
 
 // ---- records: hit (+ mirrored hit) per stored line, in line order.  One pass: ids, record slots (chained tiles), records
-static int paf_records(mahip_ctx *c, PafBufs *b, PafParse &ps, int bi_dir)
+// dst: where the records go -- nullptr: the context's own record buffer, sized here; a streamed ingest hands in the place behind the records of the pieces so far
+static int paf_records(mahip_ctx *c, PafBufs *b, PafParse &ps, int bi_dir, ma_hit_t *dst = nullptr)
 {
 	const size_t max_hits = bi_dir ? 2 * ps.n_pass : ps.n_pass;
 	if (max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
-	CHK(dev_reserve(c, c->aos_own, (max_hits + 1) * sizeof(ma_hit_t)));
+	if (!dst) { CHK(dev_reserve(c, c->aos_own, (max_hits + 1) * sizeof(ma_hit_t))); dst = (ma_hit_t*)c->aos_own.p; }
 	const size_t nb = ((size_t)ps.L + EM_TILE - 1) / EM_TILE;
 	uint32_t *ticket; unsigned long long *state; uint32_t ticket_base, epoch;
 	CHK(scan_chain_begin(c, nb, &state, &ticket, &ticket_base, &epoch));
 	uint32_t nh = 0;
 	{
 		ProfScope ps_(c, "k_paf_emit", 37.0 * (double)ps.n_pass + 32.0 * (double)max_hits);
-		hipLaunchKernelGGL(k_paf_emit_chain, dim3((unsigned)nb), dim3(256), 0, c->st, ps.o, ps.slot_to_id, ps.L, bi_dir, (uint4*)c->aos_own.p, P<uint32_t>(b->scal), state, ticket, ticket_base, epoch);
+		hipLaunchKernelGGL(k_paf_emit_chain, dim3((unsigned)nb), dim3(256), 0, c->st, ps.o, ps.slot_to_id, ps.L, bi_dir, (uint4*)dst, P<uint32_t>(b->scal), state, ticket, ticket_base, epoch);
 	}
 	CHK(fetch_u32(c, b->scal.p, &nh));
 	ps.n_hits = nh;
@@ -1437,6 +1442,364 @@ extern "C" int mahip_paf_parse_excl(mahip_ctx_t *c, int min_span, int min_match,
 extern "C" int mahip_paf_parse_sharded(mahip_ctx_t *c, int min_span, int min_match, int bi_dir, mahip_paf_info_t *info)
 {
 	return paf_parse_impl(c, min_span, min_match, bi_dir, 0, 0, 0.f, info, mahip_comm_active(c) != 0);
+}
+
+// ------------------------------------------------------------------------------------------------ streamed ingest: pieces of one text, in order
+// The pieces of a stream are ranks in time (the sharded ingest above joins ranges of one text the same way), with one simplification: they arrive in order, so
+// a name that is new in piece k takes the ids behind those of all earlier pieces (sdict.c:27-45: ids in order of first appearance) and no sort over the first
+// appearances of the whole text is needed.  What persists between pieces: a table of the names so far (open addressing, one 64-bit word per slot:
+// tag(32) | id), the names themselves in an arena laid out as mahip_paf_names hands them out (NUL behind each, id order), their first-seen lengths, the records
+// so far, the `bl` of the last line with an 11th column (paf.c:54), and the running totals.  A piece runs the stages of a whole parse on its own text; its local
+// dictionary (distinct names in local first-appearance order) is then FOLDED into the table: found names keep their id and length, the others get
+// n_seq + their rank among the piece's new names -- local ids rise with 2 x line + column, so the order is the reference's.
+#define ST_PROV 0x80000000u // low word of a slot claimed in the fold that is running: ST_PROV | local id (ids stay below 2^31); made an id by k_stream_commit
+
+struct PafStream {
+	bool active = false, closed = false; // between begin and end / abort; the last piece has been seen
+	int min_span = 0, min_match = 0, bi_dir = 0;
+	DevBuf tab, arena, seq_len, name_pos, name_len, rec, fold, map;
+	uint32_t cap = 0, n_seq = 0;
+	size_t arena_bytes = 0, n_rec = 0, rec_cap = 0;
+	uint64_t n_lines = 0, n_valid = 0, n_pass = 0;
+	uint32_t max_qs = 0, last_bl = 0;
+	bool have_bl = false, any_parsed = false;
+	mahip_paf_stream_report_t rep = {};
+};
+
+static void paf_stream_free(mahip_ctx *c, PafBufs *b)
+{
+	PafStream *st = b->stream;
+	if (!st) return;
+	DevBuf *all[] = { &st->tab, &st->arena, &st->seq_len, &st->name_pos, &st->name_len, &st->rec, &st->fold, &st->map };
+	for (DevBuf *d : all) dev_free(c, *d);
+	delete st;
+	b->stream = nullptr;
+}
+
+// the hash that places a name in the persistent table: over the bytes alone, so that a piece of short names and a piece of long ones meet in one table
+__device__ __forceinline__ uint64_t stream_hash(const unsigned char *__restrict__ nm, uint32_t len) { return key_mix(fnv_bytes(nm, len)); }
+
+// One thread per local name j (names of one piece are distinct: two threads never look for the same name).  Found: l2g[j] = its id, is_new[j] = 0.  Not found: the
+// first free slot of its probe sequence is claimed (CAS) with ST_PROV | j, slot_of[j] says which, is_new[j] = 1, blen[j] = its bytes in the arena.  A slot that
+// holds another thread's claim holds another name: the probe goes on.  At most PAF_PROBE_LIMIT probes; a sequence that runs out raises PC_OVERFLOW (the host
+// rebuilds a larger table from the arena, which drops every claim of this launch, and repeats the fold).
+__global__ __launch_bounds__(256) void k_stream_fold(const unsigned char *__restrict__ lnames, const uint32_t *__restrict__ lpos, const uint32_t *__restrict__ llen, uint32_t R,
+                                                      unsigned long long *__restrict__ tab, uint32_t mask, const unsigned char *__restrict__ arena, const uint32_t *__restrict__ g_pos,
+                                                      const uint32_t *__restrict__ g_len, uint32_t *__restrict__ l2g, uint32_t *__restrict__ slot_of, uint32_t *__restrict__ is_new,
+                                                      uint32_t *__restrict__ blen, unsigned long long *__restrict__ ctr)
+{
+	uint32_t fail = 0;
+	for (uint32_t j = blockIdx.x * 256u + threadIdx.x; j < R; j += gridDim.x * 256u) {
+		const uint32_t len = llen[j];
+		const unsigned char *nm = lnames + lpos[j];
+		const uint64_t h = stream_hash(nm, len);
+		const uint32_t tag = (uint32_t)(h >> 32);
+		uint32_t s = (uint32_t)h & mask, found = 0xffffffffu, claimed = 0xffffffffu;
+		for (uint32_t probe = 0; probe < PAF_PROBE_LIMIT; ++probe, s = (s + 1) & mask) {
+			unsigned long long e = tab[s];
+			if (e == PAF_EMPTY) {
+				e = atomicCAS(&tab[s], PAF_EMPTY, (unsigned long long)tag << 32 | (ST_PROV | j));
+				if (e == PAF_EMPTY) { claimed = s; break; }
+			}
+			const uint32_t v = (uint32_t)e;
+			if ((uint32_t)(e >> 32) == tag && !(v & ST_PROV) && g_len[v] == len && name_eq(nm, arena + g_pos[v], len)) { found = v; break; } // the bytes decide, never the tag alone
+		}
+		is_new[j] = claimed != 0xffffffffu;
+		blen[j] = claimed != 0xffffffffu ? len + 1u : 0u;
+		slot_of[j] = claimed;
+		l2g[j] = found;
+		if (found == 0xffffffffu && claimed == 0xffffffffu) fail = 1;
+	}
+	blk_add_u64(&ctr[PC_OVERFLOW], fail);
+}
+// the new names get their ids (n_seq0 + rank among the piece's new names, in local-id order) and their places: slot, arena (bytes + NUL at arena0 + bpos[j] .. < arena0 +
+// the scanned total), first-seen length.  One thread per local name; every write goes to an index the scans made unique.
+__global__ __launch_bounds__(256) void k_stream_commit(const unsigned char *__restrict__ lnames, const uint32_t *__restrict__ lpos, const uint32_t *__restrict__ llen,
+                                                        const uint32_t *__restrict__ lseq, uint32_t R, const uint32_t *__restrict__ is_new, const uint32_t *__restrict__ pos,
+                                                        const uint32_t *__restrict__ bpos, const uint32_t *__restrict__ slot_of, uint32_t n_seq0, uint32_t arena0,
+                                                        unsigned long long *__restrict__ tab, unsigned char *__restrict__ arena, uint32_t *__restrict__ g_pos, uint32_t *__restrict__ g_len,
+                                                        uint32_t *__restrict__ g_seq, uint32_t *__restrict__ l2g)
+{
+	const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+	if (j >= R || !is_new[j]) return;
+	const uint32_t g = n_seq0 + pos[j], len = llen[j], at = arena0 + bpos[j];
+	const unsigned char *nm = lnames + lpos[j];
+	tab[slot_of[j]] = (tab[slot_of[j]] & 0xffffffff00000000ull) | g; // (the claim is this thread's own: nobody else writes the slot)
+	for (uint32_t k = 0; k < len; ++k) arena[at + k] = nm[k];
+	arena[at + len] = 0;
+	g_pos[g] = at; g_len[g] = len; g_seq[g] = lseq[j];
+	l2g[j] = g;
+}
+// the piece's table slot -> global id, through the slot's local id: what k_merge_map makes for a rank (k_paf_emit_chain's slot_id)
+__global__ __launch_bounds__(256) void k_stream_map(const uint32_t *__restrict__ tmin, const uint32_t *__restrict__ slot_id, uint32_t cap, const uint32_t *__restrict__ l2g, uint32_t *__restrict__ out)
+{
+	const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+	if (s < cap && tmin[s] != 0xffffffffu) out[s] = l2g[slot_id[s]];
+}
+// a fresh (all PAF_EMPTY) table from the arena: one thread per id so far, exactly those ids are inserted; all names differ, so nothing is compared
+__global__ __launch_bounds__(256) void k_stream_rebuild(const unsigned char *__restrict__ arena, const uint32_t *__restrict__ g_pos, const uint32_t *__restrict__ g_len, uint32_t n_seq,
+                                                         unsigned long long *__restrict__ tab, uint32_t mask, unsigned long long *__restrict__ ctr)
+{
+	uint32_t fail = 0;
+	for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < n_seq; g += gridDim.x * 256u) {
+		const uint64_t h = stream_hash(arena + g_pos[g], g_len[g]);
+		uint32_t s = (uint32_t)h & mask, probe = 0;
+		for (; probe < PAF_PROBE_LIMIT; ++probe, s = (s + 1) & mask)
+			if (tab[s] == PAF_EMPTY && atomicCAS(&tab[s], PAF_EMPTY, (unsigned long long)((h >> 32) << 32 | g)) == PAF_EMPTY) break;
+		if (probe == PAF_PROBE_LIMIT) fail = 1;
+	}
+	blk_add_u64(&ctr[PC_OVERFLOW], fail);
+}
+// what a piece leaves behind for the 10-column lines of later pieces: out[0] = it has a line with an 11th column, out[1] = the bl of the last such line;
+// out[2] = the flags of its first line.  One wave walks back from the last line, 64 lines a step, at most ceil(L / 64) steps.
+__global__ __launch_bounds__(64) void k_stream_last_bl(const uint8_t *__restrict__ flags, const uint32_t *__restrict__ bl, uint32_t L, uint32_t *__restrict__ out)
+{
+	const uint32_t lane = threadIdx.x;
+	uint32_t has = 0, v = 0;
+	for (long top = (long)L; top > 0 && !has; top -= 64) {
+		const long i = top - 1 - (long)lane;
+		const bool mine = i >= 0 && (flags[i] & 4u);
+		const unsigned long long m = __ballot(mine);
+		if (m) { const int src = __ffsll((long long)m) - 1; v = wv_bcast(mine ? bl[i] : 0u, src); has = 1; } // the lowest lane holds the highest line
+	}
+	if (lane == 0) { out[0] = has; out[1] = v; out[2] = flags[0]; }
+}
+
+// a persistent buffer that must hold `need` bytes and keep its first `used`: a new one (at least twice the old) and a device-to-device copy
+static int stream_grow(mahip_ctx *c, DevBuf &b, size_t used, size_t need, int *grown = nullptr)
+{
+	if (need <= b.cap) return 0;
+	DevBuf nb;
+	CHK(dev_reserve(c, nb, need > 2 * b.cap ? need : 2 * b.cap));
+	if (used) HIPCHK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, c->st));
+	HIPCHK(hipStreamSynchronize(c->st)); // dev_free hands the old memory on at once
+	dev_free(c, b);
+	b = nb;
+	if (grown) *grown = 1;
+	return 0;
+}
+
+static int stream_table(mahip_ctx *c, PafStream *st, uint32_t cap)
+{ // a table of `cap` slots holding the names so far; a probe sequence that runs out: four times the slots
+	for (;; cap = cap < 0x40000000u ? cap << 2 : 0x80000000u) {
+		CHK(dev_reserve(c, st->tab, (size_t)cap * 8));
+		HIPCHK(hipMemsetAsync(st->tab.p, 0xff, (size_t)cap * 8, c->st));
+		CHK(ctr_zero(c));
+		if (st->n_seq) hipLaunchKernelGGL(k_stream_rebuild, dim3(grid_for(st->n_seq, 256, 8192)), dim3(256), 0, c->st, (const unsigned char*)P<unsigned char>(st->arena), (const uint32_t*)P<uint32_t>(st->name_pos),
+		                                  (const uint32_t*)P<uint32_t>(st->name_len), st->n_seq, P<unsigned long long>(st->tab), cap - 1, P<unsigned long long>(c->ctr));
+		CHK(ctr_fetch(c));
+		if (st->cap) ++st->rep.n_rebuilds; // (the first table replaces none)
+		st->cap = cap;
+		if (c->h_ctr[PC_OVERFLOW] == 0) return 0;
+		if (cap >= 0x80000000u) { mahip_set_error("mahip_paf_stream_piece_mem: name table overflow"); return -1; }
+	}
+}
+
+// the fold: the piece's local dictionary (paf_dict_local: b->names / name_pos / name_len / seq_len, R names in local first-appearance order) into the persistent one
+static int paf_stream_fold(mahip_ctx *c, PafBufs *b, PafStream *st, PafParse &ps)
+{
+	const uint32_t R = ps.R;
+	mahip_paf_stream_report_t &sr = st->rep;
+	if ((uint64_t)st->n_seq + R >= 0x7fffffffull) { mahip_set_error("mahip_paf_stream_piece_mem: too many names"); return -1; }
+	// growth is decided here, before the fold: the table is at most half full after it whatever the piece brings
+	if (st->cap == 0 || 2 * ((uint64_t)st->n_seq + R) > st->cap) {
+		uint32_t cap = st->cap;
+		if (cap == 0) {
+			cap = 1u << 16;
+			if (const char *e = getenv("MA_STREAM_DICT_CAP_LOG2")) { const int l2 = atoi(e); if (l2 >= 4 && l2 <= 31) cap = 1u << l2; }
+			if (2 * ((uint64_t)st->n_seq + R) > cap) cap = pow2_at_least(4 * ((uint64_t)st->n_seq + R));
+		} else {
+			const uint32_t want = pow2_at_least(4 * ((uint64_t)st->n_seq + R));
+			cap = cap < 0x20000000u ? cap << 2 : 0x80000000u;
+			if (want > cap) cap = want;
+		}
+		CHK(stream_table(c, st, cap));
+	}
+	// per local name: l2g | slot_of | blen | bpos (is_new and its scan live in the context's keep / pos)
+	CHK(dev_reserve(c, st->fold, ((size_t)R + 16) * 16));
+	CHK(dev_reserve(c, c->keep, ((size_t)R + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)R + 16) * 4));
+	uint32_t *l2g = P<uint32_t>(st->fold), *slot_of = l2g + R, *blen = slot_of + R, *bpos = blen + R;
+	uint32_t *is_new = P<uint32_t>(c->keep), *pos = P<uint32_t>(c->pos);
+	const unsigned char *lnames = (const unsigned char*)b->names.p;
+	const uint32_t *lpos = (const uint32_t*)b->name_pos.p, *llen = (const uint32_t*)b->name_len.p, *lseq = (const uint32_t*)b->seq_len.p;
+	for (;;) {
+		CHK(ctr_zero(c));
+		hipLaunchKernelGGL(k_stream_fold, dim3(grid_for(R, 256, 8192)), dim3(256), 0, c->st, lnames, lpos, llen, R, P<unsigned long long>(st->tab), st->cap - 1, (const unsigned char*)P<unsigned char>(st->arena),
+		                   (const uint32_t*)P<uint32_t>(st->name_pos), (const uint32_t*)P<uint32_t>(st->name_len), l2g, slot_of, is_new, blen, P<unsigned long long>(c->ctr));
+		CHK(ctr_fetch(c));
+		if (c->h_ctr[PC_OVERFLOW] == 0) break;
+		if (st->cap >= 0x80000000u) { mahip_set_error("mahip_paf_stream_piece_mem: name table overflow"); return -1; }
+		++sr.n_fold_repeats; // the claims of this launch die with the old table
+		CHK(stream_table(c, st, st->cap < 0x20000000u ? st->cap << 2 : 0x80000000u));
+	}
+	uint32_t tot[2] = { 0, 0 }; // new names, their bytes in the arena
+	CHK(scan_exclusive_u32(c, is_new, pos, R, P<uint32_t>(b->scal)));
+	CHK(scan_exclusive_u32(c, blen, bpos, R, P<uint32_t>(b->scal) + 1));
+	CHK(fetch_bytes(c, b->scal.p, tot, 8));
+	if ((uint64_t)st->arena_bytes + tot[1] >= 0xffffffffull) { mahip_set_error("mahip_paf_stream_piece_mem: more than 2^32 bytes of names"); return -1; }
+	const size_t ids = (size_t)st->n_seq, ids_new = ids + tot[0];
+	CHK(stream_grow(c, st->arena, st->arena_bytes, st->arena_bytes + tot[1] + 16));
+	CHK(stream_grow(c, st->seq_len, ids * 4, (ids_new + 4) * 4)); CHK(stream_grow(c, st->name_pos, ids * 4, (ids_new + 4) * 4)); CHK(stream_grow(c, st->name_len, ids * 4, (ids_new + 4) * 4));
+	hipLaunchKernelGGL(k_stream_commit, dim3(grid_for(R, 256)), dim3(256), 0, c->st, lnames, lpos, llen, lseq, R, (const uint32_t*)is_new, (const uint32_t*)pos, (const uint32_t*)bpos, (const uint32_t*)slot_of,
+	                   st->n_seq, (uint32_t)st->arena_bytes, P<unsigned long long>(st->tab), P<unsigned char>(st->arena), P<uint32_t>(st->name_pos), P<uint32_t>(st->name_len), P<uint32_t>(st->seq_len), l2g);
+	CHK(dev_reserve(c, st->map, (size_t)ps.cap_used * 4 + 16));
+	hipLaunchKernelGGL(k_stream_map, dim3(grid_for(ps.cap_used, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(b->tmin), (const uint32_t*)P<uint32_t>(b->slot_id), ps.cap_used, (const uint32_t*)l2g,
+	                   P<uint32_t>(st->map));
+	st->n_seq += tot[0]; st->arena_bytes += tot[1];
+	sr.last_local = R; sr.last_new = tot[0];
+	ps.slot_to_id = (const uint32_t*)P<uint32_t>(st->map);
+	return 0;
+}
+
+static double stream_now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec + 1e-9 * (double)t.tv_nsec; }
+
+static PafStream *stream_of(mahip_ctx *c, const char *who, bool must_be_active)
+{
+	PafBufs *b = (PafBufs*)c->paf;
+	PafStream *st = b ? b->stream : nullptr;
+	if (!st || (must_be_active && !st->active)) { mahip_set_error("%s: no stream in this context (mahip_paf_stream_begin first)", who); return nullptr; }
+	return st;
+}
+
+extern "C" int mahip_paf_stream_begin(mahip_ctx_t *c, int min_span, int min_match, int bi_dir)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (mahip_comm_active(c)) { mahip_set_error("mahip_paf_stream_begin: a context with a communicator parses ranges (mahip_paf_parse_sharded), not a stream"); return -1; }
+	PafBufs *b = paf_of(c);
+	HIPCHK(hipStreamSynchronize(c->st));
+	paf_stream_free(c, b);
+	PafStream *st = b->stream = new PafStream();
+	st->active = true; st->min_span = min_span; st->min_match = min_match; st->bi_dir = bi_dir != 0;
+	b->n_seq = 0; b->name_bytes = 0; b->loaded = false;
+	b->parsed = false; b->rep = {}; b->odd_snap.clear();
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, int last)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	PafStream *st = stream_of(c, "mahip_paf_stream_piece_mem", true);
+	if (!st) return -1;
+	PafBufs *b = paf_of(c);
+	mahip_paf_stream_report_t &sr = st->rep;
+	if (st->closed) { mahip_set_error("mahip_paf_stream_piece_mem: a piece behind the last piece"); return -1; }
+	if (nbytes && !last && ((const char*)text)[nbytes - 1] != '\n') { mahip_set_error("mahip_paf_stream_piece_mem: a piece that is not the last must end with a newline (pieces are whole lines)"); return -1; }
+	++sr.n_pieces;
+	if (last) st->closed = true;
+	if (!nbytes) { ++sr.n_empty; return 0; }
+	const double t0 = stream_now();
+	// ---- the piece's text (MA_PAF_MAX_BYTES counts its own bytes)
+	CHK(paf_reserve_text(c, nbytes));
+	CHK(xfer_copy(c, b->text.p, (void*)text, nbytes, 1));
+	b->loaded = true;
+	const double t1 = stream_now();
+	// ---- the stages of a whole parse on the piece
+	b->parsed = false; b->rep = {}; b->odd_snap.clear();
+	mahip_paf_report_t &rp = b->rep;
+	PafParse ps;
+	CHK(paf_census(c, b, ps));
+	if (st->n_lines + ps.L + 1 >= 0x7fffffffull) { mahip_set_error("mahip_paf_parse: more than 2^31 lines"); return -1; }
+	CHK(paf_reserve_cols(c, b, ps));
+	CHK(paf_fields(c, b, ps, st->min_span, st->min_match));
+	rp.n_lines = ps.L; rp.n_gran = ps.n_gran; rp.tile_k = ps.tile_k; rp.n_tiles = ps.n_tiles; rp.open_line = ps.open_line; rp.n_long = ps.n_long;
+	// ---- the stale bl (paf.c:54): a 10-column line in front of the piece's first 11-column line inherits from the last such line of ANY earlier piece (0 before the first)
+	const uint32_t before = st->have_bl ? st->last_bl : 0u;
+	sr.last_before = before;
+	if (ps.L && ps.n_valid) {
+		uint32_t lb[3] = { 0, 0, 0 };
+		hipLaunchKernelGGL(k_stream_last_bl, dim3(1), dim3(64), 0, c->st, (const uint8_t*)ps.o.flags, (const uint32_t*)ps.o.bl, ps.L, P<uint32_t>(b->scal) + 4);
+		CHK(fetch_bytes(c, P<uint32_t>(b->scal) + 4, lb, 12));
+		if (ps.n_nobl) {
+			rp.bl_pass = 1;
+			CHK(paf_stale_bl(c, b, ps, false, before));
+			if (st->have_bl && (lb[2] & 5u) == 1u) ++sr.n_inherited; // its first line is a 10-column line, and an earlier piece had left a bl
+		}
+		if (lb[0]) { st->have_bl = true; st->last_bl = lb[1]; }
+	}
+	double t_fold = 0.0;
+	// ---- names and records
+	sr.last_local = sr.last_new = 0;
+	if (ps.n_pass) {
+		CHK(paf_dict_local(c, b, ps, 0, 0, 0.f));
+		const double f0 = stream_now();
+		CHK(paf_stream_fold(c, b, st, ps));
+		t_fold = stream_now() - f0;
+		const size_t max_hits = st->bi_dir ? 2 * ps.n_pass : ps.n_pass;
+		if (st->n_rec + max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
+		if (st->rec_cap == 0) { // the first capacity
+			st->rec_cap = (size_t)1 << 20;
+			if (const char *e = getenv("MA_STREAM_REC_CAP")) { const long long v = atoll(e); if (v >= 1) st->rec_cap = (size_t)v; }
+			CHK(dev_reserve(c, st->rec, (st->rec_cap + 1) * sizeof(ma_hit_t)));
+		}
+		if (st->n_rec + max_hits > st->rec_cap) {
+			size_t want = 2 * st->rec_cap;
+			if (want < st->n_rec + max_hits) want = st->n_rec + max_hits;
+			CHK(stream_grow(c, st->rec, st->n_rec * sizeof(ma_hit_t), (want + 1) * sizeof(ma_hit_t)));
+			st->rec_cap = want;
+			++sr.n_rec_grow;
+		}
+		CHK(paf_records(c, b, ps, st->bi_dir, (ma_hit_t*)st->rec.p + st->n_rec));
+		st->n_rec += ps.n_hits;
+	}
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipStreamSynchronize(c->st));
+	// ---- the running totals
+	st->n_lines += ps.L; st->n_valid += ps.n_valid; st->n_pass += ps.n_pass;
+	if (ps.max_qs > st->max_qs) st->max_qs = ps.max_qs;
+	st->any_parsed = true;
+	sr.last_form = rp.dict_form;
+	sr.n_short += rp.dict_form == MAHIP_PAF_DICT_SHORT; sr.n_text += rp.dict_form == MAHIP_PAF_DICT_TEXT;
+	sr.tab_cap = st->cap;
+	const double t3 = stream_now();
+	sr.t_upload += t1 - t0; sr.t_fold += t_fold; sr.t_parse += (t3 - t1) - t_fold;
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	PafStream *st = stream_of(c, "mahip_paf_stream_end", true);
+	if (!st) return -1;
+	PafBufs *b = paf_of(c);
+	memset(info, 0, sizeof(*info));
+	HIPCHK(hipStreamSynchronize(c->st));
+	// the dictionary and the records change hands: they are laid out as a whole parse leaves them
+	dev_free(c, b->names); dev_free(c, b->name_pos); dev_free(c, b->seq_len); dev_free(c, b->name_len); dev_free(c, c->aos_own);
+	b->names = st->arena; b->name_pos = st->name_pos; b->seq_len = st->seq_len; b->name_len = st->name_len; c->aos_own = st->rec;
+	st->arena = DevBuf(); st->name_pos = DevBuf(); st->seq_len = DevBuf(); st->name_len = DevBuf(); st->rec = DevBuf();
+	dev_free(c, st->tab); dev_free(c, st->fold); dev_free(c, st->map);
+	b->n_seq = st->n_seq; b->name_bytes = st->arena_bytes;
+	PafParse ps;
+	ps.n_hits = st->n_rec; ps.R = st->n_seq;
+	CHK(paf_adopt(c, ps));
+	HIPCHK(hipStreamSynchronize(c->st));
+	c->hint_max_qs = c->paf_max_qs = st->max_qs;
+	c->run_stride = st->bi_dir ? 2 : 1; // still a line's record and its mirror side by side, in line order
+	b->parsed = true; // (mahip_paf_last / mahip_paf_cols_download: the last piece that had text; zeros when none had)
+	b->loaded = false;
+	info->n_records = st->n_valid; info->n_stored_lines = st->n_pass; info->n_hits = st->n_rec; info->n_seq = st->n_seq; info->max_qs = st->max_qs;
+	info->name_bytes = st->arena_bytes; info->n_lines = st->n_lines;
+	st->active = false;
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_abort(mahip_ctx_t *c)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	PafBufs *b = (PafBufs*)c->paf;
+	if (!b || !b->stream) return 0;
+	HIPCHK(hipStreamSynchronize(c->st));
+	paf_stream_free(c, b);
+	b->loaded = false; b->parsed = false;
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *out)
+{
+	PafStream *st = stream_of(c, "mahip_paf_stream_last", false);
+	if (!st) return -1;
+	if (out) *out = st->rep;
+	return 0;
 }
 
 extern "C" int mahip_paf_names(mahip_ctx_t *c, char *names, uint32_t *lens)

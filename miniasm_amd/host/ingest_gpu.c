@@ -3,13 +3,17 @@
  * The host only moves bytes: a plain file goes from the page cache straight into pinned staging slots and on to
  * HBM (mahip_paf_load_fd); a bgzip-compressed (BGZF) file goes to HBM as it is and is inflated there, one wave per block (mahip_bgzf_load_fd; the walk over
  * its member chain is below); a plain gzip file can be cut into chunks and inflated there too (MA_GZIP_DEVICE=1: mahip_gzip_load_fd; its header and trailer are
- * read below); otherwise gzip / stdin input is inflated into memory first (zlib, as the reference does through gzread) and uploaded.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
+ * read below); otherwise gzip / stdin input is read by zlib (as the reference does through gzread) one PIECE of whole lines at a time, and piece k is uploaded
+ * and parsed (mahip_paf_stream_piece_mem) while a second thread inflates piece k + 1 (ma_hit_ingest_stream below); MA_INGEST_STREAM=0, -R and ma_paf_load_file
+ * inflate the whole text into memory first and upload it.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
  * first-appearance ids and the (mirrored) hit records are all produced by csrc/paf.hip; what comes back is the
  * dictionary (names + first-seen lengths, R entries) and, only for the per-symbol ABI, the records.
  * The -R pre-filter (ma_hit_no_cont, hit.c:38-68) rides in the same parse: the exclusion is a flag per name.
  * MA_HOST_PARSE=1 forces the host reader (ingest_mt.c / paf_reader.c); both are pinned to the same records and ids.
  */
+#define _GNU_SOURCE /* memrchr */
 #include <fcntl.h>
+#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,6 +203,8 @@ int ma_gpu_parse_enabled(void)
 	return !(s && atoi(s) != 0);
 }
 
+static void ingest_dictionary(mahip_ctx_t *c, const mahip_paf_info_t *pi, sdict_t *d, size_t *n_hits, int release, double t1);
+
 /* parse the text already loaded into the context (mahip_paf_load_*): records stay on the device, the dictionary is
  * rebuilt in d (which must be empty or a previous result of this function); release = free the text afterwards */
 int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release)
@@ -209,17 +215,25 @@ int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d
 /* no_cont: -R, the reference's Step 0 (hit.c:38-68) folded into the same parse; prints its log line first */
 int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release, int no_cont, int max_hang, float int_frac)
 {
-	const int timing = ma_timing_level() >= 1;
-	double t1 = sys_realtime(), t2, t3;
+	double t1 = sys_realtime();
 	mahip_paf_info_t info;
-	size_t tot_len = 0;
 	GPU(mahip_set_shard(c, 0, 0xffffffffu));
 	GPU_SOFT(mahip_paf_parse_excl(c, min_span, min_match, bi_dir, no_cont, max_hang, int_frac, &info));
 	if (no_cont) {
 		if (ma_verbose >= 3) fprintf(MA_LOG, "[M::%s::%s] dropped %d contained reads\n", "ma_hit_no_cont", sys_timestamp(), info.n_excl);
 		fprintf(MA_LOG, "[M::%s] ===> Step 1: reading read mappings <===\n", "main");
 	}
-	t2 = sys_realtime();
+	ingest_dictionary(c, &info, d, n_hits, release, t1);
+	return 0;
+}
+
+/* what follows a parse, whole or streamed: the dictionary comes to the host, the reference's log line (hit.c:102) */
+static void ingest_dictionary(mahip_ctx_t *c, const mahip_paf_info_t *pi, sdict_t *d, size_t *n_hits, int release, double t1)
+{
+	const int timing = ma_timing_level() >= 1;
+	const mahip_paf_info_t info = *pi;
+	double t2 = sys_realtime(), t3;
+	size_t tot_len = 0;
 	/* the dictionary: the names in one block (the dictionary's arena) and the sd_seq_t records the device wrote for that block -- two copies, no
 	 * per-name work on the host */
 	{
@@ -240,14 +254,16 @@ int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict
 		fprintf(MA_LOG, "[M::%s::%s] read %ld hits; stored %ld hits and %d sequences (%ld bp)\n", "ma_hit_read", sys_timestamp(), (long)info.n_records, (long)info.n_hits, d->n_seq, (long)tot_len);
 	if (timing) fprintf(stderr, "[T::ingest_gpu] parse %.3f  dictionary%s %.3f s (%lu lines)\n", t2 - t1, release ? "+release" : "", t3 - t2, (unsigned long)info.n_lines);
 	*n_hits = (size_t)info.n_hits;
-	return 0;
 }
 
-/* file -> HBM; 0 ok, -1 = could not open */
-int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
+/* file -> HBM; 0 ok, -1 = could not open, -2 = the device refused.  The ladder: a plain file whole, bgzip on the device, plain gzip on the device when enabled, and
+ * on the last rung zlib on the host.  stream_fp == 0: the last rung inflates everything and uploads it.  Otherwise the last rung is left to the caller: 1 is
+ * returned with the input open in *stream_fp (*seekable: a regular file, which a reader that starts over can open again); force_stream: every input goes that way. */
+static int paf_load_ladder(mahip_ctx_t *c, const char *fn, gzFile *stream_fp, int *seekable, int force_stream)
 {
 	int fd = -1, is_plain = 0, is_reg = 0;
 	struct stat st;
+	if (seekable) *seekable = 0;
 	if (fn && strcmp(fn, "-") != 0) {
 		unsigned char magic[2] = { 0, 0 };
 		fd = open(fn, O_RDONLY);
@@ -257,6 +273,12 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 			is_reg = 1;
 			is_plain = !(r == 2 && magic[0] == 0x1f && magic[1] == 0x8b);
 		}
+	}
+	if (seekable) *seekable = is_reg;
+	if (stream_fp && force_stream) {
+		*stream_fp = fd >= 0 ? gzdopen(fd, "r") : gzdopen(fileno(stdin), "r");
+		if (*stream_fp == 0) { if (fd >= 0) close(fd); return -1; }
+		return 1;
 	}
 	if (is_plain) {
 		if (mahip_paf_load_fd(c, fd, (size_t)st.st_size) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
@@ -290,6 +312,7 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 		size_t len = 0;
 		char *buf;
 		if (fp == 0) { if (fd >= 0) close(fd); return -1; }
+		if (stream_fp) { *stream_fp = fp; return 1; }
 		gzbuffer(fp, 1u << 20);
 		buf = slurp_gz(fp, &len);
 		gzclose(fp);
@@ -299,8 +322,166 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn)
 	return 0;
 }
 
+int ma_paf_load_file(mahip_ctx_t *c, const char *fn) { return paf_load_ladder(c, fn, 0, 0, 0); }
+
+/* MA_INGEST_STREAM: 0 = gzip / stdin input is inflated whole before the first byte is uploaded; 1 = EVERY input is streamed piece by piece, plain, bgzip and gzip
+ * files too (tests reach the streamed road with any file); unset: MA_INGEST_STREAM_DEFAULT, where -1 = stream what reaches the ladder's last rung (DESIGN 7 has
+ * the measurement the default follows from) */
+#define MA_INGEST_STREAM_DEFAULT -1
+int ma_ingest_stream_mode(void)
+{
+	const char *s = getenv("MA_INGEST_STREAM");
+	return s && *s ? (atoi(s) != 0) : MA_INGEST_STREAM_DEFAULT;
+}
+/* MA_INGEST_PIECE: bytes of text per piece, clamped to [256, 1 GiB] */
+#define MA_INGEST_PIECE_DEFAULT ((size_t)16 << 20)
+size_t ma_ingest_piece(void)
+{
+	const char *s = getenv("MA_INGEST_PIECE");
+	long long v = s && *s ? atoll(s) : (long long)MA_INGEST_PIECE_DEFAULT;
+	return v < 256 ? (size_t)256 : v > (1ll << 30) ? (size_t)1 << 30 : (size_t)v;
+}
+
+/* ---- cut and carry.  The reader hands out pieces of WHOLE LINES: it fills a buffer with what the last piece left over (the carry: the bytes behind its last
+ * newline) and `piece` more bytes, cuts behind the last newline (memrchr) and keeps the rest for the next piece.  A buffer without any newline grows by another
+ * `piece` and is read on, so a line longer than a piece -- than any number of pieces -- is one piece.  The end of the input hands over what is left, newline or
+ * not, as the last piece.  The source is a callback, so that tests/stream_cut_main.c can drive the same code from a pipe with small buffers. */
+int ma_cut_next(ma_cut_t *k, char **buf, size_t *cap, size_t *len, int *last)
+{
+	size_t n = k->carry_len, target;
+	if (*cap < n + k->piece) {
+		char *nb = (char*)realloc(*buf, n + k->piece);
+		if (nb == 0) return -1;
+		*buf = nb; *cap = n + k->piece;
+	}
+	if (n) memcpy(*buf, k->carry, n);
+	k->carry_len = 0;
+	target = n + k->piece;
+	for (;;) {
+		while (n < target) {
+			size_t want = target - n < ((size_t)1 << 30) ? target - n : (size_t)1 << 30;
+			long got = k->read(k->src, *buf + n, want);
+			if (got <= 0) { *len = n; *last = 1; return 0; } /* the end (zlib reports a damaged stream the same way; what it gave so far counts, as in the reference) */
+			n += (size_t)got;
+		}
+		{
+			const char *nl = (const char*)memrchr(*buf, '\n', n);
+			if (nl) {
+				const size_t cut = (size_t)(nl - *buf) + 1, rest = n - cut;
+				if (rest > k->carry_cap) {
+					char *nc = (char*)realloc(k->carry, rest);
+					if (nc == 0) return -1;
+					k->carry = nc; k->carry_cap = rest;
+				}
+				if (rest) memcpy(k->carry, *buf + cut, rest);
+				k->carry_len = rest;
+				*len = cut; *last = 0;
+				return 0;
+			}
+		}
+		{ /* one line so far: more room, read on */
+			char *nb = (char*)realloc(*buf, *cap + k->piece);
+			if (nb == 0) return -1;
+			*buf = nb; *cap += k->piece; target += k->piece;
+		}
+	}
+}
+
+static long gz_read_cb(void *src, char *dst, size_t want) { return (long)gzread((gzFile)src, dst, (unsigned)want); }
+
+/* two buffers between the producer (zlib + the cut) and the calling thread (upload + parse): state 0 = the producer's, 1 = holds a piece */
+typedef struct {
+	ma_cut_t cut;
+	pthread_mutex_t mu;
+	pthread_cond_t cv;
+	struct { char *p; size_t cap, len; int last, full; } b[2];
+	int stop, failed; /* the consumer gave up; the producer ran out of memory */
+	double t_prod;
+} stream_q_t;
+
+static void *stream_producer(void *arg)
+{
+	stream_q_t *q = (stream_q_t*)arg;
+	int i = 0;
+	for (;; i ^= 1) {
+		double t0;
+		int rc;
+		pthread_mutex_lock(&q->mu);
+		while (q->b[i].full && !q->stop) pthread_cond_wait(&q->cv, &q->mu);
+		if (q->stop) { pthread_mutex_unlock(&q->mu); break; }
+		pthread_mutex_unlock(&q->mu);
+		t0 = sys_realtime();
+		rc = ma_cut_next(&q->cut, &q->b[i].p, &q->b[i].cap, &q->b[i].len, &q->b[i].last);
+		q->t_prod += sys_realtime() - t0;
+		pthread_mutex_lock(&q->mu);
+		if (rc != 0) { q->failed = 1; q->b[i].len = 0; q->b[i].last = 1; }
+		q->b[i].full = 1;
+		pthread_cond_broadcast(&q->cv);
+		pthread_mutex_unlock(&q->mu);
+		if (q->b[i].last) break;
+	}
+	return 0;
+}
+
+/* the text behind fp (plain or gzip, file or pipe) piece by piece through the streamed parse: 0 = the records are in the context and d holds the dictionary, as
+ * after ma_hit_ingest_loaded; -2 = the device refused (the stream is aborted, the text stage released; fp has been read from).  fp stays open. */
+int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes)
+{
+	const int timing = ma_timing_level() >= 1;
+	const double t0 = sys_realtime();
+	double t_wait = 0.0;
+	stream_q_t q;
+	pthread_t th;
+	mahip_paf_info_t info;
+	mahip_paf_stream_report_t sr;
+	int i = 0, bad = 0;
+	memset(&q, 0, sizeof(q));
+	memset(&sr, 0, sizeof(sr));
+	q.cut.piece = piece_bytes; q.cut.read = gz_read_cb; q.cut.src = fp;
+	gzbuffer(fp, 1u << 20);
+	pthread_mutex_init(&q.mu, 0);
+	pthread_cond_init(&q.cv, 0);
+	GPU(mahip_set_shard(c, 0, 0xffffffffu));
+	if (mahip_paf_stream_begin(c, min_span, min_match, bi_dir) != 0) bad = 1;
+	if (!bad && pthread_create(&th, 0, stream_producer, &q) != 0) { mahip_paf_stream_abort(c); ma_gpu_fail(__func__); }
+	for (; !bad; i ^= 1) {
+		const double w0 = sys_realtime();
+		int last;
+		pthread_mutex_lock(&q.mu);
+		while (!q.b[i].full) pthread_cond_wait(&q.cv, &q.mu);
+		pthread_mutex_unlock(&q.mu);
+		t_wait += sys_realtime() - w0;
+		last = q.b[i].last;
+		if (q.failed) { fprintf(stderr, "[E::%s] out of memory for a piece of the input\n", __func__); exit(1); }
+		if (mahip_paf_stream_piece_mem(c, q.b[i].p, q.b[i].len, last) != 0) bad = 1;
+		pthread_mutex_lock(&q.mu);
+		q.b[i].full = 0;
+		if (bad) q.stop = 1;
+		pthread_cond_broadcast(&q.cv);
+		pthread_mutex_unlock(&q.mu);
+		if (last || bad) { pthread_join(th, 0); break; }
+	}
+	if (!bad && mahip_paf_stream_end(c, &info) != 0) bad = 1;
+	mahip_paf_stream_last(c, &sr);
+	free(q.b[0].p); free(q.b[1].p); free(q.cut.carry);
+	pthread_mutex_destroy(&q.mu);
+	pthread_cond_destroy(&q.cv);
+	if (bad) {
+		fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror());
+		mahip_paf_stream_abort(c);
+		mahip_paf_release(c);
+		return -2;
+	}
+	if (timing)
+		fprintf(stderr, "[T::ingest_gpu] stream: pieces=%lu piece=%lu B producer %.3f upload %.3f parse %.3f fold %.3f waited-for-input %.3f s\n", (unsigned long)sr.n_pieces,
+		        (unsigned long)piece_bytes, q.t_prod, sr.t_upload, sr.t_parse, sr.t_fold, t_wait);
+	ingest_dictionary(c, &info, d, n_hits, 1, t0);
+	return 0;
+}
+
 /* returns 0 and leaves the unsorted records in the context (as after mahip_hits_upload); -1 = could not open;
- * -2 = the device-side stage could not run (memory): nothing was consumed, the caller may use the host reader */
+ * -2 = the device-side stage could not run (memory): the caller may use the host reader, which opens the file again (input that cannot be read twice -- stdin,
+ * a pipe -- and was being streamed when the device refused is an error of the run instead) */
 int ma_hit_ingest_gpu(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir)
 {
 	return ma_hit_ingest_gpu_excl(c, fn, min_span, min_match, d, n_hits, bi_dir, 0, 0, 0.f);
@@ -308,10 +489,21 @@ int ma_hit_ingest_gpu(mahip_ctx_t *c, const char *fn, int min_span, int min_matc
 
 int ma_hit_ingest_gpu_excl(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int no_cont, int max_hang, float int_frac)
 {
-	const int timing = ma_timing_level() >= 1;
+	const int timing = ma_timing_level() >= 1, mode = ma_ingest_stream_mode();
 	double t0 = sys_realtime();
 	{
-		int rc = ma_paf_load_file(c, fn);
+		gzFile fp = 0;
+		int seekable = 0;
+		int rc = paf_load_ladder(c, fn, !no_cont && mode != 0 && !mahip_comm_active(c) ? &fp : 0, &seekable, mode == 1); /* -R never streams: its exclusion needs every line before any id is given out; nor does a rank of several */
+		if (rc == 1) { /* the last rung, piece by piece */
+			rc = ma_hit_ingest_stream(c, fp, min_span, min_match, d, n_hits, bi_dir, ma_ingest_piece());
+			gzclose(fp);
+			if (rc == -2 && !seekable) {
+				fprintf(stderr, "[E::%s] the device refused a piece of the input (%s), and what was read of it cannot be read again\n", __func__, mahip_strerror());
+				exit(1);
+			}
+			return rc;
+		}
 		if (rc != 0) return rc; /* -1 cannot open, -2 does not fit */
 	}
 	if (timing) fprintf(stderr, "[T::ingest_gpu] load %.3f s\n", sys_realtime() - t0);

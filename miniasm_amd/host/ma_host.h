@@ -4,6 +4,7 @@
 
 #include "miniasm_amd.h"
 #include "mahip.h"
+#include <zlib.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -74,6 +75,14 @@ int ma_ingest_sharded_possible(const char *fn);
 int ma_hit_ingest_sharded(mahip_ctx_t *c, const char *fn, int min_span, int min_match, sdict_t *d, size_t *n_hits_total, int bi_dir, ma_ingest_shard_info_t *si);
 int ma_hit_ingest_loaded_excl(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release, int no_cont, int max_hang, float int_frac);
 int ma_paf_load_file(mahip_ctx_t *c, const char *fn); /* plain / gzip / "-": text into HBM */
+/* the streamed road (ingest_gpu.c): the text behind an open gzFile (plain or gzip; a file, stdin or a pipe) in pieces of about piece_bytes of whole lines, piece k
+ * uploaded and parsed while a second thread inflates piece k + 1; 0 = records in the context and d filled, as ma_hit_ingest_loaded leaves them; -2 = the device refused */
+int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes);
+int ma_ingest_stream_mode(void); /* MA_INGEST_STREAM: 0 off, 1 every input, -1 (unset) what reaches zlib on the host */
+size_t ma_ingest_piece(void);    /* MA_INGEST_PIECE or the default, clamped to [256, 1 GiB] */
+/* the cut-and-carry reader of that road, on its own (tests/stream_cut_main.c): pieces of whole lines from a byte source */
+typedef struct { size_t piece; long (*read)(void *src, char *dst, size_t want); void *src; char *carry; size_t carry_len, carry_cap; } ma_cut_t;
+int ma_cut_next(ma_cut_t *k, char **buf, size_t *cap, size_t *len, int *last); /* the next piece into *buf (grown as needed); 0 ok, -1 out of memory */
 int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release);
 int ma_gpu_parse_enabled(void); /* 0 when MA_HOST_PARSE=1 */
 int ma_gzip_device_enabled(void); /* MA_GZIP_DEVICE: plain gzip files are cut into chunks and inflated on the device (ingest_gpu.c) */

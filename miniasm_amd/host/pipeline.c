@@ -429,7 +429,8 @@ int ma_pipeline_run(const ma_opt_t *opt, const char *fn, const char *outfmt, int
 	ma_hit_t *hit;
 	size_t n_hits = 0;
 	FILE *lg = MA_LOG;
-	const int dev_parse = ma_gpu_parse_enabled() && strcmp(fn, "-") != 0;
+	/* stdin goes to the device piece by piece (ingest_gpu.c: ma_hit_ingest_stream); with MA_INGEST_STREAM=0, or with -R (which reads its input twice), it is the host reader's */
+	const int dev_parse = ma_gpu_parse_enabled() && (strcmp(fn, "-") != 0 || (ma_ingest_stream_mode() != 0 && !(flags & 8)));
 	int on_device = 0;
 	if (flags & 8) fprintf(lg, "[M::%s] ===> Step 0: removing contained reads <===\n", "main");
 	if (dev_parse) { /* text -> records + dictionary on the device (csrc/paf.hip); with -R the pre-filter rides in the same parse */
@@ -448,7 +449,7 @@ int ma_pipeline_run(const ma_opt_t *opt, const char *fn, const char *outfmt, int
 		if (flags & 8) excl = ma_hit_no_cont(fn, opt->min_span, opt->min_match, opt->max_hang, opt->int_frac);
 		if (!dev_parse || (flags & 8)) fprintf(lg, "[M::%s] ===> Step 1: reading read mappings <===\n", "main");
 	}
-	if (!on_device) { /* MA_HOST_PARSE=1, stdin (a stream cannot be re-read after a failed device attempt), or a text too big for the device stage */
+	if (!on_device) { /* MA_HOST_PARSE=1, stdin that is not streamed (a stream cannot be re-read after a failed device attempt), or a text too big for the device stage */
 		const int timing = ma_timing_level() >= 1;
 		double t0 = sys_realtime(), t1, t2;
 		hit = ma_hit_ingest(fn, opt->min_span, opt->min_match, d, &n_hits, !(flags & 4), excl);

@@ -2,7 +2,9 @@
 """Randomised differential test WITHOUT a GPU: random pafgen inputs (incl. tie-rich grids, noise, tiny and deep reads) and random
 command-line options, the unmodified reference binary (oracle/_ref/miniasm_ref) against the CPU build of the kernel sources
 (tests/emu/_build/miniasm), every dump format, bytes compared.  Test tooling: `python tools/fuzz_emu.py --cases 200 --seed 1`.
-With --ranks the same case is also run as MA_GPUS=N over the shared-memory double."""
+With --ranks the same case is also run as MA_GPUS=N over the shared-memory double.  With --stream the case's text also goes through the streamed ingest: cut at
+random line borders into pieces (empty and single-line pieces included) through mahip_paf_stream_* of the CPU build, compared with the whole parse, the host reader
+and the reference library; and through the command line with MA_INGEST_STREAM=1 and a random MA_INGEST_PIECE, compared with the reference binary."""
 import argparse
 import gzip
 import hashlib
@@ -210,8 +212,46 @@ def write_gzip(rng, data, path):
     open(path, "wb").write(h + body + struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff))
 
 
+_stream = None
+
+
+def stream_case(rng, data, tmp):
+    """the text cut at random line borders -> the streamed ingest of the CPU build against the whole parse, the host reader and the reference library (the
+    comparison is tests/test_gpu_ingest_stream.py's); an AssertionError says what differs"""
+    global _stream
+    if _stream is None:
+        os.environ["MA_EMU_BUILD"] = os.path.basename(os.path.dirname(EMU))
+        sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import emu_plugin  # noqa: F401  (points the ctypes harness at the CPU build)
+        import miniasm_amd as ma
+        import test_gpu_ingest_stream as T
+        _stream = (T, ma.Ctx(0))
+    T, ctx = _stream
+    lines = data.splitlines(keepends=True)
+    how = rng.choice(["few", "many", "single", "one"])
+    lines = lines[:300 if how == "single" else 3000]  # (the CPU build takes a piece in tens of milliseconds)
+    n_cut = 0 if how == "one" else len(lines) if how == "single" else rng.randint(1, 4) if how == "few" else rng.randint(5, 60)
+    cuts = sorted(rng.randint(0, len(lines)) for _ in range(n_cut)) if how != "single" else list(range(1, len(lines)))
+    pieces, last = [], 0
+    for c in cuts + [len(lines)]:
+        pieces.append(b"".join(lines[last:c]))  # (equal cuts: an empty piece)
+        last = c
+    for _ in range(rng.choice([0, 0, 1, 3])):
+        pieces.insert(rng.randint(0, len(pieces)), b"")
+    ms, mm = rng.choice([(2000, 100), (0, 0), (500, 40)])
+    env = {}
+    if rng.random() < 0.4:
+        env["MA_STREAM_DICT_CAP_LOG2"] = rng.choice([4, 6, 10])
+    if rng.random() < 0.4:
+        env["MA_STREAM_REC_CAP"] = rng.choice([1, 8, 1000])
+    T.check(ctx, tmp, pieces, ms, mm, rng.randint(0, 1), **env)
+    return len(pieces)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--stream", action="store_true", help="the streamed ingest: the text cut at random line borders through mahip_paf_stream_* (against the whole parse, the host reader, the reference library), and the command line under MA_INGEST_STREAM=1 with a random MA_INGEST_PIECE")
     ap.add_argument("--gzip", action="store_true", help="every case also runs on its PAF text as a plain gzip file (random level, memLevel, strategy, flush points, header fields) with MA_GZIP_DEVICE=1 and a random MA_GZIP_CHUNK: the chunked device inflater; the road taken is tallied by reason")
     ap.add_argument("--seq", action="store_true", help="unitig sequences: every case also gets a random reads file and runs with -f (ma_ug_seq; the device byte gather)")
     ap.add_argument("--text", action="store_true", help="damage the PAF text (reader / dictionary semantics) instead of varying the options")
@@ -235,7 +275,7 @@ def main():
     rng = random.Random(a.seed)
     tmp = tempfile.mkdtemp(prefix="ma_fuzz_")
     paf = os.path.join(tmp, "f.paf")
-    bad = skipped = 0
+    bad = skipped = n_pieces_cut = 0
     paths, readers = {}, {}
     for k in range(a.cases):
         gen, args = rand_case(rng)
@@ -251,6 +291,19 @@ def main():
             reads = os.path.join(tmp, "reads.fx")
             write_reads(rng, paf, reads)
             args = [x for x in args if x not in ("-p", "sg", "paf", "bed", "ug") and not x.startswith("-S")] + ["-f", reads]
+        if a.stream:
+            if len(open(paf, "rb").read()) > (2 << 20):
+                continue  # (small texts, many cuts)
+            if rng.random() < 0.5 and not a.text:
+                open(paf, "wb").write(mutate_text(rng, open(paf, "rb").read()))
+            try:
+                n_pieces_cut += stream_case(rng, open(paf, "rb").read(), tmp)
+            except AssertionError as e:
+                bad += 1
+                print("case %d MISMATCH [stream, cut at line borders]: pafgen %s: %s" % (k, " ".join(gen), str(e)[:300]))
+                if a.keep:
+                    os.makedirs(a.keep, exist_ok=True)
+                    open(os.path.join(a.keep, "case%d.paf" % k), "wb").write(open(paf, "rb").read())
         rc0, out0, err0 = run(REF, args, paf)
         if rc0 < 0:  # the reference itself dies on this combination (e.g. -p bed -S1 dereferences the intervals before they exist): nothing to compare
             skipped += 1
@@ -259,6 +312,8 @@ def main():
         if a.gzip:
             write_gzip(rng, open(paf, "rb").read(), paf + ".gz")
             runs.append(("emu gzip", {"MA_GZIP_DEVICE": "1", "MA_GZIP_CHUNK": str(1024 << rng.randint(0, 6)), "FILE": paf + ".gz"}))
+        if a.stream:
+            runs.append(("emu stream", {"MA_INGEST_STREAM": "1", "MA_INGEST_PIECE": str(max(256, os.path.getsize(paf) // rng.choice([1, 2, 7, 40, 200])))}))
         if a.seq:  # the same case with the host reader of the reads file: both must equal the reference
             runs.append(("emu host reader", {"MA_FASTX_HOST": "1"}))
         if a.ranks > 1:  # requests the sharded head does not serve fall back to one GPU: the bytes must be the same either way
@@ -297,6 +352,8 @@ def main():
     print("tie paths taken:", paths)
     if a.seq or a.gzip:
         print("readers taken:", readers)
+    if a.stream:
+        print("pieces handed to mahip_paf_stream_piece_mem:", n_pieces_cut)
     print("done: %d cases, %d mismatches, %d skipped (reference crashed)" % (a.cases, bad, skipped))
     sys.exit(1 if bad else 0)
 
