@@ -130,12 +130,16 @@ typedef struct {
 	uint32_t last_before;             /* ... the bl its 10-column lines in front of its first 11-column line inherit */
 	int last_form;                    /* ... its MAHIP_PAF_DICT_* */
 	double t_upload, t_parse, t_fold; /* seconds so far: text to the device; the stages of the parse; the fold into the persistent dictionary */
+	uint32_t n_arena_grow, n_ids_grow; /* pieces for which the names arena / any of the three per-id arrays was replaced by a larger one (the first buffers replace none) */
 } mahip_paf_stream_report_t;
 int mahip_paf_stream_begin(mahip_ctx_t *c, int min_span, int min_match, int bi_dir);
 int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, int last);
 int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info);
 int mahip_paf_stream_abort(mahip_ctx_t *c);
 int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *out);   /* valid from begin until the next begin, abort or mahip_paf_release */
+/* read-only, between begin and end: the persistent name table as it stands, report.tab_cap words of tag(32) | id, all ones = free (no slots before the first
+ * piece that stored a line).  Between pieces no word holds a provisional claim (bit 31 of the low word).  For tests. */
+int mahip_paf_stream_tab_download(mahip_ctx_t *c, uint64_t *slots);
 int mahip_hits_raw_download(mahip_ctx_t *c, ma_hit_t *out);                 /* the unsorted records held by the context (n_hits of them) */
 /* device-to-device: the unsorted records whose query id lies in [q_beg,q_end), in input order, into d_dst (NULL: only count
  * them); *n_out = their number.  Lets a caller keep the records of one read-range shard (bench.py, multi-GPU set-up). */

@@ -157,7 +157,7 @@ class PafStreamReport(C.Structure):  # include/mahip.h: mahip_paf_stream_report_
     _fields_ = [("n_pieces", C.c_uint64), ("n_empty", C.c_uint64), ("n_short", C.c_uint64), ("n_text", C.c_uint64), ("n_inherited", C.c_uint64),
                 ("tab_cap", C.c_uint32), ("n_rebuilds", C.c_uint32), ("n_fold_repeats", C.c_uint32), ("n_rec_grow", C.c_uint32),
                 ("last_local", C.c_uint32), ("last_new", C.c_uint32), ("last_before", C.c_uint32), ("last_form", C.c_int),
-                ("t_upload", C.c_double), ("t_parse", C.c_double), ("t_fold", C.c_double)]
+                ("t_upload", C.c_double), ("t_parse", C.c_double), ("t_fold", C.c_double), ("n_arena_grow", C.c_uint32), ("n_ids_grow", C.c_uint32)]
 
 
 PAF_DICT_FORMS = {0: None, 1: "short", 2: "text"}  # MAHIP_PAF_DICT_*
@@ -232,6 +232,7 @@ def lib():
         L.mahip_paf_stream_end.argtypes = [vp, C.POINTER(PafInfo)]
         L.mahip_paf_stream_abort.argtypes = [vp]
         L.mahip_paf_stream_last.argtypes = [vp, C.POINTER(PafStreamReport)]
+        L.mahip_paf_stream_tab_download.argtypes = [vp, vp]
         L.mahip_hits_sort.argtypes = [vp]
         L.mahip_hits_index.argtypes = [vp]
         L.mahip_hits_sub.argtypes = [vp, i32, C.c_float, i32, i32, C.POINTER(sz)]

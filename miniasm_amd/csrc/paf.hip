@@ -1573,9 +1573,9 @@ static int stream_grow(mahip_ctx *c, DevBuf &b, size_t used, size_t need, int *g
 	CHK(dev_reserve(c, nb, need > 2 * b.cap ? need : 2 * b.cap));
 	if (used) HIPCHK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, c->st));
 	HIPCHK(hipStreamSynchronize(c->st)); // dev_free hands the old memory on at once
+	if (grown && b.p) *grown = 1; // (the first buffer replaces none)
 	dev_free(c, b);
 	b = nb;
-	if (grown) *grown = 1;
 	return 0;
 }
 
@@ -1622,7 +1622,8 @@ static int paf_stream_fold(mahip_ctx *c, PafBufs *b, PafStream *st, PafParse &ps
 	uint32_t *is_new = P<uint32_t>(c->keep), *pos = P<uint32_t>(c->pos);
 	const unsigned char *lnames = (const unsigned char*)b->names.p;
 	const uint32_t *lpos = (const uint32_t*)b->name_pos.p, *llen = (const uint32_t*)b->name_len.p, *lseq = (const uint32_t*)b->seq_len.p;
-	for (;;) {
+	for (int repeat = 0;; ++repeat) {
+		if (repeat > 16) { mahip_set_error("mahip_paf_stream_piece_mem: the fold ran out of probes on %d tables", repeat); return -1; } // (every repeat has 4 x the slots: 14 lead from 16 to 2^31)
 		CHK(ctr_zero(c));
 		hipLaunchKernelGGL(k_stream_fold, dim3(grid_for(R, 256, 8192)), dim3(256), 0, c->st, lnames, lpos, llen, R, P<unsigned long long>(st->tab), st->cap - 1, (const unsigned char*)P<unsigned char>(st->arena),
 		                   (const uint32_t*)P<uint32_t>(st->name_pos), (const uint32_t*)P<uint32_t>(st->name_len), l2g, slot_of, is_new, blen, P<unsigned long long>(c->ctr));
@@ -1638,8 +1639,10 @@ static int paf_stream_fold(mahip_ctx *c, PafBufs *b, PafStream *st, PafParse &ps
 	CHK(fetch_bytes(c, b->scal.p, tot, 8));
 	if ((uint64_t)st->arena_bytes + tot[1] >= 0xffffffffull) { mahip_set_error("mahip_paf_stream_piece_mem: more than 2^32 bytes of names"); return -1; }
 	const size_t ids = (size_t)st->n_seq, ids_new = ids + tot[0];
-	CHK(stream_grow(c, st->arena, st->arena_bytes, st->arena_bytes + tot[1] + 16));
-	CHK(stream_grow(c, st->seq_len, ids * 4, (ids_new + 4) * 4)); CHK(stream_grow(c, st->name_pos, ids * 4, (ids_new + 4) * 4)); CHK(stream_grow(c, st->name_len, ids * 4, (ids_new + 4) * 4));
+	int grew_arena = 0, grew_ids = 0;
+	CHK(stream_grow(c, st->arena, st->arena_bytes, st->arena_bytes + tot[1] + 16, &grew_arena));
+	CHK(stream_grow(c, st->seq_len, ids * 4, (ids_new + 4) * 4, &grew_ids)); CHK(stream_grow(c, st->name_pos, ids * 4, (ids_new + 4) * 4, &grew_ids)); CHK(stream_grow(c, st->name_len, ids * 4, (ids_new + 4) * 4, &grew_ids));
+	sr.n_arena_grow += grew_arena; sr.n_ids_grow += grew_ids;
 	hipLaunchKernelGGL(k_stream_commit, dim3(grid_for(R, 256)), dim3(256), 0, c->st, lnames, lpos, llen, lseq, R, (const uint32_t*)is_new, (const uint32_t*)pos, (const uint32_t*)bpos, (const uint32_t*)slot_of,
 	                   st->n_seq, (uint32_t)st->arena_bytes, P<unsigned long long>(st->tab), P<unsigned char>(st->arena), P<uint32_t>(st->name_pos), P<uint32_t>(st->name_len), P<uint32_t>(st->seq_len), l2g);
 	CHK(dev_reserve(c, st->map, (size_t)ps.cap_used * 4 + 16));
@@ -1799,6 +1802,15 @@ extern "C" int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *
 	PafStream *st = stream_of(c, "mahip_paf_stream_last", false);
 	if (!st) return -1;
 	if (out) *out = st->rep;
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_tab_download(mahip_ctx_t *c, uint64_t *slots)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	PafStream *st = stream_of(c, "mahip_paf_stream_tab_download", true);
+	if (!st) return -1;
+	if (st->cap) CHK(fetch_bytes(c, st->tab.p, slots, (size_t)st->cap * 8));
 	return 0;
 }
 

@@ -4,7 +4,8 @@
  * count and FNV-1a hash, computed on the way in and on the way out) -- and prints "OK <pieces> <bytes> <longest piece>".
  *   gcc -g -fsanitize=address,undefined -static-libasan -Iinclude -Iminiasm_amd/host -Iminiasm_amd/csrc tests/stream_cut_main.c miniasm_amd/host/ingest_gpu.c \
  *       -Ltests/emu/_build -lminiasm_amd_emu -Wl,-rpath,$PWD/tests/emu/_build -lz -lpthread -o /tmp/stream_cut && head -c 300000 x.paf | /tmp/stream_cut 256 7
- * (the library only supplies what the rest of ingest_gpu.c refers to; nothing of it runs).  Never loaded into Python, never run on a GPU. */
+ * (the library only supplies what the rest of ingest_gpu.c refers to; nothing of it runs).  Never loaded into Python, never run on a GPU.
+ * tests/test_stream_cut_cpu.py builds it so and drives it from a pipe, over piece and read sizes, against a model of the rule. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

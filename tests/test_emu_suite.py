@@ -24,7 +24,12 @@ tests; the 132 MiB round trips take about a second each, the three 2048 x 2048-e
 together reversed with guard pages, and 10 s of build + 13 s of run for the copy workers under the thread sanitizer.
 tests/test_gpu_ingest_shard_edges.py adds about three quarters of a minute: 16 s in normal order for its 141 tests (five runs of 2, 3, 5, 8 and 3 child processes, 139
 cases in all: 2.3 s, 2.2 s, 3.0 s, 5.8 s and 0.3 s of wall time, most of it process start-up, so nothing is held back for MA_EMU_FULL) and 26 s reversed with guard
-pages (2.8 s, 2.9 s, 4.9 s, 13.0 s and 0.4 s), both on 16 cores."""
+pages (2.8 s, 2.9 s, 4.9 s, 13.0 s and 0.4 s), both on 16 cores.
+tests/test_gpu_ingest_stream_edges.py (run by tests/test_ingest_stream_emu.py) adds about a minute and three quarters: 50 s in normal order for its 69 tests and 50 s reversed
+with guard pages and the pool off, both on 8 cores.  Its slowest case, the refusal in the middle of a stream (five runs of the command line, the module's shared
+input included), takes 14 s, the two truncated gzip streams 4 s each, the two crowded probe chains 2 to 4 s each and the child process with the pool off 5 s, so nothing
+is held back for MA_EMU_FULL.  tests/test_stream_cut_cpu.py (the cut-and-carry reader as a stand-alone program under the address and undefined-behaviour
+sanitizers) takes 5 s, its build included."""
 import os
 import subprocess
 import sys
