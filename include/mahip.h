@@ -360,10 +360,51 @@ int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_
                           uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms);
 /* What the LAST ma_ug_seq of this context did (host bookkeeping, noted by host/unitig_gfa.c through mahip_useq_note; the tests assert from it that an input reached
  * the reader it was built for): reader 1 = host, 2 = device; reason: why the host reader ran (MAHIP_FASTX_*). */
-enum { MAHIP_USEQ_HOST = 1, MAHIP_USEQ_DEVICE = 2 };
+enum { MAHIP_USEQ_HOST = 1, MAHIP_USEQ_DEVICE = 2, MAHIP_USEQ_STREAM = 3 }; /* 3: the streamed device reader below; reason = why it handed the rest of the input to the host reader (OK: it did not) */
 typedef struct { int reader, reason, format; uint64_t n_records, n_matched, n_dup, n_short; } mahip_useq_info_t;
 void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in);
 int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out);
+/* The reads file read on the device A PIECE AT A TIME (csrc/useq.hip): for input that cannot lie in HBM whole or cannot be opened twice -- gzip through
+ * zlib, stdin, a FIFO.  The caller feeds pieces of WHOLE LINES in input order; the device keeps one WINDOW = the carry (the trailing bytes of the window before
+ * that did not yet form a complete record; it never leaves the device) + the piece, consumes the complete records of the window and carries the rest:
+ *   FASTQ  with L newline-terminated lines in the window the records are lines 0 .. 4*floor(L/4) - 1 (kseq.h:222-230: header, ONE sequence line, '+', ONE quality
+ *          line of the sequence's length -- the form the check below verifies);
+ *   FASTA  everything in front of the window's last header line: the last record may go on in the next piece (kseq.h:209-213 reads sequence lines until the next
+ *          '>'), so it is always carried;
+ *   the last window is consumed whole; its final line may lack the '\n' (kseq.h:139-144); a FASTQ last window whose line count is no multiple of 4 is FASTQ_SHAPE.
+ * The format is fixed by the first byte of the INPUT (kseq.h:197-199 scans to the first '>' or '@'); every later window is checked in that format.  Every window
+ * gets a verdict over its complete records BEFORE it touches the arena -- the checks of the regular form above ('\r', NUL, FASTA line starts, FASTQ shape and
+ * quality length, LONG_LINE) and SHORT_READ (a matching record with fewer bases than its placement, asm.c:279-285).  A verdict other than OK ends the stream:
+ * windows 0 .. k-1 stay placed, window k places nothing, and the caller's host reader takes over from the first byte of window k, which is a record boundary where
+ * kseq's state is `last_char == 0` (FASTQ, kseq.h:229) or "just consumed the next header's '>'" (FASTA, kseq.h:214) -- a fresh reader that scans to the first
+ * '>' / '@' (kseq.h:197) continues identically.  A name the input carries more than once takes its LAST record (asm.c:262-284 overwrites): inside a window by the
+ * record number, across windows by stream order; n_matched counts distinct names, n_dup matching records beyond the first of a name, over the whole stream.
+ * Per window the cost follows the window, never the wanted list: the table over the wanted names is built once (begin), the probe appends the wanted reads that
+ * matched to a list and the placement runs one block per entry, which also clears the entry's slot of the per-wanted record array for the next window. */
+typedef struct {
+	int reason;                /* MAHIP_FASTX_*; anything but OK: nothing of this window was placed and the stream takes no more pieces */
+	uint64_t n_records;        /* complete records of the window */
+	uint64_t bytes_consumed;   /* bytes of the window in front of the carry (0 with a reason) */
+	uint64_t carry_bytes;      /* bytes kept for the next window */
+	uint64_t n_placed;         /* wanted reads this window placed (the length of its match list) */
+} mahip_useq_stream_verdict_t;
+typedef struct {
+	int format;                /* MAHIP_FASTX_FASTA / _FASTQ by the first byte of the input; 0: no byte yet, or neither */
+	uint64_t n_pieces;         /* pieces taken, empty ones and a refused one included */
+	uint64_t n_records, n_matched, n_dup, n_short; /* over the windows that were placed (n_short: of the refused window) */
+	uint64_t n_jobs;           /* sum of the match-list lengths = blocks of the placement launched */
+	uint64_t max_carry;        /* the largest carry, bytes */
+	uint32_t n_window_grow;    /* times the window buffer was replaced by a larger one (the first buffer replaces none) */
+	int refused_reason;        /* MAHIP_FASTX_* of the refused piece */
+	int64_t refused_piece;     /* -1: none */
+	double laps_ms[4];         /* wall time so far: upload (carry move included), line index + prefix + form, lookup, placement */
+} mahip_useq_stream_report_t;
+int mahip_useq_stream_begin(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes); /* between mahip_useq_begin and mahip_useq_end; asm.c:248-260 (where every read lands) as the wanted list */
+int mahip_useq_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, int last, mahip_useq_stream_verdict_t *v); /* asm.c:262-284 + kseq.h:192-232 on the window's records; whole lines, only the last piece may lack '\n'; nbytes may be 0 */
+int mahip_useq_stream_window_download(mahip_ctx_t *c, void *dst, uint64_t *nbytes); /* after a verdict != OK: the bytes of the refused window (carry + piece); dst == NULL: only the size */
+int mahip_useq_stream_end(mahip_ctx_t *c);   /* waits for the last placement; the arena is mahip_useq_end's */
+int mahip_useq_stream_abort(mahip_ctx_t *c); /* legal without a stream */
+int mahip_useq_stream_last(mahip_ctx_t *c, mahip_useq_stream_report_t *out); /* valid from begin until the next begin */
 /* ---- bgzip-compressed (BGZF) input inflated on the device (csrc/xfer.hip: k_bgzf_inflate, csrc/inflate_core.h; the member walk: host/ingest_gpu.c).
  * A BGZF file is a chain of gzip members of at most 64 KiB of text each, every one with its compressed size in a `BC` extra subfield and its inflated size in
  * its trailer: the host walks the chain once (one small read per member) into a table -- where each member's deflate bytes lie, its CRC and ISIZE, and where

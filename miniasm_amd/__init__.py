@@ -83,10 +83,20 @@ class UseqInfo(C.Structure):  # include/mahip.h: mahip_useq_info_t
                 ("n_short", C.c_uint64)]
 
 
+class UseqStreamVerdict(C.Structure):  # include/mahip.h: mahip_useq_stream_verdict_t
+    _fields_ = [("reason", C.c_int), ("n_records", C.c_uint64), ("bytes_consumed", C.c_uint64), ("carry_bytes", C.c_uint64), ("n_placed", C.c_uint64)]
+
+
+class UseqStreamReport(C.Structure):  # include/mahip.h: mahip_useq_stream_report_t
+    _fields_ = [("format", C.c_int), ("n_pieces", C.c_uint64), ("n_records", C.c_uint64), ("n_matched", C.c_uint64), ("n_dup", C.c_uint64), ("n_short", C.c_uint64),
+                ("n_jobs", C.c_uint64), ("max_carry", C.c_uint64), ("n_window_grow", C.c_uint32), ("refused_reason", C.c_int), ("refused_piece", C.c_int64),
+                ("laps_ms", C.c_double * 4)]
+
+
 # include/mahip.h: MAHIP_FASTX_* reasons, formats, MAHIP_USEQ_* readers
 FASTX_REASONS = ["OK", "CR", "FIRST_BYTE", "FASTA_LINE_START", "FASTQ_SHAPE", "FASTQ_QUAL_LEN", "TOO_MANY_LINES", "NOMEM", "SHORT_READ", "NOT_PLAIN", "FORCED", "NUL_BYTE", "LONG_LINE"]
 FASTX_FORMATS = {0: None, 1: "fasta", 2: "fastq"}
-USEQ_READERS = {0: None, 1: "host", 2: "device"}
+USEQ_READERS = {0: None, 1: "host", 2: "device", 3: "stream"}
 
 
 class BgzfInfo(C.Structure):  # include/mahip.h: mahip_bgzf_info_t
@@ -272,6 +282,12 @@ def lib():
         L.mahip_useq_end.argtypes = [vp, vp]
         L.mahip_useq_place_text.argtypes = [vp, vp, sz, vp, sz, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
         L.mahip_useq_last.argtypes = [vp, C.POINTER(UseqInfo)]
+        L.mahip_useq_stream_begin.argtypes = [vp, vp, sz, vp, sz]
+        L.mahip_useq_stream_piece_mem.argtypes = [vp, vp, sz, i32, C.POINTER(UseqStreamVerdict)]
+        L.mahip_useq_stream_window_download.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+        L.mahip_useq_stream_end.argtypes = [vp]
+        L.mahip_useq_stream_abort.argtypes = [vp]
+        L.mahip_useq_stream_last.argtypes = [vp, C.POINTER(UseqStreamReport)]
         L.mahip_bgzf_load_fd.argtypes = [vp, i32, sz, i32, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_load_mem.argtypes = [vp, vp, sz, i32, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_inflate_mem.argtypes = [vp, vp, sz, vp, sz, C.POINTER(BgzfInfo)]
@@ -540,6 +556,64 @@ class Ctx:
         out = C.create_string_buffer(max(arena_bytes, 1))
         _chk(L.mahip_useq_end(self.h, out), "useq_end")
         return out.raw[:arena_bytes], nm.value, nd.value, ns.value
+
+    # ---- the reads file a piece at a time (csrc/useq.hip): for stage tests
+    def useq_stream_last(self):
+        """dict of mahip_useq_stream_report_t, format and refused_reason as names"""
+        r = UseqStreamReport()
+        _chk(lib().mahip_useq_stream_last(self.h, C.byref(r)), "useq_stream_last")
+        return dict(format=FASTX_FORMATS[r.format], pieces=r.n_pieces, records=r.n_records, matched=r.n_matched, dup=r.n_dup, short=r.n_short, jobs=r.n_jobs, max_carry=r.max_carry,
+                    window_growths=r.n_window_grow, refused_piece=r.refused_piece, refused_reason=FASTX_REASONS[r.refused_reason], laps_ms=list(r.laps_ms))
+
+    def useq_stream_piece(self, text, last):
+        """one piece into the open stream -> verdict dict(reason, records, consumed, carry, placed); raises when the stream takes no piece"""
+        v = UseqStreamVerdict()
+        buf = C.create_string_buffer(bytes(text), len(text)) if len(text) else None
+        _chk(lib().mahip_useq_stream_piece_mem(self.h, buf, len(text), 1 if last else 0, C.byref(v)), "useq_stream_piece_mem")
+        return dict(reason=FASTX_REASONS[v.reason], records=v.n_records, consumed=v.bytes_consumed, carry=v.carry_bytes, placed=v.n_placed)
+
+    def useq_stream(self, pieces, arena_bytes, wanted, each=None):
+        """pieces (bytes objects of whole lines; only the last may end without a newline) through the streamed reader: useq_begin, stream_begin, a piece at a time
+        until the last piece or the first verdict other than OK, useq_end.  wanted: as useq_place_text.  each(k, verdict): called behind piece k.
+        Returns (arena bytes, or None when arena_bytes is 0; the verdicts; the report).  After a refusal the stream is left open, for useq_stream_window() and
+        useq_stream_abort(); otherwise it is ended."""
+        L = lib()
+        pieces = list(pieces)
+        arr = (UseqWant * max(len(wanted), 1))()
+        blob = b""
+        for k, w in enumerate(wanted):
+            arr[k] = UseqWant(w["dst_off"], len(blob), len(w["name"]), w["len"], w.get("s") or 0, w["e"] if w.get("e") is not None else 0, 1 if w["rev"] else 0, 1 if w.get("e") is None else 0)
+            blob += w["name"]
+        _chk(L.mahip_fastx_release(self.h), "fastx_release")  # (a window buffer of the size the pieces ask for: the growths are the stream's own)
+        _chk(L.mahip_useq_begin(self.h, arena_bytes), "useq_begin")
+        _chk(L.mahip_useq_stream_begin(self.h, C.addressof(arr), len(wanted), blob, len(blob)), "useq_stream_begin")
+        verdicts = []
+        try:
+            for k, p in enumerate(pieces):
+                verdicts.append(self.useq_stream_piece(p, k + 1 == len(pieces)))
+                if each is not None:
+                    each(k, verdicts[-1])
+                if verdicts[-1]["reason"] != "OK":
+                    break
+            else:
+                _chk(L.mahip_useq_stream_end(self.h), "useq_stream_end")
+        except Exception:
+            L.mahip_useq_stream_abort(self.h)
+            raise
+        out = C.create_string_buffer(max(arena_bytes, 1))
+        _chk(L.mahip_useq_end(self.h, out), "useq_end")
+        return (out.raw[:arena_bytes] if arena_bytes else None), verdicts, self.useq_stream_last()
+
+    def useq_stream_window(self):
+        """after a verdict other than OK: the bytes of the refused window (carry + piece)"""
+        n = C.c_uint64(0)
+        _chk(lib().mahip_useq_stream_window_download(self.h, None, C.byref(n)), "useq_stream_window_download")
+        buf = C.create_string_buffer(max(n.value, 1))
+        _chk(lib().mahip_useq_stream_window_download(self.h, buf, C.byref(n)), "useq_stream_window_download")
+        return buf.raw[:n.value]
+
+    def useq_stream_abort(self):
+        _chk(lib().mahip_useq_stream_abort(self.h), "useq_stream_abort")
 
     def useq_last(self):
         """which reader the context's last ma_ug_seq used, and why"""

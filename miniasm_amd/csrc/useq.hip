@@ -13,6 +13,10 @@ struct UseqBufs {
 	DevBuf fx_text, fx_gcnt, fx_gpos, fx_ls, fx_hdr, fx_hpos, fx_recl, fx_ctr, fx_want, fx_wname, fx_whash, fx_tab, fx_win;
 	size_t fx_n = 0; uint32_t fx_L = 0, fx_R = 0; int fx_format = 0; bool fx_loaded = false, fx_regular = false;
 	mahip_useq_info_t last = {0, 0, 0, 0, 0, 0, 0};
+	// the streamed reader: the window lives in fx_text; counters of a window, its match list, the names seen so far
+	DevBuf fw_ctr, fw_list, fw_seen;
+	bool fw_active = false, fw_ended = false; size_t fw_n_want = 0, fw_n = 0, fw_carry_off = 0, fw_carry = 0, fw_cap = 0; uint32_t fw_mask = 0; double fw_t_place = 0;
+	mahip_useq_stream_report_t fw_rep = {};
 };
 static void fx_drop(mahip_ctx *c, UseqBufs *b);
 
@@ -156,8 +160,8 @@ __global__ __launch_bounds__(256) void k_fx_lines(const unsigned char *__restric
 
 __device__ __forceinline__ uint32_t fx_first(const FxText &x, uint32_t i) { const uint64_t b = x.ls[i]; return x.ls[i + 1] - 1 > b ? x.t[b] : 0u; } // 0: an empty line
 
-// FASTA: header flags, the lines that may not be there, and lines of FX_LONG_LINE bytes or more in a record of several lines
-__global__ __launch_bounds__(256) void k_fx_form_fasta(const FxText x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr)
+// FASTA: header flags, the lines that may not be there, and lines of FX_LONG_LINE bytes or more in a record of several lines (the whole block calls it)
+__device__ __forceinline__ void fx_form_fasta_lines(const FxText &x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr)
 {
 	uint64_t bad = 0, lng = 0;
 	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < x.L; i += (uint64_t)gridDim.x * 256u) {
@@ -170,14 +174,15 @@ __global__ __launch_bounds__(256) void k_fx_form_fasta(const FxText x, uint32_t 
 	blk_add_u64(ctr + FX_V_FASTA, bad);
 	blk_add_u64(ctr + FX_V_LONG, lng);
 }
+__global__ __launch_bounds__(256) void k_fx_form_fasta(const FxText x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr) { fx_form_fasta_lines(x, hdr, ctr); }
 // recl[r] = header line of record r, recl[R] = L
 __global__ __launch_bounds__(256) void k_fx_rec_lines(const uint32_t *__restrict__ hdr, const uint32_t *__restrict__ hpos, uint32_t L, uint32_t *__restrict__ recl)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < L; i += (uint64_t)gridDim.x * 256u) if (hdr[i]) recl[hpos[i]] = (uint32_t)i;
 	if (blockIdx.x == 0 && threadIdx.x == 0) recl[hpos[L]] = L;
 }
-// FASTQ: record r = lines 4r .. 4r + 3 (L is a multiple of 4)
-__global__ __launch_bounds__(256) void k_fx_form_fastq(const FxText x, unsigned long long *__restrict__ ctr)
+// FASTQ: record r = lines 4r .. 4r + 3 (the whole block calls it)
+__device__ __forceinline__ void fx_form_fastq_records(const FxText &x, unsigned long long *__restrict__ ctr)
 {
 	uint64_t shape = 0, qual = 0;
 	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < x.R; r += (uint64_t)gridDim.x * 256u) {
@@ -188,6 +193,7 @@ __global__ __launch_bounds__(256) void k_fx_form_fastq(const FxText x, unsigned 
 	blk_add_u64(ctr + FX_V_SHAPE, shape);
 	blk_add_u64(ctr + FX_V_QUAL, qual);
 }
+__global__ __launch_bounds__(256) void k_fx_form_fastq(const FxText x, unsigned long long *__restrict__ ctr) { fx_form_fastq_records(x, ctr); } // (L is a multiple of 4)
 
 // record r: its header line, its sequence lines [*j0, *j1) and the bases they hold (every line of the stretch ends with one byte that is not a base)
 __device__ __forceinline__ uint32_t fx_record(const FxText &x, uint32_t r, uint32_t *j0, uint32_t *j1, uint64_t *nb)
@@ -231,91 +237,218 @@ __global__ __launch_bounds__(256) void k_fx_tab_build(const mahip_useq_want_t *_
 		while (atomicCAS(&tab[s], 0u, w + 1u) != 0u) s = (s + 1u) & mask;
 	}
 }
+// record r's name against the table: the wanted read that carries it + 1 (0: none), and the bases the record holds
+__device__ __forceinline__ uint32_t fx_lookup(const FxText &x, uint32_t r, const mahip_useq_want_t *__restrict__ want, const unsigned char *__restrict__ wname, const uint64_t *__restrict__ whash,
+                                              const uint32_t *__restrict__ tab, uint32_t mask, uint64_t *nb)
+{
+	uint32_t j0, j1; uint64_t off;
+	const uint32_t l = fx_name(x, fx_record(x, r, &j0, &j1, nb), &off);
+	if (l == 0) return 0; // an empty name matches nothing
+	const unsigned char *s = x.t + off;
+	const uint64_t h = fx_hash(s, l);
+	for (uint32_t p = (uint32_t)h & mask;; p = (p + 1u) & mask) {
+		const uint32_t e = tab[p];
+		if (e == 0) return 0;
+		if (whash[e - 1] != h || want[e - 1].name_len != l) continue;
+		const unsigned char *q = wname + want[e - 1].name_off;
+		uint32_t k = 0;
+		while (k < l && q[k] == s[k]) ++k;
+		if (k == l) return e;
+	}
+}
 // every record's name against the table; a wanted read keeps the LAST record that carries its name (the reference's loop overwrites, asm.c:262-284)
 __global__ __launch_bounds__(256) void k_fx_probe(const FxText x, const mahip_useq_want_t *__restrict__ want, const unsigned char *__restrict__ wname, const uint64_t *__restrict__ whash,
                                                   const uint32_t *__restrict__ tab, uint32_t mask, uint32_t *__restrict__ win, unsigned long long *__restrict__ ctr)
 {
 	uint64_t n_match = 0, n_distinct = 0, n_short = 0;
 	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < x.R; r += (uint64_t)gridDim.x * 256u) {
-		uint32_t j0, j1; uint64_t nb, off;
-		const uint32_t l = fx_name(x, fx_record(x, (uint32_t)r, &j0, &j1, &nb), &off);
-		if (l == 0) continue; // an empty name matches nothing
-		const unsigned char *s = x.t + off;
-		const uint64_t h = fx_hash(s, l);
-		for (uint32_t p = (uint32_t)h & mask;; p = (p + 1u) & mask) {
-			const uint32_t e = tab[p];
-			if (e == 0) break;
-			const mahip_useq_want_t wt = want[e - 1];
-			if (whash[e - 1] != h || wt.name_len != l) continue;
-			const unsigned char *q = wname + wt.name_off;
-			uint32_t k = 0;
-			while (k < l && q[k] == s[k]) ++k;
-			if (k < l) continue;
-			++n_match;
-			n_distinct += atomicMax(&win[e - 1], (uint32_t)r + 1u) == 0u;
-			n_short += nb < (uint64_t)(wt.whole ? wt.len : wt.e);
-			break;
-		}
+		uint64_t nb;
+		const uint32_t e = fx_lookup(x, (uint32_t)r, want, wname, whash, tab, mask, &nb);
+		if (e == 0) continue;
+		++n_match;
+		n_distinct += atomicMax(&win[e - 1], (uint32_t)r + 1u) == 0u;
+		n_short += nb < (uint64_t)(want[e - 1].whole ? want[e - 1].len : want[e - 1].e);
 	}
 	blk_add_u64(ctr + FX_MATCH, n_match);
 	blk_add_u64(ctr + FX_DISTINCT, n_distinct);
 	blk_add_u64(ctr + FX_SHORT, n_short);
 }
 
-// one block per wanted read: its bases from the text into the arena, forward or reverse complement as k_useq_gather does it.  A sequence on one line
-// (FASTQ, unwrapped FASTA) is a straight coalesced copy; a wrapped one goes through 256 lines at a time: their lengths are scanned into base offsets in
-// LDS and every base finds its line by a binary search there (8 steps), so consecutive lanes still read consecutive bytes except at the line ends.
+// the per-read body of the placement (the whole block calls it): the bases of record `rec` from the text into the arena, forward or reverse complement as
+// k_useq_gather does it.  A sequence on one line (FASTQ, unwrapped FASTA) is a straight coalesced copy; a wrapped one goes through 256 lines at a time: their
+// lengths are scanned into base offsets in LDS and every base finds its line by a binary search there (8 steps), so consecutive lanes still read consecutive
+// bytes except at the line ends.
+struct FxPlaceLds { unsigned char comp[128]; uint64_t start[256]; uint32_t off[256], wave[4]; };
+__device__ __forceinline__ void fx_place_read(const FxText &x, const mahip_useq_want_t &wt, uint32_t rec, unsigned char *__restrict__ arena, FxPlaceLds &m)
+{
+	uint32_t j0, j1; uint64_t nb;
+	fx_record(x, rec, &j0, &j1, &nb);
+	const uint64_t s = wt.whole ? 0 : wt.s, e = wt.whole ? nb : wt.e; // the kept interval [s, e) of the read's bases (the caller made sure that nb >= e)
+	const uint64_t len = wt.len < e - s ? wt.len : e - s;
+	const uint64_t lo = wt.rev ? e - len : s, hi = lo + len;          // the bases that are placed
+	unsigned char *dst = arena + wt.dst_off;
+	if (j1 - j0 == 1) {
+		const unsigned char *src = x.t + x.ls[j0];
+		if (!wt.rev) for (uint64_t i = threadIdx.x; i < len; i += 256) dst[i] = src[s + i];
+		else for (uint64_t i = threadIdx.x; i < len; i += 256) { const unsigned ch = src[e - 1 - i]; dst[i] = ch >= 128 ? 'N' : m.comp[ch]; } // asm.c:280-281
+		return;
+	}
+	uint64_t run = 0; // bases in front of the chunk
+	for (uint32_t cj = j0; cj < j1 && run < hi; cj += 256) {
+		const uint32_t cnt = j1 - cj < 256u ? j1 - cj : 256u, j = cj + threadIdx.x;
+		uint32_t tot;
+		const uint32_t ll = threadIdx.x < cnt ? (uint32_t)(x.ls[j + 1] - x.ls[j] - 1) : 0u;
+		const uint32_t ex = block_excl_scan_256(ll, m.wave, &tot);
+		if (threadIdx.x < cnt) { m.start[threadIdx.x] = x.ls[j]; m.off[threadIdx.x] = ex; }
+		__syncthreads();
+		const uint64_t b0 = lo > run ? lo : run, b1 = hi < run + tot ? hi : run + tot;
+		for (uint64_t b = b0 + threadIdx.x; b < b1; b += 256) {
+			const uint32_t rel = (uint32_t)(b - run);
+			uint32_t ka = 0, kb = cnt; // the last line of the chunk that starts at or in front of the base
+			while (kb - ka > 1) { const uint32_t mid = (ka + kb) >> 1; if (m.off[mid] <= rel) ka = mid; else kb = mid; }
+			const unsigned ch = x.t[m.start[ka] + (rel - m.off[ka])];
+			if (!wt.rev) dst[b - s] = (unsigned char)ch;
+			else dst[e - 1 - b] = ch >= 128 ? 'N' : m.comp[ch];
+		}
+		run += tot;
+		__syncthreads();
+	}
+}
+// one block per wanted read (the whole-file reader: once per file)
 __global__ __launch_bounds__(256) void k_fx_place(const FxText x, const mahip_useq_want_t *__restrict__ want, uint32_t n_want, const uint32_t *__restrict__ win, unsigned char *__restrict__ arena)
 {
-	__shared__ unsigned char s_comp[128];
-	__shared__ uint64_t s_start[256];
-	__shared__ uint32_t s_off[256], s_wave[4];
-	if (threadIdx.x < 128) s_comp[threadIdx.x] = comp_of(threadIdx.x);
+	__shared__ FxPlaceLds m;
+	if (threadIdx.x < 128) m.comp[threadIdx.x] = comp_of(threadIdx.x);
 	__syncthreads();
 	for (uint32_t w = blockIdx.x; w < n_want; w += gridDim.x) { // the whole block
 		const uint32_t rec = win[w];
 		if (rec == 0) continue; // not in the file: its positions stay 'N'
-		const mahip_useq_want_t wt = want[w];
-		uint32_t j0, j1; uint64_t nb;
-		fx_record(x, rec - 1, &j0, &j1, &nb);
-		const uint64_t s = wt.whole ? 0 : wt.s, e = wt.whole ? nb : wt.e; // the kept interval [s, e) of the read's bases (the caller made sure that nb >= e)
-		const uint64_t len = wt.len < e - s ? wt.len : e - s;
-		const uint64_t lo = wt.rev ? e - len : s, hi = lo + len;          // the bases that are placed
-		unsigned char *dst = arena + wt.dst_off;
-		if (j1 - j0 == 1) {
-			const unsigned char *src = x.t + x.ls[j0];
-			if (!wt.rev) for (uint64_t i = threadIdx.x; i < len; i += 256) dst[i] = src[s + i];
-			else for (uint64_t i = threadIdx.x; i < len; i += 256) { const unsigned ch = src[e - 1 - i]; dst[i] = ch >= 128 ? 'N' : s_comp[ch]; } // asm.c:280-281
-			continue;
+		fx_place_read(x, want[w], rec - 1, arena, m);
+	}
+}
+
+// ------------------------------------------------------------------------------------------------ the same text a window at a time
+// The streamed reader holds one WINDOW of the text: the carry (the bytes of the window before that did not yet form a complete record) and the next piece.  The
+// census and the line index above run on the window as they are; the kernels below find the consumed prefix (FASTQ: lines 0 .. 4*floor(L/4) - 1; FASTA: the lines
+// in front of the window's last header line; everything in the last window), number its records only and leave the carry in the counter block.  Everything that
+// follows reads L and R of the PREFIX from that block, so the host reads counters twice a window (the line count, then everything else) and no launch is sized
+// by, or sweeps, the wanted list: the probe appends the wanted reads that matched to a list, and the placement runs one block per entry of it.
+enum { FXW_LASTHDR = 16, FXW_LC, FXW_R, FXW_CONSUMED, FXW_CARRY, FXW_NLIST, FXW_CR, FXW_NUL, FXW_NCTR = 32 };
+
+__device__ __forceinline__ FxText fxw_prefix_view(FxText x, const unsigned long long *__restrict__ ctr) { x.L = (uint32_t)ctr[FXW_LC]; x.R = (uint32_t)ctr[FXW_R]; return x; }
+
+// FASTA: header flags of every line of the window, and its last header line (+ 1)
+__global__ __launch_bounds__(256) void k_fxw_hdr(const FxText x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr)
+{
+	uint64_t last = 0;
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < x.L; i += (uint64_t)gridDim.x * 256u) {
+		const uint32_t h = fx_first(x, (uint32_t)i) == '>';
+		hdr[i] = h;
+		if (h) last = i + 1;
+	}
+	blk_max_u64(ctr + FXW_LASTHDR, last);
+}
+// the consumed prefix: its lines, its records, its bytes, and what stays behind it (one thread; x.L = the lines of the window; hpos: FASTA only)
+__global__ void k_fxw_prefix(const FxText x, const uint32_t *__restrict__ hpos, int last, unsigned long long *__restrict__ ctr)
+{
+	if (blockIdx.x || threadIdx.x) return;
+	uint32_t Lc, R;
+	if (x.fq) { Lc = last ? x.L : x.L & ~3u; R = x.L / 4u; }
+	else { const uint32_t lh = (uint32_t)ctr[FXW_LASTHDR]; Lc = last ? x.L : lh ? lh - 1u : 0u; R = hpos[Lc]; }
+	const uint64_t used = x.ls[Lc] < x.n ? x.ls[Lc] : x.n; // (ls[L] = n + 1 behind a last line without its newline)
+	ctr[FXW_LC] = Lc; ctr[FXW_R] = R; ctr[FXW_CONSUMED] = used; ctr[FXW_CARRY] = x.n - used;
+}
+// recl[r] = header line of record r of the prefix, recl[R] = its line count
+__global__ __launch_bounds__(256) void k_fxw_rec_lines(const uint32_t *__restrict__ hdr, const uint32_t *__restrict__ hpos, const unsigned long long *__restrict__ ctr, uint32_t *__restrict__ recl)
+{
+	const uint32_t Lc = (uint32_t)ctr[FXW_LC];
+	for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < Lc; i += (uint64_t)gridDim.x * 256u) if (hdr[i]) recl[hpos[i]] = (uint32_t)i;
+	if (blockIdx.x == 0 && threadIdx.x == 0) recl[ctr[FXW_R]] = Lc;
+}
+// '\r' and NUL bytes of the prefix (one wave per granule, as the census)
+__global__ __launch_bounds__(256) void k_fxw_bytes(const unsigned char *__restrict__ t, unsigned long long *__restrict__ ctr)
+{
+	const uint64_t n = ctr[FXW_CONSUMED];
+	const uint32_t lane = threadIdx.x & 63, n_waves = gridDim.x * 4u, n_gran = (uint32_t)((n + FX_GRAN - 1) / FX_GRAN);
+	uint64_t cr = 0, nul = 0;
+	for (uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6); g < n_gran; g += n_waves) {
+		const uint4 v = fx_load16(t, n, (uint64_t)g * FX_GRAN + lane * 16u);
+		cr += (uint32_t)(__popc(fx_eq(v.x, 0x0d0d0d0du)) + __popc(fx_eq(v.y, 0x0d0d0d0du)) + __popc(fx_eq(v.z, 0x0d0d0d0du)) + __popc(fx_eq(v.w, 0x0d0d0d0du)));
+		nul += (uint32_t)(__popc(fx_eq(v.x, 0u)) + __popc(fx_eq(v.y, 0u)) + __popc(fx_eq(v.z, 0u)) + __popc(fx_eq(v.w, 0u)));
+	}
+	blk_add_u64(ctr + FXW_CR, cr);
+	blk_add_u64(ctr + FXW_NUL, nul);
+}
+__global__ __launch_bounds__(256) void k_fxw_form_fasta(const FxText x, uint32_t *__restrict__ hdr, unsigned long long *__restrict__ ctr) { fx_form_fasta_lines(fxw_prefix_view(x, ctr), hdr, ctr); }
+__global__ __launch_bounds__(256) void k_fxw_form_fastq(const FxText x, unsigned long long *__restrict__ ctr) { fx_form_fastq_records(fxw_prefix_view(x, ctr), ctr); }
+
+// the probe of a window: as k_fx_probe, and the lane whose atomicMax found win[w] == 0 -- the first record of the window that carries the name -- appends w to the
+// window's match list, one atomic per wave (ballot, popcount, one add by the first lane that has one, broadcast).  `seen` lives for the whole stream: a name
+// counts as distinct only in the first window that holds it.  The loop is uniform for the wave: every lane is at the ballot.
+__global__ __launch_bounds__(256) void k_fxw_probe(const FxText xw, const mahip_useq_want_t *__restrict__ want, const unsigned char *__restrict__ wname, const uint64_t *__restrict__ whash,
+                                                   const uint32_t *__restrict__ tab, uint32_t mask, uint32_t *__restrict__ win, const unsigned char *__restrict__ seen, uint32_t *__restrict__ list,
+                                                   unsigned long long *__restrict__ ctr)
+{
+	const FxText x = fxw_prefix_view(xw, ctr);
+	const unsigned lane = threadIdx.x & 63;
+	uint64_t n_match = 0, n_distinct = 0, n_short = 0;
+	for (uint64_t r0 = (uint64_t)blockIdx.x * 256u; r0 < x.R; r0 += (uint64_t)gridDim.x * 256u) {
+		const uint64_t r = r0 + threadIdx.x;
+		uint64_t nb = 0;
+		const uint32_t e = r < x.R ? fx_lookup(x, (uint32_t)r, want, wname, whash, tab, mask, &nb) : 0u;
+		int first = 0;
+		if (e) {
+			++n_match;
+			first = atomicMax(&win[e - 1], (uint32_t)r + 1u) == 0u;
+			n_distinct += first && !seen[e - 1];
+			n_short += nb < (uint64_t)(want[e - 1].whole ? want[e - 1].len : want[e - 1].e);
 		}
-		uint64_t run = 0; // bases in front of the chunk
-		for (uint32_t cj = j0; cj < j1 && run < hi; cj += 256) {
-			const uint32_t cnt = j1 - cj < 256u ? j1 - cj : 256u, j = cj + threadIdx.x;
-			uint32_t tot;
-			const uint32_t ll = threadIdx.x < cnt ? (uint32_t)(x.ls[j + 1] - x.ls[j] - 1) : 0u;
-			const uint32_t ex = block_excl_scan_256(ll, s_wave, &tot);
-			if (threadIdx.x < cnt) { s_start[threadIdx.x] = x.ls[j]; s_off[threadIdx.x] = ex; }
-			__syncthreads();
-			const uint64_t b0 = lo > run ? lo : run, b1 = hi < run + tot ? hi : run + tot;
-			for (uint64_t b = b0 + threadIdx.x; b < b1; b += 256) {
-				const uint32_t rel = (uint32_t)(b - run);
-				uint32_t ka = 0, kb = cnt; // the last line of the chunk that starts at or in front of the base
-				while (kb - ka > 1) { const uint32_t mid = (ka + kb) >> 1; if (s_off[mid] <= rel) ka = mid; else kb = mid; }
-				const unsigned ch = x.t[s_start[ka] + (rel - s_off[ka])];
-				if (!wt.rev) dst[b - s] = (unsigned char)ch;
-				else dst[e - 1 - b] = ch >= 128 ? 'N' : s_comp[ch];
-			}
-			run += tot;
-			__syncthreads();
+		const uint64_t m = wv_ballot(first);
+		if (m) {
+			const int lead = __ffsll((long long)m) - 1;
+			uint32_t base = 0;
+			if (lane == (unsigned)lead) base = (uint32_t)atomicAdd(ctr + FXW_NLIST, (unsigned long long)__popcll(m));
+			base = wv_bcast(base, lead);
+			if (first) list[base + (uint32_t)__popcll(m & wv_lt(lane))] = e - 1;
 		}
+	}
+	blk_add_u64(ctr + FX_MATCH, n_match);
+	blk_add_u64(ctr + FX_DISTINCT, n_distinct);
+	blk_add_u64(ctr + FX_SHORT, n_short);
+}
+// one block per entry of the match list: the copy of k_fx_place; then win[w] goes back to 0 -- win[] is all zero between windows without a sweep -- and the name is seen
+__global__ __launch_bounds__(256) void k_fxw_place(const FxText x, const mahip_useq_want_t *__restrict__ want, const uint32_t *__restrict__ list, uint32_t n_list, uint32_t *__restrict__ win,
+                                                   unsigned char *__restrict__ seen, unsigned char *__restrict__ arena)
+{
+	__shared__ FxPlaceLds m;
+	if (threadIdx.x < 128) m.comp[threadIdx.x] = comp_of(threadIdx.x);
+	__syncthreads();
+	for (uint32_t k = blockIdx.x; k < n_list; k += gridDim.x) { // the whole block
+		const uint32_t w = list[k], rec = win[w];
+		fx_place_read(x, want[w], rec - 1, arena, m);
+		__syncthreads(); // every thread has read win[w]
+		if (threadIdx.x == 0) { win[w] = 0; seen[w] = 1; }
+	}
+}
+// the carry to the front of the window when the two stretches overlap: one block, ascending tiles of 4 KiB, every tile read whole before it is written (the
+// destination lies in front of the source, so a tile's stores reach no byte that is still to be read)
+__global__ __launch_bounds__(256) void k_fxw_move(unsigned char *__restrict__ t, uint64_t src, uint64_t n)
+{
+	for (uint64_t b = 0; b < n; b += 4096) {
+		unsigned char v[16];
+		const uint64_t at = b + threadIdx.x * 16u;
+		for (uint32_t k = 0; k < 16; ++k) if (at + k < n) v[k] = t[src + at + k];
+		__syncthreads();
+		for (uint32_t k = 0; k < 16; ++k) if (at + k < n) t[at + k] = v[k];
+		__syncthreads();
 	}
 }
 
 static void fx_drop(mahip_ctx *c, UseqBufs *b)
 {
-	DevBuf *all[] = {&b->fx_text, &b->fx_gcnt, &b->fx_gpos, &b->fx_ls, &b->fx_hdr, &b->fx_hpos, &b->fx_recl, &b->fx_ctr, &b->fx_want, &b->fx_wname, &b->fx_whash, &b->fx_tab, &b->fx_win};
+	DevBuf *all[] = {&b->fx_text, &b->fx_gcnt, &b->fx_gpos, &b->fx_ls, &b->fx_hdr, &b->fx_hpos, &b->fx_recl, &b->fx_ctr, &b->fx_want, &b->fx_wname, &b->fx_whash, &b->fx_tab, &b->fx_win, &b->fw_ctr, &b->fw_list, &b->fw_seen};
 	for (DevBuf *d : all) dev_free(c, *d);
-	b->fx_n = 0; b->fx_loaded = b->fx_regular = false;
+	b->fx_n = 0; b->fx_loaded = b->fx_regular = false; b->fw_active = false;
 }
 
 static int fx_reserve_text(mahip_ctx *c, size_t nbytes)
@@ -473,6 +606,31 @@ extern "C" int mahip_fastx_name_spans(mahip_ctx_t *c, uint64_t *off, uint32_t *l
 
 static double fx_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; }
 
+// the wanted reads, their names and the table over them on the device (once per file, once per stream); win[] starts all zero.  *cap = slots of the table
+static int fx_want_upload(mahip_ctx *c, UseqBufs *b, const char *who, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes, uint32_t *cap_out)
+{
+	if (n_wanted >= 0x40000000ull) { mahip_set_error("%s: too many wanted reads", who); return -1; }
+	for (size_t w = 0; w < n_wanted; ++w) // the kernels trust these
+		if (wanted[w].name_off + wanted[w].name_len > name_bytes || wanted[w].dst_off + wanted[w].len > b->arena_bytes || (!wanted[w].whole && wanted[w].s > wanted[w].e)) {
+			mahip_set_error("%s: wanted read %zu reaches outside the names or the arena", who, w); return -1;
+		}
+	uint32_t cap = 64; while (cap < 2 * n_wanted) cap <<= 1;
+	CHK(dev_reserve(c, b->fx_want, (n_wanted ? n_wanted : 1) * sizeof(mahip_useq_want_t))); CHK(dev_reserve(c, b->fx_wname, name_bytes + 64)); CHK(dev_reserve(c, b->fx_whash, (n_wanted ? n_wanted : 1) * 8));
+	CHK(dev_reserve(c, b->fx_tab, (size_t)cap * 4)); CHK(dev_reserve(c, b->fx_win, (n_wanted ? n_wanted : 1) * 4));
+	if (n_wanted) HIPCHK(hipMemcpyAsync(b->fx_want.p, wanted, n_wanted * sizeof(mahip_useq_want_t), hipMemcpyHostToDevice, c->st));
+	if (name_bytes) HIPCHK(hipMemcpyAsync(b->fx_wname.p, names, name_bytes, hipMemcpyHostToDevice, c->st));
+	HIPCHK(hipMemsetAsync(b->fx_tab.p, 0, (size_t)cap * 4, c->st));
+	if (n_wanted) HIPCHK(hipMemsetAsync(b->fx_win.p, 0, n_wanted * 4, c->st));
+	if (n_wanted) {
+		ProfScope ps(c, "k_fx_tab_build", 0);
+		hipLaunchKernelGGL(k_fx_tab_build, dim3(grid_for(n_wanted, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (uint32_t)n_wanted,
+		                   P<uint64_t>(b->fx_whash), P<uint32_t>(b->fx_tab), cap - 1);
+		HIPCHK(hipGetLastError());
+	}
+	*cap_out = cap;
+	return 0;
+}
+
 extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes,
                                      uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms)
 {
@@ -483,26 +641,11 @@ extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wa
 	*n_matched = *n_dup = *n_short = 0;
 	if (laps_ms) laps_ms[0] = laps_ms[1] = 0;
 	if (n_wanted == 0 || b->fx_R == 0) return 0;
-	for (size_t w = 0; w < n_wanted; ++w) // the kernels trust these
-		if (wanted[w].name_off + wanted[w].name_len > name_bytes || wanted[w].dst_off + wanted[w].len > b->arena_bytes || (!wanted[w].whole && wanted[w].s > wanted[w].e)) {
-			mahip_set_error("mahip_useq_place_text: wanted read %zu reaches outside the names or the arena", w); return -1;
-		}
 	const double t0 = fx_now();
-	uint32_t cap = 64; while (cap < 2 * n_wanted) cap <<= 1;
-	CHK(dev_reserve(c, b->fx_want, n_wanted * sizeof(mahip_useq_want_t))); CHK(dev_reserve(c, b->fx_wname, name_bytes + 64)); CHK(dev_reserve(c, b->fx_whash, n_wanted * 8));
-	CHK(dev_reserve(c, b->fx_tab, (size_t)cap * 4)); CHK(dev_reserve(c, b->fx_win, n_wanted * 4));
-	HIPCHK(hipMemcpyAsync(b->fx_want.p, wanted, n_wanted * sizeof(mahip_useq_want_t), hipMemcpyHostToDevice, c->st));
-	HIPCHK(hipMemcpyAsync(b->fx_wname.p, names, name_bytes, hipMemcpyHostToDevice, c->st));
-	HIPCHK(hipMemsetAsync(b->fx_tab.p, 0, (size_t)cap * 4, c->st));
-	HIPCHK(hipMemsetAsync(b->fx_win.p, 0, n_wanted * 4, c->st));
+	uint32_t cap = 0;
+	CHK(fx_want_upload(c, b, "mahip_useq_place_text", wanted, n_wanted, names, name_bytes, &cap));
 	HIPCHK(hipMemsetAsync(b->fx_ctr.p, 0, FX_NCTR * 8, c->st));
 	const FxText x = fx_view(b);
-	{
-		ProfScope ps(c, "k_fx_tab_build", 0);
-		hipLaunchKernelGGL(k_fx_tab_build, dim3(grid_for(n_wanted, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (uint32_t)n_wanted,
-		                   P<uint64_t>(b->fx_whash), P<uint32_t>(b->fx_tab), cap - 1);
-		HIPCHK(hipGetLastError());
-	}
 	{
 		ProfScope ps(c, "k_fx_probe", 0);
 		hipLaunchKernelGGL(k_fx_probe, dim3(grid_for(b->fx_R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (const uint64_t*)b->fx_whash.p,
@@ -523,6 +666,195 @@ extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wa
 	if (laps_ms) { HIPCHK(hipStreamSynchronize(c->st)); laps_ms[1] = (fx_now() - t1) * 1e3; }
 	return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ the streamed reader (include/mahip.h)
+extern "C" int mahip_useq_stream_begin(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	b->fx_loaded = b->fx_regular = false; // the window takes the text buffer
+	b->fw_active = false;
+	uint32_t cap = 0;
+	CHK(fx_want_upload(c, b, "mahip_useq_stream_begin", wanted, n_wanted, names, name_bytes, &cap));
+	CHK(dev_reserve(c, b->fw_ctr, FXW_NCTR * 8)); CHK(dev_reserve(c, b->fw_seen, n_wanted ? n_wanted : 1));
+	HIPCHK(hipMemsetAsync(b->fw_seen.p, 0, n_wanted ? n_wanted : 1, c->st));
+	HIPCHK(hipStreamSynchronize(c->st)); // the caller may reuse wanted / names
+	b->fw_mask = cap - 1; b->fw_n_want = n_wanted; b->fw_n = b->fw_carry_off = b->fw_carry = b->fw_cap = 0; b->fw_t_place = 0; // (the first piece brings the window's first buffer)
+	memset(&b->fw_rep, 0, sizeof(b->fw_rep));
+	b->fw_rep.refused_piece = -1;
+	b->fw_active = true; b->fw_ended = false;
+	return 0;
+}
+
+static int fxw_counters(mahip_ctx *c, UseqBufs *b, unsigned long long *h)
+{
+	HIPCHK(hipMemcpyAsync(h, b->fw_ctr.p, FXW_NCTR * 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+// what is still running of the window before (its placement) ends here: the lap belongs to `place`
+static int fxw_drain(mahip_ctx *c, UseqBufs *b)
+{
+	const double t0 = fx_now();
+	HIPCHK(hipStreamSynchronize(c->st));
+	b->fw_t_place += fx_now() - t0;
+	b->fw_rep.laps_ms[3] = b->fw_t_place * 1e3;
+	return 0;
+}
+
+#define FXW_RESERVE(buf, bytes) do { if (dev_reserve(c, (buf), (bytes)) != 0) { reason = MAHIP_FASTX_NOMEM; goto refuse; } } while (0)
+extern "C" int mahip_useq_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, int last, mahip_useq_stream_verdict_t *v)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	mahip_useq_stream_report_t *rep = &b->fw_rep;
+	memset(v, 0, sizeof(*v));
+	if (!b->fw_active) { mahip_set_error("mahip_useq_stream_piece_mem: no stream (mahip_useq_stream_begin)"); return -1; }
+	if (rep->refused_piece >= 0) { mahip_set_error("mahip_useq_stream_piece_mem: piece %lld was refused, the stream takes no more", (long long)rep->refused_piece); return -1; }
+	if (b->fw_ended) { mahip_set_error("mahip_useq_stream_piece_mem: a piece behind the last one"); return -1; }
+	if (!last && nbytes && ((const char*)text)[nbytes - 1] != '\n') { mahip_set_error("mahip_useq_stream_piece_mem: a piece that is not the last ends inside a line"); return -1; }
+	const int64_t piece_no = (int64_t)rep->n_pieces++;
+	if (last) b->fw_ended = true;
+	double t0 = fx_now(), t1;
+	int reason = MAHIP_FASTX_OK;
+	unsigned long long h[FXW_NCTR];
+	memset(h, 0, sizeof(h));
+	// ---- the window: the carry to the front, the piece behind it
+	CHK(fxw_drain(c, b)); // the placement of the window before reads the text
+	t0 = fx_now();
+	const size_t carry = b->fw_carry, n = carry + nbytes;
+	if (n + 64 > b->fw_cap) { // a record longer than the window: a larger one, by half as much again as is needed now (fw_cap: what was asked for -- the pool may have given more)
+		DevBuf nw;
+		CHK(dev_reserve(c, nw, n + n / 2 + 64)); // (no room for ONE record and a piece: an error, not a verdict -- the window could not be handed back whole)
+		if (carry) HIPCHK(hipMemcpyAsync(nw.p, (const char*)b->fx_text.p + b->fw_carry_off, carry, hipMemcpyDeviceToDevice, c->st));
+		HIPCHK(hipStreamSynchronize(c->st));
+		if (b->fw_cap) ++rep->n_window_grow;
+		dev_free(c, b->fx_text);
+		b->fx_text = nw; b->fw_cap = n + n / 2 + 64;
+	} else if (carry && b->fw_carry_off) {
+		if (carry <= b->fw_carry_off) HIPCHK(hipMemcpyAsync(b->fx_text.p, (const char*)b->fx_text.p + b->fw_carry_off, carry, hipMemcpyDeviceToDevice, c->st));
+		else {
+			hipLaunchKernelGGL(k_fxw_move, dim3(1), dim3(256), 0, c->st, (unsigned char*)b->fx_text.p, (uint64_t)b->fw_carry_off, (uint64_t)carry);
+			HIPCHK(hipGetLastError());
+		}
+	}
+	b->fw_carry_off = 0; b->fw_n = n;
+	if (nbytes) CHK(xfer_copy(c, (char*)b->fx_text.p + carry, (void*)text, nbytes, 1));
+	else HIPCHK(hipStreamSynchronize(c->st));
+	rep->laps_ms[0] += ((t1 = fx_now()) - t0) * 1e3; t0 = t1;
+	if (n == 0) return 0; // nothing yet, or nothing at all
+	if (rep->format == 0) { // the first byte of the INPUT fixes the format of every window (window 0 holds no carry)
+		const unsigned char c0 = *(const unsigned char*)text;
+		rep->format = c0 == '>' ? MAHIP_FASTX_FASTA : c0 == '@' ? MAHIP_FASTX_FASTQ : 0;
+		if (rep->format == 0) { reason = MAHIP_FASTX_FIRST_BYTE; goto refuse; }
+	}
+	{
+		// ---- the line index of the window (the whole-file reader's census and line starts)
+		if ((n + FX_GRAN - 1) / FX_GRAN > 0xffffffffull) { reason = MAHIP_FASTX_TOO_MANY_LINES; goto refuse; }
+		const uint32_t n_gran = (uint32_t)((n + FX_GRAN - 1) / FX_GRAN);
+		const bool fq = rep->format == MAHIP_FASTX_FASTQ;
+		unsigned long long *ctr = P<unsigned long long>(b->fw_ctr);
+		FXW_RESERVE(b->fx_gcnt, (size_t)n_gran * 4); FXW_RESERVE(b->fx_gpos, (size_t)n_gran * 4 + 4);
+		HIPCHK(hipMemsetAsync(ctr, 0, FXW_NCTR * 8, c->st));
+		{
+			ProfScope ps(c, "k_fx_census", (double)n);
+			hipLaunchKernelGGL(k_fx_census, dim3(grid_for(n_gran, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const unsigned char*)b->fx_text.p, (uint64_t)n, n_gran, P<uint32_t>(b->fx_gcnt), ctr);
+			HIPCHK(hipGetLastError());
+		}
+		CHK(fxw_counters(c, b, h));
+		const uint64_t L = h[FX_NL] + (h[FX_LAST] != '\n');
+		if (L > 0xffffffffull) { reason = MAHIP_FASTX_TOO_MANY_LINES; goto refuse; }
+		const size_t list_cap = (L < b->fw_n_want ? (size_t)L : b->fw_n_want) + 1; // a wanted read enters the list once a window, a record once
+		FXW_RESERVE(b->fx_ls, (size_t)(L + 2) * 8); FXW_RESERVE(b->fw_list, list_cap * 4);
+		if (!fq) { FXW_RESERVE(b->fx_hdr, (size_t)L * 4); FXW_RESERVE(b->fx_hpos, (size_t)(L + 1) * 4); FXW_RESERVE(b->fx_recl, (size_t)(L + 1) * 4); }
+		CHK(scan_exclusive_u32(c, P<uint32_t>(b->fx_gcnt), P<uint32_t>(b->fx_gpos), n_gran, nullptr));
+		{
+			ProfScope ps(c, "k_fx_lines", (double)n + 8.0 * (double)L);
+			hipLaunchKernelGGL(k_fx_lines, dim3(grid_for(n_gran, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const unsigned char*)b->fx_text.p, (uint64_t)n, n_gran, P<uint32_t>(b->fx_gpos), (uint32_t)L, P<uint64_t>(b->fx_ls));
+			HIPCHK(hipGetLastError());
+		}
+		// ---- the consumed prefix, its records, its form: L and R of the prefix stay on the device
+		const FxText x = {(const unsigned char*)b->fx_text.p, (const uint64_t*)b->fx_ls.p, (const uint32_t*)b->fx_recl.p, (uint64_t)n, (uint32_t)L, 0u, fq};
+		const unsigned g_lines = grid_for(L, 256, MA_STREAM_BLOCKS);
+		ProfScope ps(c, "k_fxw_window", (double)n);
+		if (!fq) {
+			hipLaunchKernelGGL(k_fxw_hdr, dim3(g_lines), dim3(256), 0, c->st, x, P<uint32_t>(b->fx_hdr), ctr);
+			HIPCHK(hipGetLastError());
+			CHK(scan_exclusive_u32(c, P<uint32_t>(b->fx_hdr), P<uint32_t>(b->fx_hpos), L, P<uint32_t>(b->fx_hpos) + L));
+		}
+		hipLaunchKernelGGL(k_fxw_prefix, dim3(1), dim3(64), 0, c->st, x, (const uint32_t*)b->fx_hpos.p, last ? 1 : 0, ctr);
+		HIPCHK(hipGetLastError());
+		hipLaunchKernelGGL(k_fxw_bytes, dim3(grid_for(n_gran, 4, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const unsigned char*)b->fx_text.p, ctr);
+		HIPCHK(hipGetLastError());
+		if (!fq) {
+			hipLaunchKernelGGL(k_fxw_rec_lines, dim3(g_lines), dim3(256), 0, c->st, (const uint32_t*)b->fx_hdr.p, (const uint32_t*)b->fx_hpos.p, (const unsigned long long*)ctr, P<uint32_t>(b->fx_recl));
+			HIPCHK(hipGetLastError());
+			hipLaunchKernelGGL(k_fxw_form_fasta, dim3(g_lines), dim3(256), 0, c->st, x, P<uint32_t>(b->fx_hdr), ctr);
+		} else hipLaunchKernelGGL(k_fxw_form_fastq, dim3(grid_for(L / 4, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, ctr);
+		HIPCHK(hipGetLastError());
+		rep->laps_ms[1] += ((t1 = fx_now()) - t0) * 1e3; t0 = t1;
+		// ---- the names of the prefix's records against the table; the wanted reads that matched go to the list
+		hipLaunchKernelGGL(k_fxw_probe, dim3(grid_for(fq ? L / 4 : L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p,
+		                   (const uint64_t*)b->fx_whash.p, (const uint32_t*)b->fx_tab.p, b->fw_mask, P<uint32_t>(b->fx_win), (const unsigned char*)b->fw_seen.p, P<uint32_t>(b->fw_list), ctr);
+		HIPCHK(hipGetLastError());
+		CHK(fxw_counters(c, b, h));
+		rep->laps_ms[2] += ((t1 = fx_now()) - t0) * 1e3; t0 = t1;
+		// ---- the verdict, before the arena is touched (the whole-file reader's order of reasons)
+		if (h[FXW_CR]) reason = MAHIP_FASTX_CR;
+		else if (h[FXW_NUL]) reason = MAHIP_FASTX_NUL_BYTE;
+		else if (fq && last && L % 4) reason = MAHIP_FASTX_FASTQ_SHAPE;
+		else if (h[FX_V_FASTA]) reason = MAHIP_FASTX_FASTA_LINE_START;
+		else if (h[FX_V_SHAPE]) reason = MAHIP_FASTX_FASTQ_SHAPE;
+		else if (h[FX_V_QUAL]) reason = MAHIP_FASTX_FASTQ_QUAL_LEN;
+		else if (h[FX_V_LONG]) reason = MAHIP_FASTX_LONG_LINE;
+		else if (h[FX_SHORT]) reason = MAHIP_FASTX_SHORT_READ;
+		if (reason != MAHIP_FASTX_OK) goto refuse;
+		if (h[FXW_NLIST] >= list_cap) { mahip_set_error("mahip_useq_stream_piece_mem: the match list overflowed"); return -1; } // (cannot happen: see list_cap)
+		if (h[FXW_NLIST]) {
+			ProfScope pp(c, "k_fxw_place", 0);
+			hipLaunchKernelGGL(k_fxw_place, dim3(grid_for(h[FXW_NLIST], 1, 65536)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const uint32_t*)b->fw_list.p, (uint32_t)h[FXW_NLIST],
+			                   P<uint32_t>(b->fx_win), P<unsigned char>(b->fw_seen), (unsigned char*)b->arena.p);
+			HIPCHK(hipGetLastError());
+		}
+		b->fw_t_place += fx_now() - t0; rep->laps_ms[3] = b->fw_t_place * 1e3;
+		b->fw_carry_off = (size_t)h[FXW_CONSUMED]; b->fw_carry = (size_t)h[FXW_CARRY];
+		v->n_records = h[FXW_R]; v->bytes_consumed = h[FXW_CONSUMED]; v->carry_bytes = h[FXW_CARRY]; v->n_placed = h[FXW_NLIST];
+		rep->n_records += h[FXW_R]; rep->n_matched += h[FX_DISTINCT]; rep->n_dup += h[FX_MATCH] - h[FX_DISTINCT]; rep->n_jobs += h[FXW_NLIST];
+		if (h[FXW_CARRY] > rep->max_carry) rep->max_carry = h[FXW_CARRY];
+		return 0;
+	}
+refuse: // not an error: the window stays where it is (mahip_useq_stream_window_download), nothing of it has reached the arena
+	v->reason = reason; v->n_records = h[FXW_R]; v->carry_bytes = h[FXW_CARRY]; v->bytes_consumed = 0; v->n_placed = 0;
+	rep->refused_piece = piece_no; rep->refused_reason = reason; rep->n_short += h[FX_SHORT];
+	return 0;
+}
+#undef FXW_RESERVE
+
+extern "C" int mahip_useq_stream_window_download(mahip_ctx_t *c, void *dst, uint64_t *nbytes)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fw_active || b->fw_rep.refused_piece < 0) { mahip_set_error("mahip_useq_stream_window_download: no refused window"); return -1; }
+	*nbytes = b->fw_n;
+	if (dst && b->fw_n) CHK(xfer_copy(c, b->fx_text.p, dst, b->fw_n, 0));
+	return 0;
+}
+extern "C" int mahip_useq_stream_end(mahip_ctx_t *c)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fw_active) { mahip_set_error("mahip_useq_stream_end: no stream"); return -1; }
+	CHK(fxw_drain(c, b));
+	b->fw_active = false;
+	return 0;
+}
+extern "C" int mahip_useq_stream_abort(mahip_ctx_t *c)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	if (c->useq) { HIPCHK(hipStreamSynchronize(c->st)); ((UseqBufs*)c->useq)->fw_active = false; }
+	return 0;
+}
+extern "C" int mahip_useq_stream_last(mahip_ctx_t *c, mahip_useq_stream_report_t *out) { *out = useq_bufs(c)->fw_rep; return 0; }
 
 extern "C" void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in) { useq_bufs(c)->last = *in; }
 extern "C" int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out) { *out = useq_bufs(c)->last; return 0; }

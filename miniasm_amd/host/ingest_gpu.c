@@ -389,19 +389,11 @@ int ma_cut_next(ma_cut_t *k, char **buf, size_t *cap, size_t *len, int *last)
 
 static long gz_read_cb(void *src, char *dst, size_t want) { return (long)gzread((gzFile)src, dst, (unsigned)want); }
 
-/* two buffers between the producer (zlib + the cut) and the calling thread (upload + parse): state 0 = the producer's, 1 = holds a piece */
-typedef struct {
-	ma_cut_t cut;
-	pthread_mutex_t mu;
-	pthread_cond_t cv;
-	struct { char *p; size_t cap, len; int last, full; } b[2];
-	int stop, failed; /* the consumer gave up; the producer ran out of memory */
-	double t_prod;
-} stream_q_t;
-
+/* two buffers between the producer (zlib + the cut) and the calling thread (upload + the device's work on the piece): ma_stream_q_t of ma_host.h; the streamed
+ * PAF ingest below and the streamed reads-file reader (unitig_gfa.c) share it */
 static void *stream_producer(void *arg)
 {
-	stream_q_t *q = (stream_q_t*)arg;
+	ma_stream_q_t *q = (ma_stream_q_t*)arg;
 	int i = 0;
 	for (;; i ^= 1) {
 		double t0;
@@ -423,49 +415,78 @@ static void *stream_producer(void *arg)
 	return 0;
 }
 
+void ma_stream_q_init(ma_stream_q_t *q, gzFile fp, size_t piece_bytes)
+{
+	memset(q, 0, sizeof(*q));
+	q->cut.piece = piece_bytes; q->cut.read = gz_read_cb; q->cut.src = fp;
+	gzbuffer(fp, 1u << 20);
+	pthread_mutex_init(&q->mu, 0);
+	pthread_cond_init(&q->cv, 0);
+}
+int ma_stream_q_start(ma_stream_q_t *q) { q->started = pthread_create(&q->th, 0, stream_producer, q) == 0; return q->started ? 0 : -1; }
+/* buffer i holds the next piece when this returns (the time waited goes to q->t_wait); -1: the producer ran out of memory */
+int ma_stream_q_wait(ma_stream_q_t *q, int i)
+{
+	const double w0 = sys_realtime();
+	pthread_mutex_lock(&q->mu);
+	while (!q->b[i].full) pthread_cond_wait(&q->cv, &q->mu);
+	pthread_mutex_unlock(&q->mu);
+	q->t_wait += sys_realtime() - w0;
+	return q->failed ? -1 : 0;
+}
+/* buffer i goes back to the producer; stop: the consumer gives up -- the producer finishes the piece it is at and ends */
+void ma_stream_q_release(ma_stream_q_t *q, int i, int stop)
+{
+	pthread_mutex_lock(&q->mu);
+	q->b[i].full = 0;
+	if (stop) q->stop = 1;
+	pthread_cond_broadcast(&q->cv);
+	pthread_mutex_unlock(&q->mu);
+}
+/* the consumer gives up but KEEPS every buffer as it is: the producer finishes the piece it is at and ends; afterwards b[] and cut.carry hold what was read ahead */
+void ma_stream_q_halt(ma_stream_q_t *q)
+{
+	pthread_mutex_lock(&q->mu);
+	q->stop = 1;
+	pthread_cond_broadcast(&q->cv);
+	pthread_mutex_unlock(&q->mu);
+	ma_stream_q_join(q);
+}
+void ma_stream_q_join(ma_stream_q_t *q) { if (q->started) { pthread_join(q->th, 0); q->started = 0; } }
+void ma_stream_q_destroy(ma_stream_q_t *q)
+{
+	ma_stream_q_join(q);
+	free(q->b[0].p); free(q->b[1].p); free(q->cut.carry);
+	pthread_mutex_destroy(&q->mu);
+	pthread_cond_destroy(&q->cv);
+}
+
 /* the text behind fp (plain or gzip, file or pipe) piece by piece through the streamed parse: 0 = the records are in the context and d holds the dictionary, as
  * after ma_hit_ingest_loaded; -2 = the device refused (the stream is aborted, the text stage released; fp has been read from).  fp stays open. */
 int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes)
 {
 	const int timing = ma_timing_level() >= 1;
 	const double t0 = sys_realtime();
-	double t_wait = 0.0;
-	stream_q_t q;
-	pthread_t th;
+	ma_stream_q_t q;
 	mahip_paf_info_t info;
 	mahip_paf_stream_report_t sr;
 	int i = 0, bad = 0;
-	memset(&q, 0, sizeof(q));
 	memset(&sr, 0, sizeof(sr));
-	q.cut.piece = piece_bytes; q.cut.read = gz_read_cb; q.cut.src = fp;
-	gzbuffer(fp, 1u << 20);
-	pthread_mutex_init(&q.mu, 0);
-	pthread_cond_init(&q.cv, 0);
+	ma_stream_q_init(&q, fp, piece_bytes);
 	GPU(mahip_set_shard(c, 0, 0xffffffffu));
 	if (mahip_paf_stream_begin(c, min_span, min_match, bi_dir) != 0) bad = 1;
-	if (!bad && pthread_create(&th, 0, stream_producer, &q) != 0) { mahip_paf_stream_abort(c); ma_gpu_fail(__func__); }
+	if (!bad && ma_stream_q_start(&q) != 0) { mahip_paf_stream_abort(c); ma_gpu_fail(__func__); }
 	for (; !bad; i ^= 1) {
-		const double w0 = sys_realtime();
 		int last;
-		pthread_mutex_lock(&q.mu);
-		while (!q.b[i].full) pthread_cond_wait(&q.cv, &q.mu);
-		pthread_mutex_unlock(&q.mu);
-		t_wait += sys_realtime() - w0;
+		if (ma_stream_q_wait(&q, i) != 0) { fprintf(stderr, "[E::%s] out of memory for a piece of the input\n", __func__); exit(1); }
 		last = q.b[i].last;
-		if (q.failed) { fprintf(stderr, "[E::%s] out of memory for a piece of the input\n", __func__); exit(1); }
 		if (mahip_paf_stream_piece_mem(c, q.b[i].p, q.b[i].len, last) != 0) bad = 1;
-		pthread_mutex_lock(&q.mu);
-		q.b[i].full = 0;
-		if (bad) q.stop = 1;
-		pthread_cond_broadcast(&q.cv);
-		pthread_mutex_unlock(&q.mu);
-		if (last || bad) { pthread_join(th, 0); break; }
+		ma_stream_q_release(&q, i, bad);
+		if (last || bad) { ma_stream_q_join(&q); break; }
 	}
 	if (!bad && mahip_paf_stream_end(c, &info) != 0) bad = 1;
 	mahip_paf_stream_last(c, &sr);
-	free(q.b[0].p); free(q.b[1].p); free(q.cut.carry);
-	pthread_mutex_destroy(&q.mu);
-	pthread_cond_destroy(&q.cv);
+	ma_stream_q_destroy(&q);
 	if (bad) {
 		fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror());
 		mahip_paf_stream_abort(c);
@@ -474,7 +495,7 @@ int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match,
 	}
 	if (timing)
 		fprintf(stderr, "[T::ingest_gpu] stream: pieces=%lu piece=%lu B producer %.3f upload %.3f parse %.3f fold %.3f waited-for-input %.3f s\n", (unsigned long)sr.n_pieces,
-		        (unsigned long)piece_bytes, q.t_prod, sr.t_upload, sr.t_parse, sr.t_fold, t_wait);
+		        (unsigned long)piece_bytes, q.t_prod, sr.t_upload, sr.t_parse, sr.t_fold, q.t_wait);
 	ingest_dictionary(c, &info, d, n_hits, 1, t0);
 	return 0;
 }

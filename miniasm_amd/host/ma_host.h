@@ -5,6 +5,7 @@
 #include "miniasm_amd.h"
 #include "mahip.h"
 #include <zlib.h>
+#include <pthread.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -84,6 +85,27 @@ size_t ma_ingest_piece(void);    /* MA_INGEST_PIECE or the default, clamped to [
 typedef struct { size_t piece; long (*read)(void *src, char *dst, size_t want); void *src; char *carry; size_t carry_len, carry_cap; } ma_cut_t;
 int ma_cut_next(ma_cut_t *k, char **buf, size_t *cap, size_t *len, int *last); /* the next piece into *buf (grown as needed); 0 ok, -1 out of memory */
 int ma_hit_ingest_loaded(mahip_ctx_t *c, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, int release);
+/* two buffers between a producer thread (zlib + ma_cut_next on fp) and the calling thread, which works on piece k while piece k + 1 is inflated (ingest_gpu.c).
+ * b[i].full: 1 = holds a piece for the consumer, 0 = the producer's; the consumer takes b[0], b[1], b[0], ... in turn.  init, start, then per piece wait / use
+ * b[i] / release; join behind the last piece; destroy frees the buffers.  halt: stop reading ahead and keep what has been read (b[] and cut.carry). */
+typedef struct {
+	ma_cut_t cut;
+	pthread_mutex_t mu;
+	pthread_cond_t cv;
+	pthread_t th;
+	struct { char *p; size_t cap, len; int last, full; } b[2];
+	int stop, failed, started; /* the consumer gave up; the producer ran out of memory; the thread runs */
+	double t_prod, t_wait;     /* seconds in ma_cut_next; seconds the consumer waited for a piece */
+} ma_stream_q_t;
+void ma_stream_q_init(ma_stream_q_t *q, gzFile fp, size_t piece_bytes);
+int ma_stream_q_start(ma_stream_q_t *q);
+int ma_stream_q_wait(ma_stream_q_t *q, int i);
+void ma_stream_q_release(ma_stream_q_t *q, int i, int stop);
+void ma_stream_q_halt(ma_stream_q_t *q);
+void ma_stream_q_join(ma_stream_q_t *q);
+void ma_stream_q_destroy(ma_stream_q_t *q);
+int ma_fastx_stream_mode(void); /* MA_FASTX_STREAM: 0 (unset) off, 1 = the reads files the whole-file device reader cannot take, 2 = every reads file (unitig_gfa.c) */
+size_t ma_fastx_piece(void);    /* MA_FASTX_PIECE or 16 MiB, clamped to [256, 1 GiB] */
 int ma_gpu_parse_enabled(void); /* 0 when MA_HOST_PARSE=1 */
 int ma_gzip_device_enabled(void); /* MA_GZIP_DEVICE: plain gzip files are cut into chunks and inflated on the device (ingest_gpu.c) */
 size_t ma_gzip_chunk(void);       /* MA_GZIP_CHUNK or the default */

@@ -344,14 +344,35 @@ void ma_ug_print_mem(const ma_ug_t *ug, const sdict_t *d, const ma_sub_t *sub, c
 #include <unistd.h>
 #include <sys/stat.h>
 
-typedef struct { gzFile fp; unsigned char *buf; int beg, end, eof; } fq_stream_t;
+/* the bytes of the stream: fp, and in front of it (pre != 0) up to FQ_SEGS stretches of memory -- what the streamed device reader had taken from fp when it handed
+ * over (below) */
+#define FQ_SEGS 3
+typedef struct { struct { const unsigned char *p; size_t len; } seg[FQ_SEGS]; int i; } fq_pre_t;
+typedef struct { gzFile fp; unsigned char *buf; int beg, end, eof; fq_pre_t *pre; } fq_stream_t;
 #define FQ_BUF (1 << 18)
+
+/* the next FQ_BUF bytes (fewer: the end of the input), as gzread returns them.  Out of line and without the stream's address: fq_getc runs once per byte, and the
+ * cursor of a stream whose address goes nowhere stays in registers */
+static int __attribute__((noinline)) fq_fill(gzFile fp, unsigned char *buf, fq_pre_t *pre)
+{
+	int n = 0, got;
+	while (pre && pre->i < FQ_SEGS && n < FQ_BUF) {
+		const size_t k = pre->seg[pre->i].len < (size_t)(FQ_BUF - n) ? pre->seg[pre->i].len : (size_t)(FQ_BUF - n);
+		if (k == 0) { ++pre->i; continue; }
+		memcpy(buf + n, pre->seg[pre->i].p, k);
+		pre->seg[pre->i].p += k; pre->seg[pre->i].len -= k;
+		n += (int)k;
+	}
+	if (n == FQ_BUF) return n;
+	got = gzread(fp, buf + n, FQ_BUF - n);
+	return got > 0 ? n + got : n ? n : got;
+}
 
 static inline int fq_getc(fq_stream_t *f)
 {
 	if (f->beg >= f->end) {
 		if (f->eof) return -1;
-		f->beg = 0; f->end = gzread(f->fp, f->buf, FQ_BUF);
+		f->beg = 0; f->end = fq_fill(f->fp, f->buf, f->pre);
 		if (f->end < FQ_BUF) f->eof = 1;
 		if (f->end <= 0) { f->end = 0; return -1; }
 	}
@@ -414,6 +435,31 @@ static int fq_read(fq_stream_t *f, int *last, fq_str_t *name, fq_str_t *seq)
 
 typedef struct { uint32_t utg:31, ori:1, start, len; } utg_place_t;
 
+/* the reads that sit on a unitig as the device readers want them (include/mahip.h: mahip_useq_want_t): name, where the bases go, strand, kept interval; free() both */
+static void ug_seq_wanted(const sdict_t *d, const ma_sub_t *sub, const utg_place_t *pl, const uint64_t *uoff, mahip_useq_want_t **want_, char **names_, size_t *n_want_, size_t *name_bytes_)
+{
+	mahip_useq_want_t *want;
+	char *names;
+	size_t n_want = 0, name_bytes = 0;
+	uint32_t i;
+	for (i = 0; i < d->n_seq; ++i) if (pl[i].len) ++n_want, name_bytes += strlen(d->seq[i].name);
+	want = (mahip_useq_want_t*)malloc((n_want ? n_want : 1) * sizeof(mahip_useq_want_t));
+	names = (char*)malloc(name_bytes ? name_bytes : 1);
+	n_want = name_bytes = 0;
+	for (i = 0; i < d->n_seq; ++i) {
+		const utg_place_t *t = &pl[i];
+		mahip_useq_want_t *w = &want[n_want];
+		const size_t l = strlen(d->seq[i].name);
+		if (t->len == 0 || l == 0) continue; /* (no record has an empty name that matches) */
+		memcpy(names + name_bytes, d->seq[i].name, l);
+		w->dst_off = uoff[t->utg] + t->start; w->name_off = name_bytes; w->name_len = (uint32_t)l;
+		w->len = t->len; w->rev = t->ori; w->whole = sub == 0;
+		w->s = sub ? sub[i].s : 0; w->e = sub ? sub[i].e : 0;
+		++n_want; name_bytes += l;
+	}
+	*want_ = want; *names_ = names; *n_want_ = n_want; *name_bytes_ = name_bytes;
+}
+
 /* The reads file on the device (csrc/useq.hip): a plain file goes to HBM as it is; the device checks that it is in the regular form (include/mahip.h), looks
  * the names of the reads that sit on a unitig up among its records and copies their bases into the arena.  Returns 1 when the arena is filled, 0 with
  * ui->reason when the host reader has to run (the arena is untouched then), -1 on an error. */
@@ -427,7 +473,6 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	mahip_useq_want_t *want;
 	char *names;
 	size_t n_want = 0, name_bytes = 0;
-	uint32_t i;
 	double t0, pl_laps[2];
 	int fd, rc;
 	if (e && atoi(e) != 0) { ui->reason = MAHIP_FASTX_FORCED; return 0; }
@@ -461,21 +506,7 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	laps[LAP_INDEX] = (sys_realtime() - t0) * 1e3;
 	ui->format = fi.format; ui->n_records = fi.n_records;
 	if (!fi.regular) { ui->reason = fi.reason; mahip_fastx_release(c); return 0; }
-	for (i = 0; i < d->n_seq; ++i) if (pl[i].len) ++n_want, name_bytes += strlen(d->seq[i].name);
-	want = (mahip_useq_want_t*)malloc((n_want ? n_want : 1) * sizeof(mahip_useq_want_t));
-	names = (char*)malloc(name_bytes ? name_bytes : 1);
-	n_want = name_bytes = 0;
-	for (i = 0; i < d->n_seq; ++i) {
-		const utg_place_t *t = &pl[i];
-		mahip_useq_want_t *w = &want[n_want];
-		const size_t l = strlen(d->seq[i].name);
-		if (t->len == 0 || l == 0) continue; /* (no record has an empty name that matches) */
-		memcpy(names + name_bytes, d->seq[i].name, l);
-		w->dst_off = uoff[t->utg] + t->start; w->name_off = name_bytes; w->name_len = (uint32_t)l;
-		w->len = t->len; w->rev = t->ori; w->whole = sub == 0;
-		w->s = sub ? sub[i].s : 0; w->e = sub ? sub[i].e : 0;
-		++n_want; name_bytes += l;
-	}
+	ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
 	rc = mahip_useq_place_text(c, want, n_want, names, name_bytes, &ui->n_matched, &ui->n_dup, &ui->n_short, pl_laps);
 	free(want); free(names);
 	laps[LAP_LOOKUP] = pl_laps[0]; laps[LAP_PLACE] = pl_laps[1];
@@ -485,58 +516,95 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	return 1;
 }
 
+/* MA_FASTX_STREAM: 0 or unset = off; 1 = the streamed device reader takes what the whole-file reader cannot (NOT_PLAIN: gzip, stdin, a FIFO, a bgzip file that is
+ * refused or host-forced; NOMEM); 2 = it takes every reads file (tests and tools/useq_stream_time.py reach it with any text).  The default stays off: DESIGN 7 */
+int ma_fastx_stream_mode(void)
+{
+	const char *s = getenv("MA_FASTX_STREAM");
+	const int v = s && *s ? atoi(s) : 0;
+	return v == 1 || v == 2 ? v : 0;
+}
+#define MA_FASTX_PIECE_DEFAULT ((size_t)16 << 20)
+size_t ma_fastx_piece(void)
+{
+	const char *s = getenv("MA_FASTX_PIECE");
+	long long v = s && *s ? atoll(s) : (long long)MA_FASTX_PIECE_DEFAULT;
+	return v < 256 ? (size_t)256 : v > (1ll << 30) ? (size_t)1 << 30 : (size_t)v;
+}
+
+/* The reads file through the device a piece at a time (csrc/useq.hip): f->fp is read in pieces of whole lines by a second thread (ingest_gpu.c:
+ * ma_stream_q_t) while this one has the piece before uploaded, indexed, checked, looked up and placed.  Returns 1 when the whole input went that way; 0 when
+ * a window got a verdict other than OK (ui->reason): the windows before it are placed, and f reads on from the first byte of that
+ * window -- the window itself (fetched from the device at this moment only), what the producer had read ahead, then the rest of fp; nothing is read twice.
+ * *keep: memory f points into, to be freed behind the host reader.  -1 on an error. */
+enum { SLAP_PRODUCER, SLAP_UPLOAD, SLAP_INDEX, SLAP_LOOKUP, SLAP_PLACE, SLAP_WAIT, N_SLAPS };
+typedef struct { void *window; ma_stream_q_t q; int q_live; fq_pre_t pre; } stream_keep_t;
+static int ug_seq_stream(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, fq_stream_t *f, const utg_place_t *pl, const uint64_t *uoff, size_t piece_bytes, mahip_useq_info_t *ui,
+                         mahip_useq_stream_report_t *sr, double *slaps, stream_keep_t *keep)
+{
+	mahip_useq_want_t *want;
+	char *names;
+	size_t n_want = 0, name_bytes = 0;
+	ma_stream_q_t *q = &keep->q;
+	int i = 0, rc, handed = 0;
+	ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
+	mahip_mem_trim(c, 0);
+	rc = mahip_useq_stream_begin(c, want, n_want, names, name_bytes);
+	free(want); free(names);
+	if (rc != 0) return -1;
+	ma_stream_q_init(q, f->fp, piece_bytes);
+	keep->q_live = 1;
+	if (ma_stream_q_start(q) != 0) { mahip_useq_stream_abort(c); return -1; }
+	for (;; i ^= 1) {
+		mahip_useq_stream_verdict_t v;
+		int last;
+		if (ma_stream_q_wait(q, i) != 0) { fprintf(stderr, "[E::%s] out of memory for a piece of the reads file\n", __func__); exit(1); }
+		last = q->b[i].last;
+		if (mahip_useq_stream_piece_mem(c, q->b[i].p, q->b[i].len, last, &v) != 0) { ma_stream_q_release(q, i, 1); ma_stream_q_join(q); mahip_useq_stream_abort(c); return -1; }
+		if (v.reason != MAHIP_FASTX_OK) { /* the handover: never a rewind */
+			uint64_t wn = 0;
+			ma_stream_q_halt(q); /* b[i] is still ours; b[i ^ 1] holds the next piece if there is one; cut.carry what follows it */
+			if (mahip_useq_stream_window_download(c, 0, &wn) != 0) return -1;
+			keep->window = malloc(wn ? wn : 1);
+			if (mahip_useq_stream_window_download(c, keep->window, &wn) != 0) return -1;
+			keep->pre.seg[0].p = (const unsigned char*)keep->window; keep->pre.seg[0].len = (size_t)wn;
+			if (!last && q->b[i ^ 1].full) { keep->pre.seg[1].p = (const unsigned char*)q->b[i ^ 1].p; keep->pre.seg[1].len = q->b[i ^ 1].len; }
+			keep->pre.seg[2].p = (const unsigned char*)q->cut.carry; keep->pre.seg[2].len = q->cut.carry_len;
+			f->pre = &keep->pre;
+			ui->reason = v.reason;
+			handed = 1;
+			break;
+		}
+		ma_stream_q_release(q, i, 0);
+		if (last) { ma_stream_q_join(q); break; }
+	}
+	if ((handed ? mahip_useq_stream_abort(c) : mahip_useq_stream_end(c)) != 0) return -1;
+	mahip_useq_stream_last(c, sr);
+	if (mahip_fastx_release(c) != 0) return -1;
+	ui->format = sr->format; ui->n_records = sr->n_records; ui->n_matched = sr->n_matched; ui->n_dup = sr->n_dup; ui->n_short = sr->n_short;
+	slaps[SLAP_PRODUCER] = q->t_prod * 1e3; slaps[SLAP_WAIT] = q->t_wait * 1e3;
+	slaps[SLAP_UPLOAD] = sr->laps_ms[0]; slaps[SLAP_INDEX] = sr->laps_ms[1]; slaps[SLAP_LOOKUP] = sr->laps_ms[2]; slaps[SLAP_PLACE] = sr->laps_ms[3];
+	if (!handed) ui->reason = MAHIP_FASTX_OK;
+	return handed ? 0 : 1;
+}
+
 /* Host reader (the fallback: gzip, stdin, files outside the regular form): the file is read here (one inflate stream, the reference's record rules); the bases of every read that sits on a unitig go to
  * the device in batches and a byte-gather kernel places them (forward copy / reverse complement, csrc/useq.hip); the unitig
  * strings come back once, at the end. */
 #define USEQ_BATCH_BYTES ((size_t)256 << 20)
-int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
+/* the host reader's loop (asm.c:262-284) over what f0 still holds.  The stream is a local copy whose address goes nowhere, so its cursor stays in registers: fq_getc
+ * runs once per byte of the input */
+static void __attribute__((noinline)) ug_seq_host(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, const fq_stream_t *f0, const utg_place_t *pl, const uint64_t *uoff)
 {
-	mahip_ctx_t *c;
-	fq_stream_t f;
+	fq_stream_t f = *f0;
 	fq_str_t name = {0, 0, 0}, seq = {0, 0, 0};
-	utg_place_t *pl;
-	uint64_t *uoff, tot = 0;
-	char *batch, *arena;
-	mahip_useq_job_t *jobs;
 	size_t n_jobs = 0, m_jobs = 1 << 16, n_batch = 0, m_batch = USEQ_BATCH_BYTES;
-	uint32_t i, j;
-	int last = 0, on_device;
-	uint32_t *in_batch, batch_no = 1; /* host reader: the batch that holds a job of the read */
-	mahip_useq_info_t ui;
-	double laps[N_LAPS] = {0, 0, 0, 0, 0}, t_dl;
-	static const char *const fmt_name[] = {"?", "fasta", "fastq"};
-	memset(&f, 0, sizeof(f));
-	memset(&ui, 0, sizeof(ui));
-	f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
-	if (f.fp == 0) return -1;                                                      /*  nothing is read through it unless the host reader runs) */
-	c = ma_gpu();
-	pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
-	uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
-	for (i = 0; i < g->u.n; ++i) { /* where every read lands; unitig strings back to back, each with its terminator */
-		const ma_utg_t *u = &g->u.a[i];
-		uint32_t l = 0;
-		uoff[i] = tot; tot += (uint64_t)u->len + 1;
-		for (j = 0; j < u->n; ++j) {
-			utg_place_t *t = &pl[u->a[j] >> 33];
-			assert(t->len == 0);
-			t->utg = i, t->ori = u->a[j] >> 32 & 1;
-			t->start = l, t->len = (uint32_t)u->a[j];
-			l += t->len;
-		}
-	}
-	GPU(mahip_useq_begin(c, (size_t)tot));
-	on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &ui, laps);
-	if (on_device < 0) ma_gpu_fail(__func__);
-	ui.reader = on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
-	mahip_useq_note(c, &ui);
-	if (!on_device) {
-		fprintf(stderr, "[W::%s] reads file read on the host: %s\n", __func__, mahip_fastx_reason_name(ui.reason));
-		f.buf = (unsigned char*)malloc(FQ_BUF);
-	}
-	batch = on_device ? 0 : (char*)malloc(m_batch);
-	jobs = on_device ? 0 : (mahip_useq_job_t*)malloc(m_jobs * sizeof(mahip_useq_job_t));
-	in_batch = on_device ? 0 : (uint32_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(uint32_t));
-	while (!on_device && fq_read(&f, &last, &name, &seq) >= 0) {
+	char *batch = (char*)malloc(m_batch);
+	mahip_useq_job_t *jobs = (mahip_useq_job_t*)malloc(m_jobs * sizeof(mahip_useq_job_t));
+	uint32_t *in_batch = (uint32_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(uint32_t)), batch_no = 1; /* the batch that holds a job of the read */
+	int last = 0;
+	f.buf = (unsigned char*)malloc(FQ_BUF);
+	while (fq_read(&f, &last, &name, &seq) >= 0) {
 		int32_t id = name.s ? sd_get(d, name.s) : -1;
 		const utg_place_t *t;
 		const char *rs = seq.s;
@@ -559,13 +627,79 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 		jobs[n_jobs].src_len = (uint32_t)rl; jobs[n_jobs].len = t->len; jobs[n_jobs].rev = t->ori; jobs[n_jobs].pad = 0;
 		++n_jobs; n_batch += rl;
 	}
-	if (!on_device) GPU(mahip_useq_batch(c, batch, n_batch, jobs, n_jobs));
+	GPU(mahip_useq_batch(c, batch, n_batch, jobs, n_jobs));
+	free(batch); free(jobs); free(in_batch); free(name.s); free(seq.s); free(f.buf);
+}
+
+int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
+{
+	mahip_ctx_t *c;
+	fq_stream_t f;
+	utg_place_t *pl;
+	uint64_t *uoff, tot = 0;
+	char *arena;
+	uint32_t i, j;
+	int on_device = 0;
+	mahip_useq_info_t ui;
+	double laps[N_LAPS] = {0, 0, 0, 0, 0}, t_dl, slaps[N_SLAPS] = {0, 0, 0, 0, 0, 0};
+	const int stream_mode = ma_fastx_stream_mode();
+	const size_t piece_bytes = ma_fastx_piece();
+	int forced, streamed = 0;
+	mahip_useq_stream_report_t sr;
+	stream_keep_t keep;
+	static const char *const fmt_name[] = {"?", "fasta", "fastq"};
+	memset(&f, 0, sizeof(f));
+	memset(&ui, 0, sizeof(ui));
+	memset(&sr, 0, sizeof(sr));
+	memset(&keep, 0, sizeof(keep));
+	f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
+	if (f.fp == 0) return -1;                                                      /*  nothing is read through it unless the host reader runs) */
+	c = ma_gpu();
+	pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
+	uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
+	for (i = 0; i < g->u.n; ++i) { /* where every read lands; unitig strings back to back, each with its terminator */
+		const ma_utg_t *u = &g->u.a[i];
+		uint32_t l = 0;
+		uoff[i] = tot; tot += (uint64_t)u->len + 1;
+		for (j = 0; j < u->n; ++j) {
+			utg_place_t *t = &pl[u->a[j] >> 33];
+			assert(t->len == 0);
+			t->utg = i, t->ori = u->a[j] >> 32 & 1;
+			t->start = l, t->len = (uint32_t)u->a[j];
+			l += t->len;
+		}
+	}
+	GPU(mahip_useq_begin(c, (size_t)tot));
+	{ const char *e = getenv("MA_FASTX_HOST"); forced = e && atoi(e) != 0; }
+	if (forced || stream_mode != 2) { /* the whole-file device reader first, as ever */
+		on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &ui, laps);
+		if (on_device < 0) ma_gpu_fail(__func__);
+	}
+	if (!forced && !on_device && (stream_mode == 2 || (stream_mode == 1 && (ui.reason == MAHIP_FASTX_NOT_PLAIN || ui.reason == MAHIP_FASTX_NOMEM)))) { /* the streamed device reader */
+		memset(&ui, 0, sizeof(ui));
+		streamed = 1;
+		on_device = ug_seq_stream(c, d, sub, &f, pl, uoff, piece_bytes, &ui, &sr, slaps, &keep);
+		if (on_device < 0) ma_gpu_fail(__func__);
+	}
+	ui.reader = streamed ? MAHIP_USEQ_STREAM : on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
+	mahip_useq_note(c, &ui);
+	if (!on_device) {
+		if (streamed) fprintf(stderr, "[W::%s] reads file handed to the host reader at piece %lld: %s\n", __func__, (long long)sr.refused_piece, mahip_fastx_reason_name(ui.reason));
+		else fprintf(stderr, "[W::%s] reads file read on the host: %s\n", __func__, mahip_fastx_reason_name(ui.reason));
+	}
+	if (!on_device) ug_seq_host(c, d, sub, &f, pl, uoff);
 	arena = (char*)malloc(tot ? tot : 1);
 	t_dl = sys_realtime();
 	GPU(mahip_useq_end(c, arena));
 	laps[LAP_DOWNLOAD] = (sys_realtime() - t_dl) * 1e3;
 	if (ma_timing_level() >= 1) {
-		if (on_device) fprintf(stderr, "[T::ug_seq] reader=device format=%s records=%llu matched=%llu dup=%llu : load %.3f index %.3f lookup %.3f place %.3f download %.3f ms\n", fmt_name[ui.format],
+		if (streamed) {
+			char ho[32];
+			if (sr.refused_piece < 0) strcpy(ho, "none"); else snprintf(ho, sizeof(ho), "%lld", (long long)sr.refused_piece);
+			fprintf(stderr, "[T::ug_seq] reader=stream format=%s pieces=%llu piece=%llu B records=%llu matched=%llu dup=%llu handover=%s reason=%d : producer %.3f upload %.3f index %.3f lookup %.3f place %.3f waited-for-input %.3f download %.3f ms\n",
+			        fmt_name[ui.format], (unsigned long long)sr.n_pieces, (unsigned long long)piece_bytes, (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, ho, ui.reason,
+			        slaps[SLAP_PRODUCER], slaps[SLAP_UPLOAD], slaps[SLAP_INDEX], slaps[SLAP_LOOKUP], slaps[SLAP_PLACE], slaps[SLAP_WAIT], laps[LAP_DOWNLOAD]);
+		} else if (on_device) fprintf(stderr, "[T::ug_seq] reader=device format=%s records=%llu matched=%llu dup=%llu : load %.3f index %.3f lookup %.3f place %.3f download %.3f ms\n", fmt_name[ui.format],
 		                       (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, laps[LAP_LOAD], laps[LAP_INDEX], laps[LAP_LOOKUP], laps[LAP_PLACE], laps[LAP_DOWNLOAD]);
 		else fprintf(stderr, "[T::ug_seq] reader=host reason=%d format=%s records=%llu : download %.3f ms\n", ui.reason, fmt_name[ui.format], (unsigned long long)ui.n_records, laps[LAP_DOWNLOAD]);
 	}
@@ -575,8 +709,9 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 		memcpy(u->s, arena + uoff[i], u->len);
 		u->s[u->len] = 0;
 	}
-	free(arena); free(batch); free(jobs); free(uoff); free(in_batch);
-	free(pl); free(name.s); free(seq.s); free(f.buf);
+	free(arena); free(uoff); free(pl);
+	if (keep.q_live) ma_stream_q_destroy(&keep.q);
+	free(keep.window);
 	if (f.fp) gzclose(f.fp);
 	return 0;
 }
