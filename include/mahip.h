@@ -109,8 +109,8 @@ uint32_t mahip_paf_max_qs(mahip_ctx_t *c);                                  /* i
  * mahip_paf_parse leaves it on the concatenated text: the same records in the same order (hit.c:70-101), the same ids and first-seen lengths (sdict.c:27-45
  * sd_put), the same mahip_paf_info_t; mahip_paf_names, mahip_paf_seqs, mahip_paf_release, mahip_hits_sort and what follows work as after a whole parse (records
  * are a line's record and its mirror side by side: the run stride is set to 2, or to 1 without bi_dir).  mahip_paf_last and mahip_paf_cols_download describe the
- * LAST PIECE THAT HAD TEXT (zeros when none had).  Not served: -R (hit.c:38-68 needs every line before any id is given out; the reference reads the file twice
- * for it) -- use mahip_paf_parse_excl --, and contexts with a communicator.
+ * LAST PIECE THAT HAD TEXT (zeros when none had).  -R is served by mahip_paf_stream_begin_excl (below: provisional ids, renumbered at the end).  Not served:
+ * contexts with a communicator.
  * mahip_paf_stream_begin (hit.c:76-79: the dictionary and the record array start empty): a stream the context still holds is dropped.
  * mahip_paf_stream_piece_mem (hit.c:80-100 on the lines of the piece): a piece is WHOLE LINES -- one that is not the last, has bytes and does not end with '\n'
  * is an error; the last piece (last != 0) may end without a newline and gets the virtual one a whole parse gives its text (kseq.h:139-144: the rest of the
@@ -137,6 +137,22 @@ int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size_t nbytes, 
 int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info);
 int mahip_paf_stream_abort(mahip_ctx_t *c);
 int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *out);   /* valid from begin until the next begin, abort or mahip_paf_release */
+/* -R in the stream (hit.c:38-68 + hit.c:86): begin_excl with no_cont != 0 ... end leaves the context as mahip_paf_parse_excl leaves it on the
+ * concatenated text, n_excl included.  One pass: names get PROVISIONAL ids while pieces arrive; every stored line gives its verdict against them (a flag per
+ * id, 0 -> 1 only); a stored line that touches an id flagged so far is dropped at once; mahip_paf_stream_end retires the records a later flag killed, renumbers
+ * the surviving names by first appearance among the surviving lines and rebuilds the dictionary in that order (a name's first-seen length is the one of its
+ * first SURVIVING line).  Until then the stream holds the records of lines that die late, and 8 bytes a record for the lengths: peak_records against
+ * info.n_hits is what the single pass costs.  no_cont == 0: mahip_paf_stream_begin, to the byte.  MA_STREAM_NOCONT_EARLY=0: no early drop (tests; same result). */
+typedef struct {
+	uint64_t n_early_lines;           /* stored lines dropped in their own piece: they touched a name flagged by then */
+	uint64_t n_late_records, n_late_lines; /* records retired at the end, and the lines they were */
+	uint64_t peak_records;            /* the most records the stream ever held */
+	uint32_t n_flagged;               /* names flagged (= info.n_excl) */
+	uint32_t n_renumbered;            /* names that got an id at the end (= info.n_seq) */
+	uint32_t n_flag_grow, n_lens_grow; /* times the flag array / the lengths column was replaced by a larger one (the first buffers replace none) */
+} mahip_paf_stream_excl_report_t;
+int mahip_paf_stream_begin_excl(mahip_ctx_t *c, int min_span, int min_match, int bi_dir, int no_cont, int max_hang, float int_frac);
+int mahip_paf_stream_excl_last(mahip_ctx_t *c, mahip_paf_stream_excl_report_t *out); /* valid as mahip_paf_stream_last; all zero without no_cont (but peak_records) */
 /* read-only, between begin and end: the persistent name table as it stands, report.tab_cap words of tag(32) | id, all ones = free (no slots before the first
  * piece that stored a line).  Between pieces no word holds a provisional claim (bit 31 of the low word).  For tests. */
 int mahip_paf_stream_tab_download(mahip_ctx_t *c, uint64_t *slots);

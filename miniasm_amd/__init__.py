@@ -170,6 +170,11 @@ class PafStreamReport(C.Structure):  # include/mahip.h: mahip_paf_stream_report_
                 ("t_upload", C.c_double), ("t_parse", C.c_double), ("t_fold", C.c_double), ("n_arena_grow", C.c_uint32), ("n_ids_grow", C.c_uint32)]
 
 
+class PafStreamExclReport(C.Structure):  # include/mahip.h: mahip_paf_stream_excl_report_t
+    _fields_ = [("n_early_lines", C.c_uint64), ("n_late_records", C.c_uint64), ("n_late_lines", C.c_uint64), ("peak_records", C.c_uint64),
+                ("n_flagged", C.c_uint32), ("n_renumbered", C.c_uint32), ("n_flag_grow", C.c_uint32), ("n_lens_grow", C.c_uint32)]
+
+
 PAF_DICT_FORMS = {0: None, 1: "short", 2: "text"}  # MAHIP_PAF_DICT_*
 PAF_TAB_ENDS = {0: "ok", 1: "load", 2: "probes"}   # MAHIP_PAF_TAB_*
 
@@ -238,6 +243,8 @@ def lib():
         L.mahip_paf_cols_download.argtypes = [vp] + [vp] * 8
         L.mahip_paf_keep_odd.argtypes = [vp, i32]
         L.mahip_paf_stream_begin.argtypes = [vp, i32, i32, i32]
+        L.mahip_paf_stream_begin_excl.argtypes = [vp, i32, i32, i32, i32, i32, C.c_float]
+        L.mahip_paf_stream_excl_last.argtypes = [vp, C.POINTER(PafStreamExclReport)]
         L.mahip_paf_stream_piece_mem.argtypes = [vp, vp, sz, i32]
         L.mahip_paf_stream_end.argtypes = [vp, C.POINTER(PafInfo)]
         L.mahip_paf_stream_abort.argtypes = [vp]
@@ -384,13 +391,22 @@ class Ctx:
         _chk(lib().mahip_paf_stream_last(self.h, C.byref(r)), "paf_stream_last")
         return r
 
-    def paf_stream(self, pieces, min_span, min_match, bi_dir, each=None):
+    def paf_stream_excl_last(self):
+        r = PafStreamExclReport()
+        _chk(lib().mahip_paf_stream_excl_last(self.h, C.byref(r)), "paf_stream_excl_last")
+        return r
+
+    def paf_stream(self, pieces, min_span, min_match, bi_dir, each=None, no_cont=None):
         """pieces (bytes objects, whole lines each; only the last may end without a newline) through the streamed ingest: begin, a piece at a time, end.
         Returns (PafInfo, PafStreamReport); the context is left as after mahip_paf_parse on the concatenated text.  each(k, report): called behind piece k.
+        no_cont=(max_hang, int_frac): -R, the context is left as after mahip_paf_parse_excl (paf_stream_excl_last() has that part's report).
         An error aborts the stream before it is raised."""
         L = lib()
         pieces = list(pieces)
-        _chk(L.mahip_paf_stream_begin(self.h, min_span, min_match, 1 if bi_dir else 0), "paf_stream_begin")
+        if no_cont is None:
+            _chk(L.mahip_paf_stream_begin(self.h, min_span, min_match, 1 if bi_dir else 0), "paf_stream_begin")
+        else:
+            _chk(L.mahip_paf_stream_begin_excl(self.h, min_span, min_match, 1 if bi_dir else 0, 1, int(no_cont[0]), float(no_cont[1])), "paf_stream_begin_excl")
         info = PafInfo()
         try:
             for k, p in enumerate(pieces):

@@ -1464,13 +1464,19 @@ struct PafStream {
 	uint32_t max_qs = 0, last_bl = 0;
 	bool have_bl = false, any_parsed = false;
 	mahip_paf_stream_report_t rep = {};
+	// -R in the stream (mahip_paf_stream_begin_excl; none of it exists without no_cont): a byte per provisional id, 1 = clearly contained (hit.c:38-68); per record, the
+	// lengths of its two names (ql, tl; a mirror record holds them swapped) -- what the first-seen length of a read is taken from once it is known which lines survive
+	int no_cont = 0, max_hang = 0, early = 1;
+	float int_frac = 0.f;
+	DevBuf excl, lens;
+	mahip_paf_stream_excl_report_t xrep = {};
 };
 
 static void paf_stream_free(mahip_ctx *c, PafBufs *b)
 {
 	PafStream *st = b->stream;
 	if (!st) return;
-	DevBuf *all[] = { &st->tab, &st->arena, &st->seq_len, &st->name_pos, &st->name_len, &st->rec, &st->fold, &st->map };
+	DevBuf *all[] = { &st->tab, &st->arena, &st->seq_len, &st->name_pos, &st->name_len, &st->rec, &st->fold, &st->map, &st->excl, &st->lens };
 	for (DevBuf *d : all) dev_free(c, *d);
 	delete st;
 	b->stream = nullptr;
@@ -1565,6 +1571,116 @@ __global__ __launch_bounds__(64) void k_stream_last_bl(const uint8_t *__restrict
 	if (lane == 0) { out[0] = has; out[1] = v; out[2] = flags[0]; }
 }
 
+// ---- -R in the stream.  The exclusion is a property of NAMES (k_paf_nocont above), and a name keeps its provisional id for the whole stream, so the
+// flag lives per provisional id and only ever goes from 0 to 1.  Per piece, behind the fold (map: the piece's table slot -> provisional id, every slot of a stored
+// line has one): every stored line gives its verdict, then the stored lines that touch a flagged id -- flagged now or by any earlier piece -- lose their stored
+// bit.  A line that is kept here may still die at the end, by a flag a later piece raises (k_stream_mark).
+__global__ __launch_bounds__(256) void k_stream_verdict(PafCols o, uint32_t L, const uint32_t *__restrict__ map, int max_hang, float int_frac, uint8_t *__restrict__ excl)
+{
+	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < L; i += gridDim.x * 256u) {
+		if (!(o.flags[i] & 2)) continue;
+		const int v = mc_no_cont(o.ql[i], o.qs[i], o.qe[i], o.tl[i], o.ts[i], o.te[i], o.flags[i] >> 3 & 1, max_hang, int_frac);
+		if (v == 1) excl[map[o.tslot[i]]] = 1;
+		else if (v == 2) excl[map[o.qslot[i]]] = 1;
+	}
+}
+// drop != 0: the early drop.  cnt[i] = the records line i will give (k_paf_emit_chain: 1, or 2 with bi_dir and two different names; 0 when it is not stored)
+__global__ __launch_bounds__(256) void k_stream_early(PafCols o, uint32_t L, const uint32_t *__restrict__ map, const uint8_t *__restrict__ excl, int drop, int bi_dir,
+                                                       uint32_t *__restrict__ cnt, unsigned long long *__restrict__ ctr)
+{
+	uint32_t pass = 0;
+	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < L; i += gridDim.x * 256u) {
+		uint32_t n = 0;
+		if (o.flags[i] & 2) {
+			const uint32_t q = map[o.qslot[i]], t = map[o.tslot[i]];
+			if (drop && (excl[q] || excl[t])) o.flags[i] &= (uint8_t)~2u;
+			else { n = 1u + (bi_dir && q != t); ++pass; }
+		}
+		cnt[i] = n;
+	}
+	blk_add_u64(&ctr[PC_PASS], pass);
+}
+// the lengths column of the piece's records: pos = the exclusive scan of cnt, which is where k_paf_emit_chain puts line i's record (lens: the place of the piece's first)
+__global__ __launch_bounds__(256) void k_stream_lens(PafCols o, uint32_t L, const uint32_t *__restrict__ cnt, const uint32_t *__restrict__ pos, uint2 *__restrict__ lens)
+{
+	for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < L; i += gridDim.x * 256u) {
+		const uint32_t n = cnt[i];
+		if (!n) continue;
+		const uint32_t ql = o.ql[i], tl = o.tl[i];
+		lens[pos[i]] = make_uint2(ql, tl);
+		if (n == 2) lens[pos[i] + 1u] = make_uint2(tl, ql);
+	}
+}
+// At the end.  A record dies when either of its ids is flagged (both records of a -b line carry the same two ids: they die together).  A surviving record r
+// brings its two names' first appearance down to 2r (query) and 2r + 1 (target): records are in line order and a mirror sits behind its twin, so the order of
+// these minima is the order of first appearance among the surviving lines (hit.c:86-90).  alive[r] = 1 / 0; counted: surviving records, and of them self hits
+// (one record per line even with bi_dir: what the line count is made of).
+__global__ __launch_bounds__(256) void k_stream_mark(const uint4 *__restrict__ rec, size_t n_rec, const uint8_t *__restrict__ excl, unsigned long long *__restrict__ first,
+                                                      uint32_t *__restrict__ alive, unsigned long long *__restrict__ ctr)
+{
+	uint32_t n_alive = 0, n_self = 0;
+	for (size_t r = (size_t)blockIdx.x * 256u + threadIdx.x; r < n_rec; r += (size_t)gridDim.x * 256u) {
+		const uint4 a = rec[2 * r];
+		const uint32_t q = a.y, t = a.w, ok = !(excl[q] || excl[t]);
+		alive[r] = ok;
+		if (!ok) continue;
+		atomicMin(&first[q], (unsigned long long)(2 * r)); atomicMin(&first[t], (unsigned long long)(2 * r + 1));
+		++n_alive; n_self += q == t;
+	}
+	blk_add_u64(&ctr[PC_PASS], n_alive);
+	blk_add_u64(&ctr[PC_VALID], n_self);
+}
+__global__ __launch_bounds__(256) void k_stream_id_flag(const unsigned long long *__restrict__ first, uint32_t n_seq, uint32_t *__restrict__ keep)
+{
+	const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+	if (g < n_seq) keep[g] = first[g] != PAF_EMPTY;
+}
+__global__ __launch_bounds__(256) void k_stream_id_collect(const uint32_t *__restrict__ keep, const uint32_t *__restrict__ pos, const unsigned long long *__restrict__ first, uint32_t n_seq,
+                                                            uint64_t *__restrict__ key, uint32_t *__restrict__ val)
+{
+	const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+	if (g < n_seq && keep[g]) { key[pos[g]] = first[g]; val[pos[g]] = g; }
+}
+// the survivors sorted by first appearance: rank = the new id (sdict.c:27-45).  Its first-seen length is the one of that appearance (the lengths column), which
+// is what k_dict_assign takes in a whole parse; blen[j] = its bytes in the new arena
+__global__ __launch_bounds__(256) void k_stream_id_assign(const uint64_t *__restrict__ key, const uint32_t *__restrict__ val, uint32_t R, const uint32_t *__restrict__ old_len,
+                                                           const uint2 *__restrict__ lens, uint32_t *__restrict__ new_id, uint32_t *__restrict__ name_len, uint32_t *__restrict__ seq_len,
+                                                           uint32_t *__restrict__ blen)
+{
+	const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+	if (j >= R) return;
+	const uint32_t g = val[j], len = old_len[g];
+	const uint64_t occ = key[j];
+	const uint2 l = lens[occ >> 1];
+	new_id[g] = j;
+	name_len[j] = len;
+	seq_len[j] = occ & 1 ? l.y : l.x;
+	blen[j] = len + 1u;
+}
+__global__ __launch_bounds__(256) void k_stream_names(const unsigned char *__restrict__ arena, const uint32_t *__restrict__ old_pos, const uint32_t *__restrict__ val,
+                                                       const uint32_t *__restrict__ name_pos, const uint32_t *__restrict__ name_len, uint32_t R, unsigned char *__restrict__ out)
+{
+	const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+	if (j >= R) return;
+	const unsigned char *s = arena + old_pos[val[j]];
+	unsigned char *d = out + name_pos[j];
+	const uint32_t len = name_len[j];
+	for (uint32_t k = 0; k < len; ++k) d[k] = s[k];
+	d[len] = 0;
+}
+// the surviving records, in order, with both ids relabelled (pos: the exclusive scan of alive, in the same array; a survivor's ids have a new id)
+__global__ __launch_bounds__(256) void k_stream_compact(const uint4 *__restrict__ rec, size_t n_rec, const uint8_t *__restrict__ excl, const uint32_t *__restrict__ pos,
+                                                         const uint32_t *__restrict__ new_id, uint4 *__restrict__ out)
+{
+	for (size_t r = (size_t)blockIdx.x * 256u + threadIdx.x; r < n_rec; r += (size_t)gridDim.x * 256u) {
+		uint4 a = rec[2 * r];
+		if (excl[a.y] || excl[a.w]) continue;
+		a.y = new_id[a.y]; a.w = new_id[a.w];
+		out[2 * (size_t)pos[r]] = a;
+		out[2 * (size_t)pos[r] + 1] = rec[2 * r + 1];
+	}
+}
+
 // a persistent buffer that must hold `need` bytes and keep its first `used`: a new one (at least twice the old) and a device-to-device copy
 static int stream_grow(mahip_ctx *c, DevBuf &b, size_t used, size_t need, int *grown = nullptr)
 {
@@ -1643,6 +1759,13 @@ static int paf_stream_fold(mahip_ctx *c, PafBufs *b, PafStream *st, PafParse &ps
 	CHK(stream_grow(c, st->arena, st->arena_bytes, st->arena_bytes + tot[1] + 16, &grew_arena));
 	CHK(stream_grow(c, st->seq_len, ids * 4, (ids_new + 4) * 4, &grew_ids)); CHK(stream_grow(c, st->name_pos, ids * 4, (ids_new + 4) * 4, &grew_ids)); CHK(stream_grow(c, st->name_len, ids * 4, (ids_new + 4) * 4, &grew_ids));
 	sr.n_arena_grow += grew_arena; sr.n_ids_grow += grew_ids;
+	if (st->no_cont) { // the flags grow with the per-id arrays: the flags so far are copied, the bytes behind them start as 0
+		const void *was = st->excl.p;
+		int grew_flags = 0;
+		CHK(stream_grow(c, st->excl, ids, ids_new + 16, &grew_flags));
+		if (st->excl.p != was) HIPCHK(hipMemsetAsync((char*)st->excl.p + ids, 0, st->excl.cap - ids, c->st));
+		st->xrep.n_flag_grow += grew_flags;
+	}
 	hipLaunchKernelGGL(k_stream_commit, dim3(grid_for(R, 256)), dim3(256), 0, c->st, lnames, lpos, llen, lseq, R, (const uint32_t*)is_new, (const uint32_t*)pos, (const uint32_t*)bpos, (const uint32_t*)slot_of,
 	                   st->n_seq, (uint32_t)st->arena_bytes, P<unsigned long long>(st->tab), P<unsigned char>(st->arena), P<uint32_t>(st->name_pos), P<uint32_t>(st->name_len), P<uint32_t>(st->seq_len), l2g);
 	CHK(dev_reserve(c, st->map, (size_t)ps.cap_used * 4 + 16));
@@ -1666,6 +1789,11 @@ static PafStream *stream_of(mahip_ctx *c, const char *who, bool must_be_active)
 
 extern "C" int mahip_paf_stream_begin(mahip_ctx_t *c, int min_span, int min_match, int bi_dir)
 {
+	return mahip_paf_stream_begin_excl(c, min_span, min_match, bi_dir, 0, 0, 0.f);
+}
+
+extern "C" int mahip_paf_stream_begin_excl(mahip_ctx_t *c, int min_span, int min_match, int bi_dir, int no_cont, int max_hang, float int_frac)
+{
 	HIPCHK(hipSetDevice(c->dev));
 	if (mahip_comm_active(c)) { mahip_set_error("mahip_paf_stream_begin: a context with a communicator parses ranges (mahip_paf_parse_sharded), not a stream"); return -1; }
 	PafBufs *b = paf_of(c);
@@ -1673,6 +1801,10 @@ extern "C" int mahip_paf_stream_begin(mahip_ctx_t *c, int min_span, int min_matc
 	paf_stream_free(c, b);
 	PafStream *st = b->stream = new PafStream();
 	st->active = true; st->min_span = min_span; st->min_match = min_match; st->bi_dir = bi_dir != 0;
+	if (no_cont) {
+		st->no_cont = 1; st->max_hang = max_hang; st->int_frac = int_frac;
+		if (const char *e = getenv("MA_STREAM_NOCONT_EARLY")) st->early = atoi(e) != 0; // tests: 0 = every line waits for the end of the stream (the same result)
+	}
 	b->n_seq = 0; b->name_bytes = 0; b->loaded = false;
 	b->parsed = false; b->rep = {}; b->odd_snap.clear();
 	return 0;
@@ -1727,22 +1859,46 @@ extern "C" int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size
 		const double f0 = stream_now();
 		CHK(paf_stream_fold(c, b, st, ps));
 		t_fold = stream_now() - f0;
+		uint32_t *cnt = nullptr, *cpos = nullptr;
+		if (st->no_cont) { // hit.c:38-68 on the piece's stored lines, then the lines that touch a flagged name go (k_stream_verdict)
+			const uint32_t L = ps.L;
+			CHK(dev_reserve(c, c->keep, ((size_t)L + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)L + 16) * 4));
+			cnt = P<uint32_t>(c->keep); cpos = P<uint32_t>(c->pos);
+			hipLaunchKernelGGL(k_stream_verdict, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, ps.o, L, ps.slot_to_id, st->max_hang, st->int_frac, P<uint8_t>(st->excl));
+			CHK(ctr_zero(c));
+			hipLaunchKernelGGL(k_stream_early, dim3(grid_for(L, 256, 8192)), dim3(256), 0, c->st, ps.o, L, ps.slot_to_id, (const uint8_t*)P<uint8_t>(st->excl), st->early, st->bi_dir, cnt,
+			                   P<unsigned long long>(c->ctr));
+			CHK(ctr_fetch(c));
+			st->xrep.n_early_lines += ps.n_pass - (size_t)c->h_ctr[PC_PASS];
+			ps.n_pass = (size_t)c->h_ctr[PC_PASS];
+		}
 		const size_t max_hits = st->bi_dir ? 2 * ps.n_pass : ps.n_pass;
 		if (st->n_rec + max_hits >= 0xffffffffull) { mahip_set_error("mahip_paf_parse: more than 2^32 records"); return -1; }
 		if (st->rec_cap == 0) { // the first capacity
 			st->rec_cap = (size_t)1 << 20;
 			if (const char *e = getenv("MA_STREAM_REC_CAP")) { const long long v = atoll(e); if (v >= 1) st->rec_cap = (size_t)v; }
 			CHK(dev_reserve(c, st->rec, (st->rec_cap + 1) * sizeof(ma_hit_t)));
+			if (st->no_cont) CHK(dev_reserve(c, st->lens, (st->rec_cap + 1) * sizeof(uint2)));
 		}
 		if (st->n_rec + max_hits > st->rec_cap) {
 			size_t want = 2 * st->rec_cap;
 			if (want < st->n_rec + max_hits) want = st->n_rec + max_hits;
 			CHK(stream_grow(c, st->rec, st->n_rec * sizeof(ma_hit_t), (want + 1) * sizeof(ma_hit_t)));
+			if (st->no_cont) { // the lengths column grows with the record buffer
+				int grew_lens = 0;
+				CHK(stream_grow(c, st->lens, st->n_rec * sizeof(uint2), (want + 1) * sizeof(uint2), &grew_lens));
+				st->xrep.n_lens_grow += grew_lens;
+			}
 			st->rec_cap = want;
 			++sr.n_rec_grow;
 		}
-		CHK(paf_records(c, b, ps, st->bi_dir, (ma_hit_t*)st->rec.p + st->n_rec));
+		if (st->no_cont && ps.n_pass) { // (the piece's records take [n_rec, n_rec + the scanned total), and that total is at most max_hits)
+			CHK(scan_exclusive_u32(c, cnt, cpos, ps.L, P<uint32_t>(b->scal) + 1));
+			hipLaunchKernelGGL(k_stream_lens, dim3(grid_for(ps.L, 256, 8192)), dim3(256), 0, c->st, ps.o, ps.L, (const uint32_t*)cnt, (const uint32_t*)cpos, (uint2*)st->lens.p + st->n_rec);
+		}
+		if (ps.n_pass) CHK(paf_records(c, b, ps, st->bi_dir, (ma_hit_t*)st->rec.p + st->n_rec));
 		st->n_rec += ps.n_hits;
+		if (st->n_rec > st->xrep.peak_records) st->xrep.peak_records = st->n_rec;
 	}
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipStreamSynchronize(c->st));
@@ -1758,6 +1914,72 @@ extern "C" int mahip_paf_stream_piece_mem(mahip_ctx_t *c, const void *text, size
 	return 0;
 }
 
+// -R at the end of the stream: what the flags of all pieces leave of the records and of the dictionary, renumbered by first appearance among the surviving
+// lines (hit.c:86-90: the second pass hands out ids only for lines that pass).  Replaces st->rec, st->arena and the per-id arrays; sets the totals.
+static int paf_stream_retire(mahip_ctx *c, PafBufs *b, PafStream *st, uint32_t *n_excl)
+{
+	mahip_paf_stream_excl_report_t &xr = st->xrep;
+	unsigned long long *ctr = P<unsigned long long>(c->ctr);
+	const size_t n_rec = st->n_rec;
+	const uint32_t n_seq = st->n_seq;
+	*n_excl = 0;
+	if (n_seq == 0) return 0; // no line was ever stored: no name, no flag, no record
+	const uint8_t *excl = (const uint8_t*)P<uint8_t>(st->excl);
+	CHK(ctr_zero(c));
+	hipLaunchKernelGGL(k_excl_count, dim3(grid_for(n_seq, 256, 2048)), dim3(256), 0, c->st, excl, n_seq, ctr);
+	CHK(ctr_fetch(c));
+	xr.n_flagged = *n_excl = (uint32_t)c->h_ctr[PC_VALID];
+	// ---- dead records; the first surviving appearance of every id
+	ScopedDev first(c), alive(c), new_id(c);
+	CHK(dev_reserve(c, first.b, ((size_t)n_seq + 2) * 8)); CHK(dev_reserve(c, alive.b, (n_rec + 16) * 4)); CHK(dev_reserve(c, new_id.b, ((size_t)n_seq + 4) * 4));
+	HIPCHK(hipMemsetAsync(first.b.p, 0xff, (size_t)n_seq * 8, c->st));
+	CHK(ctr_zero(c));
+	if (n_rec) hipLaunchKernelGGL(k_stream_mark, dim3(grid_for(n_rec, 256, 8192)), dim3(256), 0, c->st, (const uint4*)st->rec.p, n_rec, excl, (unsigned long long*)first.b.p, (uint32_t*)alive.b.p, ctr);
+	CHK(ctr_fetch(c));
+	const size_t n_alive = (size_t)c->h_ctr[PC_PASS], n_self = (size_t)c->h_ctr[PC_VALID];
+	const size_t lines_alive = st->bi_dir ? (n_alive - n_self) / 2 + n_self : n_alive; // hit.c:87-98: two records a line, one for a self hit
+	xr.n_late_records = n_rec - n_alive; xr.n_late_lines = st->n_pass - lines_alive;
+	// ---- the survivors' new ids: the ranks of their first appearances
+	uint32_t R = 0, nb = 0, n_keep = 0;
+	CHK(dev_reserve(c, c->keep, ((size_t)n_seq + 16) * 4)); CHK(dev_reserve(c, c->pos, ((size_t)n_seq + 16) * 4));
+	hipLaunchKernelGGL(k_stream_id_flag, dim3(grid_for(n_seq, 256)), dim3(256), 0, c->st, (const unsigned long long*)first.b.p, n_seq, P<uint32_t>(c->keep));
+	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), n_seq, P<uint32_t>(b->scal)));
+	CHK(fetch_u32(c, b->scal.p, &R));
+	for (int k = 0; k < 2; ++k) { CHK(dev_reserve(c, c->key[k], ((size_t)R + 1) * 8)); CHK(dev_reserve(c, c->val[k], ((size_t)R + 1) * 4)); }
+	hipLaunchKernelGGL(k_stream_id_collect, dim3(grid_for(n_seq, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->keep), (const uint32_t*)P<uint32_t>(c->pos), (const unsigned long long*)first.b.p, n_seq,
+	                   P<uint64_t>(c->key[0]), P<uint32_t>(c->val[0]));
+	int gen = 0;
+	if (R) CHK(radix_sort_pairs(c, R, 0, bitlen_u64(2ull * n_rec), 0, 0, &gen));
+	// ---- the dictionary in new-id order: R <= n_seq names, their bytes (<= arena_bytes) out of the old arena
+	DevBuf arena2, pos2, len2, seq2, rec2;
+	auto give_up = [&]() { (void)hipStreamSynchronize(c->st); dev_free(c, arena2); dev_free(c, pos2); dev_free(c, len2); dev_free(c, seq2); dev_free(c, rec2); return -1; };
+#define CHK2(x) do { if ((x) != 0) return give_up(); } while (0)
+	CHK2(dev_reserve(c, pos2, ((size_t)R + 4) * 4)); CHK2(dev_reserve(c, len2, ((size_t)R + 4) * 4)); CHK2(dev_reserve(c, seq2, ((size_t)R + 4) * 4));
+	CHK2(dev_reserve(c, c->keep, ((size_t)R + 16) * 4));
+	if (R) hipLaunchKernelGGL(k_stream_id_assign, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint64_t*)P<uint64_t>(c->key[gen]), (const uint32_t*)P<uint32_t>(c->val[gen]), R,
+	                          (const uint32_t*)P<uint32_t>(st->name_len), (const uint2*)st->lens.p, (uint32_t*)new_id.b.p, (uint32_t*)len2.p, (uint32_t*)seq2.p, P<uint32_t>(c->keep));
+	CHK2(scan_exclusive_u32(c, P<uint32_t>(c->keep), (uint32_t*)pos2.p, R, P<uint32_t>(b->scal)));
+	CHK2(fetch_u32(c, b->scal.p, &nb));
+	CHK2(dev_reserve(c, arena2, (size_t)nb + 16));
+	if (R) hipLaunchKernelGGL(k_stream_names, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const unsigned char*)P<unsigned char>(st->arena), (const uint32_t*)P<uint32_t>(st->name_pos),
+	                          (const uint32_t*)P<uint32_t>(c->val[gen]), (const uint32_t*)pos2.p, (const uint32_t*)len2.p, R, (unsigned char*)arena2.p);
+	// ---- the surviving records, relabelled, into a second buffer (the lengths column has done its work: it goes first)
+	if (hipStreamSynchronize(c->st) != hipSuccess) return give_up();
+	dev_free(c, st->lens);
+	CHK2(scan_exclusive_u32(c, (const uint32_t*)alive.b.p, (uint32_t*)alive.b.p, n_rec, P<uint32_t>(b->scal)));
+	CHK2(fetch_u32(c, b->scal.p, &n_keep));
+	if (n_keep != n_alive) { mahip_set_error("mahip_paf_stream_end: %u records survive the scan, %zu the count", n_keep, n_alive); return give_up(); }
+	CHK2(dev_reserve(c, rec2, ((size_t)n_keep + 1) * sizeof(ma_hit_t)));
+	if (n_rec) hipLaunchKernelGGL(k_stream_compact, dim3(grid_for(n_rec, 256, 8192)), dim3(256), 0, c->st, (const uint4*)st->rec.p, n_rec, excl, (const uint32_t*)alive.b.p, (const uint32_t*)new_id.b.p, (uint4*)rec2.p);
+	{ hipError_t le = hipGetLastError(); if (le != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) { mahip_set_error("mahip_paf_stream_end: %s", hipGetErrorString(le)); return give_up(); } }
+#undef CHK2
+	dev_free(c, st->rec); dev_free(c, st->arena); dev_free(c, st->name_pos); dev_free(c, st->name_len); dev_free(c, st->seq_len);
+	st->rec = rec2; st->arena = arena2; st->name_pos = pos2; st->name_len = len2; st->seq_len = seq2;
+	st->n_rec = n_keep; st->n_seq = R; st->arena_bytes = nb; st->n_pass = lines_alive;
+	xr.n_renumbered = R;
+	return 0;
+}
+
 extern "C" int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info)
 {
 	HIPCHK(hipSetDevice(c->dev));
@@ -1766,11 +1988,13 @@ extern "C" int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info)
 	PafBufs *b = paf_of(c);
 	memset(info, 0, sizeof(*info));
 	HIPCHK(hipStreamSynchronize(c->st));
+	uint32_t n_excl = 0;
+	if (st->no_cont) CHK(paf_stream_retire(c, b, st, &n_excl));
 	// the dictionary and the records change hands: they are laid out as a whole parse leaves them
 	dev_free(c, b->names); dev_free(c, b->name_pos); dev_free(c, b->seq_len); dev_free(c, b->name_len); dev_free(c, c->aos_own);
 	b->names = st->arena; b->name_pos = st->name_pos; b->seq_len = st->seq_len; b->name_len = st->name_len; c->aos_own = st->rec;
 	st->arena = DevBuf(); st->name_pos = DevBuf(); st->seq_len = DevBuf(); st->name_len = DevBuf(); st->rec = DevBuf();
-	dev_free(c, st->tab); dev_free(c, st->fold); dev_free(c, st->map);
+	dev_free(c, st->tab); dev_free(c, st->fold); dev_free(c, st->map); dev_free(c, st->excl); dev_free(c, st->lens);
 	b->n_seq = st->n_seq; b->name_bytes = st->arena_bytes;
 	PafParse ps;
 	ps.n_hits = st->n_rec; ps.R = st->n_seq;
@@ -1782,6 +2006,7 @@ extern "C" int mahip_paf_stream_end(mahip_ctx_t *c, mahip_paf_info_t *info)
 	b->loaded = false;
 	info->n_records = st->n_valid; info->n_stored_lines = st->n_pass; info->n_hits = st->n_rec; info->n_seq = st->n_seq; info->max_qs = st->max_qs;
 	info->name_bytes = st->arena_bytes; info->n_lines = st->n_lines;
+	b->rep.n_excl = info->n_excl = n_excl;
 	st->active = false;
 	return 0;
 }
@@ -1802,6 +2027,14 @@ extern "C" int mahip_paf_stream_last(mahip_ctx_t *c, mahip_paf_stream_report_t *
 	PafStream *st = stream_of(c, "mahip_paf_stream_last", false);
 	if (!st) return -1;
 	if (out) *out = st->rep;
+	return 0;
+}
+
+extern "C" int mahip_paf_stream_excl_last(mahip_ctx_t *c, mahip_paf_stream_excl_report_t *out)
+{
+	PafStream *st = stream_of(c, "mahip_paf_stream_excl_last", false);
+	if (!st) return -1;
+	if (out) *out = st->xrep;
 	return 0;
 }
 

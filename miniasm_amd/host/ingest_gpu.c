@@ -4,8 +4,8 @@
  * HBM (mahip_paf_load_fd); a bgzip-compressed (BGZF) file goes to HBM as it is and is inflated there, one wave per block (mahip_bgzf_load_fd; the walk over
  * its member chain is below); a plain gzip file can be cut into chunks and inflated there too (MA_GZIP_DEVICE=1: mahip_gzip_load_fd; its header and trailer are
  * read below); otherwise gzip / stdin input is read by zlib (as the reference does through gzread) one PIECE of whole lines at a time, and piece k is uploaded
- * and parsed (mahip_paf_stream_piece_mem) while a second thread inflates piece k + 1 (ma_hit_ingest_stream below); MA_INGEST_STREAM=0, -R and ma_paf_load_file
- * inflate the whole text into memory first and upload it.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
+ * and parsed (mahip_paf_stream_piece_mem) while a second thread inflates piece k + 1 (ma_hit_ingest_stream below); MA_INGEST_STREAM=0, -R (unless
+ * MA_STREAM_NOCONT=1: ma_hit_ingest_stream_excl) and ma_paf_load_file inflate the whole text into memory first and upload it.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
  * first-appearance ids and the (mirrored) hit records are all produced by csrc/paf.hip; what comes back is the
  * dictionary (names + first-seen lengths, R entries) and, only for the per-symbol ABI, the records.
  * The -R pre-filter (ma_hit_no_cont, hit.c:38-68) rides in the same parse: the exclusion is a flag per name.
@@ -333,6 +333,12 @@ int ma_ingest_stream_mode(void)
 	const char *s = getenv("MA_INGEST_STREAM");
 	return s && *s ? (atoi(s) != 0) : MA_INGEST_STREAM_DEFAULT;
 }
+/* MA_STREAM_NOCONT: 1 = with -R, too, what reaches the ladder's last rung is streamed; off by default */
+int ma_stream_nocont(void)
+{
+	const char *s = getenv("MA_STREAM_NOCONT");
+	return s && *s && atoi(s) != 0;
+}
 /* MA_INGEST_PIECE: bytes of text per piece, clamped to [256, 1 GiB] */
 #define MA_INGEST_PIECE_DEFAULT ((size_t)16 << 20)
 size_t ma_ingest_piece(void)
@@ -465,16 +471,25 @@ void ma_stream_q_destroy(ma_stream_q_t *q)
  * after ma_hit_ingest_loaded; -2 = the device refused (the stream is aborted, the text stage released; fp has been read from).  fp stays open. */
 int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes)
 {
+	return ma_hit_ingest_stream_excl(c, fp, min_span, min_match, d, n_hits, bi_dir, piece_bytes, 0, 0, 0.f);
+}
+
+/* no_cont: -R in the same single pass (mahip_paf_stream_begin_excl: provisional ids, renumbered at the end); prints the reference's log lines of Step 0 first,
+ * as ma_hit_ingest_loaded_excl does */
+int ma_hit_ingest_stream_excl(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes, int no_cont, int max_hang, float int_frac)
+{
 	const int timing = ma_timing_level() >= 1;
 	const double t0 = sys_realtime();
 	ma_stream_q_t q;
 	mahip_paf_info_t info;
 	mahip_paf_stream_report_t sr;
+	mahip_paf_stream_excl_report_t xr;
 	int i = 0, bad = 0;
 	memset(&sr, 0, sizeof(sr));
+	memset(&xr, 0, sizeof(xr));
 	ma_stream_q_init(&q, fp, piece_bytes);
 	GPU(mahip_set_shard(c, 0, 0xffffffffu));
-	if (mahip_paf_stream_begin(c, min_span, min_match, bi_dir) != 0) bad = 1;
+	if (mahip_paf_stream_begin_excl(c, min_span, min_match, bi_dir, no_cont, max_hang, int_frac) != 0) bad = 1;
 	if (!bad && ma_stream_q_start(&q) != 0) { mahip_paf_stream_abort(c); ma_gpu_fail(__func__); }
 	for (; !bad; i ^= 1) {
 		int last;
@@ -486,6 +501,7 @@ int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match,
 	}
 	if (!bad && mahip_paf_stream_end(c, &info) != 0) bad = 1;
 	mahip_paf_stream_last(c, &sr);
+	mahip_paf_stream_excl_last(c, &xr);
 	ma_stream_q_destroy(&q);
 	if (bad) {
 		fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror());
@@ -496,6 +512,13 @@ int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match,
 	if (timing)
 		fprintf(stderr, "[T::ingest_gpu] stream: pieces=%lu piece=%lu B producer %.3f upload %.3f parse %.3f fold %.3f waited-for-input %.3f s\n", (unsigned long)sr.n_pieces,
 		        (unsigned long)piece_bytes, q.t_prod, sr.t_upload, sr.t_parse, sr.t_fold, q.t_wait);
+	if (timing && no_cont)
+		fprintf(stderr, "[T::ingest_gpu] stream: -R dropped early %lu lines, late %lu lines (%lu records); held %lu records at the peak, kept %lu\n", (unsigned long)xr.n_early_lines,
+		        (unsigned long)xr.n_late_lines, (unsigned long)xr.n_late_records, (unsigned long)xr.peak_records, (unsigned long)info.n_hits);
+	if (no_cont) {
+		if (ma_verbose >= 3) fprintf(MA_LOG, "[M::%s::%s] dropped %d contained reads\n", "ma_hit_no_cont", sys_timestamp(), info.n_excl);
+		fprintf(MA_LOG, "[M::%s] ===> Step 1: reading read mappings <===\n", "main");
+	}
 	ingest_dictionary(c, &info, d, n_hits, 1, t0);
 	return 0;
 }
@@ -515,9 +538,10 @@ int ma_hit_ingest_gpu_excl(mahip_ctx_t *c, const char *fn, int min_span, int min
 	{
 		gzFile fp = 0;
 		int seekable = 0;
-		int rc = paf_load_ladder(c, fn, !no_cont && mode != 0 && !mahip_comm_active(c) ? &fp : 0, &seekable, mode == 1); /* -R never streams: its exclusion needs every line before any id is given out; nor does a rank of several */
+		/* -R streams only under MA_STREAM_NOCONT=1 (the one-pass exclusion of mahip_paf_stream_begin_excl; measured in DESIGN 7, the default stays off); a rank of several never does */
+		int rc = paf_load_ladder(c, fn, (!no_cont || ma_stream_nocont()) && mode != 0 && !mahip_comm_active(c) ? &fp : 0, &seekable, mode == 1);
 		if (rc == 1) { /* the last rung, piece by piece */
-			rc = ma_hit_ingest_stream(c, fp, min_span, min_match, d, n_hits, bi_dir, ma_ingest_piece());
+			rc = ma_hit_ingest_stream_excl(c, fp, min_span, min_match, d, n_hits, bi_dir, ma_ingest_piece(), no_cont, max_hang, int_frac);
 			gzclose(fp);
 			if (rc == -2 && !seekable) {
 				fprintf(stderr, "[E::%s] the device refused a piece of the input (%s), and what was read of it cannot be read again\n", __func__, mahip_strerror());

@@ -79,6 +79,8 @@ int ma_paf_load_file(mahip_ctx_t *c, const char *fn); /* plain / gzip / "-": tex
 /* the streamed road (ingest_gpu.c): the text behind an open gzFile (plain or gzip; a file, stdin or a pipe) in pieces of about piece_bytes of whole lines, piece k
  * uploaded and parsed while a second thread inflates piece k + 1; 0 = records in the context and d filled, as ma_hit_ingest_loaded leaves them; -2 = the device refused */
 int ma_hit_ingest_stream(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes);
+int ma_hit_ingest_stream_excl(mahip_ctx_t *c, gzFile fp, int min_span, int min_match, sdict_t *d, size_t *n_hits, int bi_dir, size_t piece_bytes, int no_cont, int max_hang, float int_frac); /* the same with -R (no_cont) */
+int ma_stream_nocont(void);      /* MA_STREAM_NOCONT: 1 = -R input that reaches zlib on the host is streamed too; off by default */
 int ma_ingest_stream_mode(void); /* MA_INGEST_STREAM: 0 off, 1 every input, -1 (unset) what reaches zlib on the host */
 size_t ma_ingest_piece(void);    /* MA_INGEST_PIECE or the default, clamped to [256, 1 GiB] */
 /* the cut-and-carry reader of that road, on its own (tests/stream_cut_main.c): pieces of whole lines from a byte source */

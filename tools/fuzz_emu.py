@@ -4,7 +4,9 @@ command-line options, the unmodified reference binary (oracle/_ref/miniasm_ref) 
 (tests/emu/_build/miniasm), every dump format, bytes compared.  Test tooling: `python tools/fuzz_emu.py --cases 200 --seed 1`.
 With --ranks the same case is also run as MA_GPUS=N over the shared-memory double.  With --stream the case's text also goes through the streamed ingest: cut at
 random line borders into pieces (empty and single-line pieces included) through mahip_paf_stream_* of the CPU build, compared with the whole parse, the host reader
-and the reference library; and through the command line with MA_INGEST_STREAM=1 and a random MA_INGEST_PIECE, compared with the reference binary."""
+and the reference library; and through the command line with MA_INGEST_STREAM=1 and a random MA_INGEST_PIECE, compared with the reference binary.  Each such case
+also runs with -R: the same pieces through mahip_paf_stream_begin_excl with the case's (max_hang, int_frac) (the comparison is
+tests/test_gpu_ingest_stream_excl.py's), and the command line with -R added under MA_STREAM_NOCONT=1."""
 import argparse
 import gzip
 import hashlib
@@ -215,9 +217,21 @@ def write_gzip(rng, data, path):
 _stream = None
 
 
-def stream_case(rng, data, tmp):
+def no_cont_of(args):
+    """(max_hang, int_frac) of a command line: -h and -I, or the defaults of ma_opt_init"""
+    mh, fr = 1000, 0.8
+    for k, x in enumerate(args[:-1]):
+        if x == "-h":
+            mh = int(args[k + 1])
+        elif x == "-I":
+            fr = float(args[k + 1])
+    return mh, fr
+
+
+def stream_case(rng, data, tmp, no_cont):
     """the text cut at random line borders -> the streamed ingest of the CPU build against the whole parse, the host reader and the reference library (the
-    comparison is tests/test_gpu_ingest_stream.py's); an AssertionError says what differs"""
+    comparison is tests/test_gpu_ingest_stream.py's), and the same pieces with -R, no_cont = (max_hang, int_frac) (tests/test_gpu_ingest_stream_excl.py's: the
+    model too); an AssertionError says what differs"""
     global _stream
     if _stream is None:
         os.environ["MA_EMU_BUILD"] = os.path.basename(os.path.dirname(EMU))
@@ -226,8 +240,9 @@ def stream_case(rng, data, tmp):
         import emu_plugin  # noqa: F401  (points the ctypes harness at the CPU build)
         import miniasm_amd as ma
         import test_gpu_ingest_stream as T
-        _stream = (T, ma.Ctx(0))
-    T, ctx = _stream
+        import test_gpu_ingest_stream_excl as X
+        _stream = (T, X, ma.Ctx(0))
+    T, X, ctx = _stream
     lines = data.splitlines(keepends=True)
     how = rng.choice(["few", "many", "single", "one"])
     lines = lines[:300 if how == "single" else 3000]  # (the CPU build takes a piece in tens of milliseconds)
@@ -246,6 +261,10 @@ def stream_case(rng, data, tmp):
     if rng.random() < 0.4:
         env["MA_STREAM_REC_CAP"] = rng.choice([1, 8, 1000])
     T.check(ctx, tmp, pieces, ms, mm, rng.randint(0, 1), **env)
+    if rng.random() < 0.3:
+        env["MA_STREAM_NOCONT_EARLY"] = 0
+    if not lines or lines[0].count(b"\t") != 9:  # (what a 10-column FIRST line holds as bl is left open by paf.c:54; with -R the reference's second pass finds what the first left)
+        X.check(ctx, tmp, pieces, ms, mm, rng.randint(0, 1), no_cont, **env)
     return len(pieces)
 
 
@@ -297,7 +316,7 @@ def main():
             if rng.random() < 0.5 and not a.text:
                 open(paf, "wb").write(mutate_text(rng, open(paf, "rb").read()))
             try:
-                n_pieces_cut += stream_case(rng, open(paf, "rb").read(), tmp)
+                n_pieces_cut += stream_case(rng, open(paf, "rb").read(), tmp, no_cont_of(args))
             except AssertionError as e:
                 bad += 1
                 print("case %d MISMATCH [stream, cut at line borders]: pafgen %s: %s" % (k, " ".join(gen), str(e)[:300]))
@@ -318,10 +337,19 @@ def main():
             runs.append(("emu host reader", {"MA_FASTX_HOST": "1"}))
         if a.ranks > 1:  # requests the sharded head does not serve fall back to one GPU: the bytes must be the same either way
             runs.append(("emu x%d" % a.ranks, {"MA_GPUS": str(a.ranks), "MA_COMM": "shm"}))
+        if a.stream:  # (last: it compares with its own run of the reference)
+            runs.append(("emu stream -R", {"MA_INGEST_STREAM": "1", "MA_STREAM_NOCONT": "1", "MA_INGEST_PIECE": str(max(256, os.path.getsize(paf) // rng.choice([1, 2, 7, 40, 200]))), "ADD_R": "1"}))
         for name, env in runs:
             env = dict(env, MA_PIPE_TIMING="1")  # the [T::ties] line: which tie path the run took
             env.update(kv.split("=", 1) for kv in a.env)
-            rc1, out1, err1 = run(EMU, args, env.pop("FILE", paf), env)
+            if env.pop("ADD_R", None):  # the case's command line with -R: its own run of the reference
+                args1 = args if "-R" in args else ["-R"] + args
+                rc0, out0, err0 = run(REF, args1, paf)
+                if rc0 < 0:
+                    continue
+            else:
+                args1 = args
+            rc1, out1, err1 = run(EMU, args1, env.pop("FILE", paf), env)
             for ln in err1.decode(errors="replace").splitlines():
                 if ln.startswith("[T::gzip]"):
                     mm = re.search(r"reader=(\w+) reason=\d+ \(([^)]*)\)", ln)
@@ -342,7 +370,7 @@ def main():
             if not ok:
                 bad += 1
                 print("case %d MISMATCH [%s]: pafgen %s | miniasm %s | rc %d vs %d, %d vs %d bytes, md5 %s vs %s" % (
-                    k, name, " ".join(gen), " ".join(args), rc0, rc1, len(out0), len(out1), hashlib.md5(out0).hexdigest()[:8], hashlib.md5(out1).hexdigest()[:8]))
+                    k, name, " ".join(gen), " ".join(args1), rc0, rc1, len(out0), len(out1), hashlib.md5(out0).hexdigest()[:8], hashlib.md5(out1).hexdigest()[:8]))
                 print("   emu stderr tail:", err1[-300:].decode(errors="replace").replace("\n", " | "))
                 if a.keep:
                     os.makedirs(a.keep, exist_ok=True)

@@ -9,6 +9,10 @@ the script.  Result: one JSON line, also written to --out.
 The two yardsticks: wall at the chosen piece size <= 1.05 x the parent's (the +- 5 % box spread README.md states), and on the 100 M-line file max RSS
 below the parent's by at least half of the file's text size.
 
+--no-cont: the same for `miniasm -R x.paf.gz` (the .gz file only; -R on stdin is the host reader's).  The input gets a length spread (pafgen -d 0.1), and every
+run must report `dropped N contained reads` with N > 0.  The parent's -R inflates the whole text first; this build runs under MA_STREAM_NOCONT=1.  From
+[T::ingest_gpu] stream: -R ... the early and late drops and the records held at the peak against the records kept are recorded: what the single pass costs in HBM.
+
   python tools/stream_time.py --parent ../parent/miniasm_amd/bin/miniasm --lines 10000000 --out profiles/stream_time_10M.json"""
 import argparse
 import json
@@ -52,6 +56,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--pieces", default="16,64,256,1024", help="MA_INGEST_PIECE values, MiB")
     ap.add_argument("--kinds", default="gz,stdin", help="gz: the .gz file by name; stdin: the plain text on stdin")
+    ap.add_argument("--no-cont", action="store_true", help="time `miniasm -R x.paf.gz` under MA_STREAM_NOCONT=1 against the parent's -R (kind gz only)")
     ap.add_argument("--miniasm", default=os.path.join(BIN, "miniasm"), help="the binary under test")
     ap.add_argument("--limit", type=int, default=600, help="seconds per run")
     ap.add_argument("--tmp", default="/tmp")
@@ -60,19 +65,22 @@ def main():
     paf = os.path.join(a.tmp, "stream_time_%d.paf" % os.getpid())
     gz = paf + ".gz"
     pieces = [int(x) for x in a.pieces.split(",") if x]
+    opts = ["-R"] if a.no_cont else []
+    own = {"MA_STREAM_NOCONT": "1"} if a.no_cont else {}
+    kinds = ["gz"] if a.no_cont else a.kinds.split(",")
     try:
-        subprocess.run([os.path.join(BIN, "pafgen"), "-r", str(a.reads), "-n", str(a.lines), "-s", "4", "-o", paf], check=True, stderr=subprocess.DEVNULL)
+        subprocess.run([os.path.join(BIN, "pafgen"), "-r", str(a.reads), "-n", str(a.lines), "-s", "4", "-o", paf] + (["-d", "0.1"] if a.no_cont else []), check=True, stderr=subprocess.DEVNULL)
         with open(gz, "wb") as g:
             subprocess.run(["gzip", "-1", "-c", paf], check=True, stdout=g)
-        res = {"lines": a.lines, "reps": a.reps, "bytes": {"plain": os.path.getsize(paf), "gzip": os.path.getsize(gz)}, "kinds": {}}
+        res = {"no_cont": bool(a.no_cont), "lines": a.lines, "reps": a.reps, "bytes": {"plain": os.path.getsize(paf), "gzip": os.path.getsize(gz)}, "kinds": {}}
         print("input ready: %d bytes of text, %d compressed" % (res["bytes"]["plain"], res["bytes"]["gzip"]), flush=True)
-        for kind in a.kinds.split(","):
-            settings = [("parent", a.parent, {})] + [("piece_%dMiB" % p, a.miniasm, {"MA_INGEST_PIECE": str(p << 20)}) for p in pieces]
-            runs = {name: {"wall_s": [], "maxrss_kib": [], "laps_s": [], "pieces": []} for name, _, _ in settings}
+        for kind in kinds:
+            settings = [("parent", a.parent, {})] + [("piece_%dMiB" % p, a.miniasm, dict(own, MA_INGEST_PIECE=str(p << 20))) for p in pieces]
+            runs = {name: {"wall_s": [], "maxrss_kib": [], "laps_s": [], "pieces": [], "excl": []} for name, _, _ in settings}
             crcs = set()
             for rep in range(a.reps):
                 for name, binary, env in settings:
-                    cmd, stdin_path = ([binary, gz], None) if kind == "gz" else ([binary, "-"], paf)
+                    cmd, stdin_path = ([binary] + opts + [gz], None) if kind == "gz" else ([binary] + opts + ["-"], paf)
                     dt, log, crc, rss = timed(cmd, env, stdin_path, a.limit)
                     crcs.add(crc)
                     runs[name]["wall_s"].append(round(dt, 4))
@@ -83,6 +91,15 @@ def main():
                             sys.exit("no [T::ingest_gpu] stream line:\n" + log[-2000:])
                         runs[name]["pieces"].append(int(m.group(1)))
                         runs[name]["laps_s"].append(dict(zip(LAPS, (float(x) for x in m.groups()[1:]))))
+                    if a.no_cont:
+                        d = re.search(r"dropped (\d+) contained reads", log)
+                        if not d or int(d.group(1)) == 0:
+                            sys.exit("the input does not trigger the -R pre-filter:\n" + log[-2000:])
+                        x = re.search(r"\[T::ingest_gpu\] stream: -R dropped early (\d+) lines, late (\d+) lines \((\d+) records\); held (\d+) records at the peak, kept (\d+)", log)
+                        if name != "parent":
+                            if not x:
+                                sys.exit("no [T::ingest_gpu] stream: -R line:\n" + log[-2000:])
+                            runs[name]["excl"].append(dict(zip(("dropped_reads", "early_lines", "late_lines", "late_records", "peak_records", "kept_records"), [int(d.group(1))] + [int(v) for v in x.groups()])))
                     print("%s rep %d %s: %.2f s, max RSS %.0f MiB" % (kind, rep, name, dt, rss / 1024.0), flush=True)
             for name in runs:
                 runs[name]["wall_median_s"] = round(statistics.median(runs[name]["wall_s"]), 4)
