@@ -23,7 +23,7 @@ HOST_OBJ  = $(addprefix $(B)/,$(addsuffix .o,$(HOST_SRC)))
 
 LIB       = $(PKG)/lib/libminiasm_amd.so
 BIN       = $(PKG)/bin/miniasm $(PKG)/bin/pafgen $(PKG)/bin/readgen
-CORE_TEST = $(PKG)/lib/libma_core_host.so $(PKG)/lib/libclean_host.so
+CORE_TEST = $(PKG)/lib/libma_core_host.so $(PKG)/lib/libclean_host.so $(PKG)/lib/libtext_core_host.so
 
 .PHONY: all lib oracle dropin clean
 all: lib $(BIN) $(CORE_TEST) oracle dropin
@@ -33,7 +33,7 @@ lib: $(LIB)
 $(B) $(PKG)/lib $(PKG)/bin:
 	mkdir -p $@
 
-$(B)/%.hip.o: $(CSRC)/%.hip $(CSRC)/mahip_internal.hpp $(CSRC)/ma_core.h $(CSRC)/clean_core.h $(CSRC)/ug_core.h $(CSRC)/inflate_core.h $(CSRC)/gzip_core.h include/mahip.h include/miniasm_amd.h | $(B)
+$(B)/%.hip.o: $(CSRC)/%.hip $(CSRC)/mahip_internal.hpp $(CSRC)/ma_core.h $(CSRC)/clean_core.h $(CSRC)/ug_core.h $(CSRC)/inflate_core.h $(CSRC)/gzip_core.h $(CSRC)/text_core.h $(CSRC)/text_dev.hpp include/mahip.h include/miniasm_amd.h | $(B)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(B)/%.o: $(HOST)/%.c $(HOST)/ma_host.h $(HOST)/refsort_body.h include/mahip.h include/miniasm_amd.h | $(B)
@@ -59,6 +59,10 @@ $(PKG)/lib/libma_core_host.so: tests/core_host.c $(CSRC)/ma_core.h | $(PKG)/lib
 # clean_core.h / ug_core.h compiled for the host: the cleaners' fixpoint and the unitig construction run on the CPU in the tests
 $(PKG)/lib/libclean_host.so: tests/clean_host.cpp $(CSRC)/clean_core.h $(CSRC)/ug_core.h | $(PKG)/lib
 	g++ -O2 -g -Wall -fPIC -shared -std=c++17 -I$(CSRC) -o $@ tests/clean_host.cpp
+
+# text_core.h compiled for the host: the dump lines' length pass and write pass run on the CPU in the tests
+$(PKG)/lib/libtext_core_host.so: tests/text_core_host.c $(CSRC)/text_core.h | $(PKG)/lib
+	$(CC) -O2 -g -Wall -fPIC -shared -I$(CSRC) -o $@ tests/text_core_host.c
 
 oracle:
 	$(MAKE) -C oracle all

@@ -628,6 +628,48 @@ int mahip_comm_all_gather_u64(mahip_ctx_t *c, const uint64_t *h_vals, size_t n, 
 int mahip_comm_barrier(mahip_ctx_t *c);
 int mahip_xbuf(mahip_ctx_t *c, int slot, size_t bytes, void **d_ptr);                                  /* exchange buffers (slot 0 / 1) */
 
+/* ---- text of the record dumps (-p paf, -p sg, -p bed) written on the device (csrc/text_dev.hpp over csrc/text_core.h) ---- */
+/* A length per record, the device-wide scan, one byte string per record, in slabs of records; every slab's text goes to the host and to a sink.
+ * Byte for byte what the host formatters (host/pipeline.c: print_hits, print_subs; host/unitig_gfa.c: ma_sg_print) and the reference write. */
+#define MAHIP_TEXT_PAF 1
+#define MAHIP_TEXT_SG  2
+#define MAHIP_TEXT_BED 3
+#define MAHIP_TEXT_ROAD_HOST   1   /* nothing was written: the caller formats on the host */
+#define MAHIP_TEXT_ROAD_DEVICE 2
+#define MAHIP_TEXT_OK        0
+#define MAHIP_TEXT_SWITCHED_OFF 1  /* MA_TEXT_DEVICE is 0 or unset (the default is the host formatter: DESIGN section 7 has the measurement behind it) */
+#define MAHIP_TEXT_NOMEM     2     /* a device or host buffer could not be had */
+#define MAHIP_TEXT_NO_NAMES  3     /* mahip_text_names has not described the reads the records name */
+typedef struct {
+	int kind, road, reason;
+	uint64_t n_records;      /* hits, arcs or reads looked at */
+	uint64_t n_lines;        /* lines written (a bed dump skips reads) */
+	uint64_t text_bytes;
+	uint64_t n_slabs, slab_records;
+	uint64_t max_name;       /* longest name of the dictionary, bytes */
+	uint64_t n_slow_lines;   /* lines of waves whose 64 lines did not fit the LDS tile: written byte by byte straight to device memory */
+	double laps_ms[4];       /* names upload, export of the records, format (lengths + scan + write kernels), copy to the host + sink */
+} mahip_text_info_t;
+/* 0 = ok; anything else ends the dump and becomes its return value */
+typedef int (*mahip_text_sink_t)(void *arg, const char *text, size_t n);
+/* the dictionary the records' ids index: n_seq names back to back in blob, name i = blob[off[i] .. off[i + 1]); del (optional): one byte per read, non-zero =
+ * the bed dump skips it.  Copied to the device; stays until the next call. */
+int mahip_text_names(mahip_ctx_t *c, const char *blob, const uint64_t *off, uint32_t n_seq, const uint8_t *del);
+/* The dump in two steps.  prepare: records exported on the device (hits in the order of a hit dump, arcs of the cleaned graph, both in the squeezed numbering when
+ * a squeeze map is pending; kept intervals of slot 0), every line's length, every buffer.  It decides the road, all or nothing, before a byte is written:
+ * returns 0 with info->road = DEVICE, or 0 with road = HOST and a reason (nothing happened; the caller formats on the host), or -1 (error).
+ * emit: the slabs' bytes to the sink.  The context must not be used for anything else in between.  dump = prepare + emit. */
+int mahip_text_prepare(mahip_ctx_t *c, int kind, int have_sub, mahip_text_info_t *info);
+int mahip_text_emit(mahip_ctx_t *c, mahip_text_sink_t sink, void *arg, mahip_text_info_t *info);
+int mahip_text_dump(mahip_ctx_t *c, int kind, int have_sub, mahip_text_sink_t sink, void *arg, mahip_text_info_t *info);
+int mahip_text_last(mahip_ctx_t *c, mahip_text_info_t *info);
+/* stage entry (tests): hand-made records (ma_hit_t / asg_arc_t; none for bed, where n_records = n_seq), kept intervals (ma_sub_t, n_seq of them, or 0), del flags and
+ * names from host memory, formatted on the device whatever MA_TEXT_DEVICE says, in slabs of `slab` records (0: the default); *text is malloc'ed */
+int mahip_text_format_mem(mahip_ctx_t *c, int kind, const void *records, uint64_t n_records, const void *sub, uint32_t n_seq, const uint8_t *del,
+                          const char *blob, const uint64_t *off, uint64_t slab, char **text, size_t *len, mahip_text_info_t *info);
+/* MA_TEXT_DEVICE: 1 on, 0 off; unset: off (the device road wins by far where the text is gigabytes, stays inside the noise where it is megabytes) */
+int mahip_text_enabled(void);
+
 /* ---- instrumentation -------------------------------------------------------------------------------- */
 /* Per-kernel timing with HIP events on the launch stream.  enable=1 brackets every kernel launch with
  * events (adds launch overhead; use for measurement runs only). */

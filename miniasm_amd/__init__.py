@@ -186,6 +186,22 @@ class XferInfo(C.Structure):  # include/mahip.h: mahip_xfer_info_t
 XFER_ROADS = {0: None, 1: "runtime", 2: "staged_mem", 3: "staged_file"}  # MAHIP_XFER_*
 
 
+class TextInfo(C.Structure):  # include/mahip.h: mahip_text_info_t
+    _fields_ = [("kind", C.c_int), ("road", C.c_int), ("reason", C.c_int), ("n_records", C.c_uint64), ("n_lines", C.c_uint64), ("text_bytes", C.c_uint64), ("n_slabs", C.c_uint64),
+                ("slab_records", C.c_uint64), ("max_name", C.c_uint64), ("n_slow_lines", C.c_uint64), ("laps_ms", C.c_double * 4)]
+
+
+TEXT_KINDS = {"paf": 1, "sg": 2, "bed": 3}  # MAHIP_TEXT_*
+TEXT_ROADS = {0: None, 1: "host", 2: "device"}
+TEXT_REASONS = ["OK", "SWITCHED_OFF", "NOMEM", "NO_NAMES"]
+
+
+def _text_dict(t):
+    d = {k: getattr(t, k) for k, _ in TextInfo._fields_ if k != "laps_ms"}
+    d.update(kind={v: k for k, v in TEXT_KINDS.items()}.get(t.kind), road=TEXT_ROADS.get(t.road), reason=TEXT_REASONS[t.reason], laps_ms=list(t.laps_ms))
+    return d
+
+
 class ProfRec(C.Structure):
     _fields_ = [("name", C.c_char_p), ("launches", C.c_uint64), ("total_ms", C.c_double), ("alg_bytes", C.c_double)]
 
@@ -312,6 +328,8 @@ def lib():
         L.mahip_gzip_reason_name.argtypes = [i32]
         L.mahip_gzip_items_download.restype = C.c_uint64
         L.mahip_gzip_items_download.argtypes = [vp, C.POINTER(GzipItem), C.c_uint64]
+        L.mahip_text_format_mem.argtypes = [vp, i32, vp, C.c_uint64, vp, u32, vp, vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(sz), C.POINTER(TextInfo)]
+        L.mahip_text_last.argtypes = [vp, C.POINTER(TextInfo)]
         L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
         L.mahip_scan_forms.restype = None
         L.ma_opt_init.argtypes = [C.POINTER(MaOpt)]
@@ -712,6 +730,36 @@ class Ctx:
         n = lib().mahip_gzip_items_download(self.h, rows, n)
         return [dict(sync_bit=None if r.sync_bit < 0 else r.sync_bit, end_bit=r.end_bit, out_len=r.out_len, status=GZIP_REASONS[r.status], saw_final=bool(r.flags & 1), on_chain=bool(r.flags & 2))
                 for r in rows[:n]]
+
+    # ---- text of the record dumps (csrc/text_dev.hpp): for stage tests
+    def text_format(self, kind, records, names, sub=None, dele=None, slab=None):
+        """hand-made records formatted on the device: kind "paf" (records: HIT_DT), "sg" (ARC_DT; sub may be None) or "bed" (records ignored: one line per read);
+        names: one bytes object per read; sub: SUB_DT per read; dele: one flag per read (bed); slab: records per slab (None: the default).  Returns (text, info dict)"""
+        k = TEXT_KINDS[kind]
+        n_seq = len(names)
+        off = np.zeros(n_seq + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        if kind == "bed":
+            rec, n = None, n_seq
+        else:
+            rec = np.ascontiguousarray(records, dtype=HIT_DT if kind == "paf" else ARC_DT)
+            n = len(rec)
+        sub = None if sub is None else np.ascontiguousarray(sub, dtype=SUB_DT)
+        assert sub is None or len(sub) == n_seq
+        dele = None if dele is None else np.ascontiguousarray(dele, dtype=np.uint8)
+        buf, ln, info = C.c_void_p(0), C.c_size_t(0), TextInfo()
+        _chk(lib().mahip_text_format_mem(self.h, k, None if rec is None or n == 0 else rec.ctypes.data, n, None if sub is None else sub.ctypes.data, n_seq,
+                                         None if dele is None else dele.ctypes.data, blob.ctypes.data, off.ctypes.data, slab or 0, C.byref(buf), C.byref(ln), C.byref(info)), "text_format")
+        out = C.string_at(buf, ln.value)
+        lib().free_buf(buf)
+        return out, _text_dict(info)
+
+    def text_last(self):
+        """what the context's last dump through the device text writer did (or why the host formatter ran)"""
+        t = TextInfo()
+        _chk(lib().mahip_text_last(self.h, C.byref(t)), "text_last")
+        return _text_dict(t)
 
     def scan_forms(self):
         """device-wide scans of this context so far by form: (one tile, chained, three-phase)"""

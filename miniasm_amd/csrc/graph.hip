@@ -1671,7 +1671,9 @@ extern "C" uint32_t mahip_asg_n_arc(mahip_ctx_t *c) { return c->n_arc; }
 // iterations of the loop at asg.c:169 the last reduction on this context ran (the reduction moves 16 (A + I) bytes)
 extern "C" uint64_t mahip_asg_trans_inner(mahip_ctx_t *c) { return c->tr_inner; }
 
-extern "C" int mahip_asg_download(mahip_ctx_t *c, asg_t *g)
+// the device half of a graph download: c->key[0] <- the arcs as dense asg_arc_t records (n of them, at offset 0), seq[] (Rn words at *off_seq) and idx[] (2 Rn
+// words at *off_idx), in the squeezed numbering when a map is pending.  mahip_asg_download copies the three to the host; the device text writer formats the arcs
+int asg_export_dev(mahip_ctx *c, size_t *n_arc, uint32_t *n_seq, size_t *off_seq_out, size_t *off_idx_out)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	if (!c->graph_ready) { mahip_set_error("mahip_asg_download: no graph"); return -1; }
@@ -1686,6 +1688,18 @@ extern "C" int mahip_asg_download(mahip_ctx_t *c, asg_t *g)
 	if (R) hipLaunchKernelGGL(k_seq_to_aos, dim3(grid_for(R, 256)), dim3(256), 0, c->st, (const uint32_t*)P<uint32_t>(c->slen), (const uint8_t*)P<uint8_t>(c->sdel),
 	                          (const unsigned long long*)P<unsigned long long>(c->idx), map, R, (uint32_t*)(stg + off_seq), (unsigned long long*)(stg + off_idx));
 	HIPCHK(hipGetLastError());
+	*n_arc = n; *n_seq = Rn;
+	if (off_seq_out) *off_seq_out = off_seq;
+	if (off_idx_out) *off_idx_out = off_idx;
+	return 0;
+}
+
+extern "C" int mahip_asg_download(mahip_ctx_t *c, asg_t *g)
+{
+	size_t n = 0, off_seq = 0, off_idx = 0;
+	uint32_t Rn = 0;
+	CHK(asg_export_dev(c, &n, &Rn, &off_seq, &off_idx));
+	char *stg = (char*)c->key[0].p;
 	g->arc = (asg_arc_t*)malloc((n ? n : 1) * sizeof(asg_arc_t));
 	g->seq = (asg_seq_t*)malloc(((size_t)Rn ? Rn : 1) * sizeof(asg_seq_t));
 	g->idx = (uint64_t*)malloc((2 * (size_t)Rn + 1) * 8);

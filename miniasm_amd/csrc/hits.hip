@@ -2104,7 +2104,9 @@ extern "C" int mahip_hits_layout_download(mahip_ctx_t *c, uint32_t *sidx, uint32
 	return 0;
 }
 
-extern "C" int mahip_hits_download(mahip_ctx_t *c, ma_hit_t *out, size_t *n_out)
+// the device half of a hit dump: the live hits as dense ma_hit_t records in c->key[0], in the order of ma_hit_sort (tie repair included) and, with a squeeze map
+// pending, in the squeezed numbering.  mahip_hits_download copies them to the host; the device text writer (text_dev.hpp) formats them where they are
+int hits_export_dev(mahip_ctx *c, size_t *n_out)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	CHK(hits_need_cols(c, "mahip_hits_download"));
@@ -2129,7 +2131,15 @@ extern "C" int mahip_hits_download(mahip_ctx_t *c, ma_hit_t *out, size_t *n_out)
 	CHK(scan_exclusive_u32(c, P<uint32_t>(c->keep), P<uint32_t>(c->pos), n, nullptr));
 	hipLaunchKernelGGL(k_hit_export, dim3(grid_for(n, 256)), dim3(256), 0, c->st, h, n, (const uint32_t*)P<uint32_t>(c->pos),
 	                   c->has_map ? (const int32_t*)P<int32_t>(c->map) : (const int32_t*)nullptr, (ma_hit_t*)c->key[0].p, rank);
-	CHK(xfer_copy(c, c->key[0].p, out, c->n_live * sizeof(ma_hit_t), 0));
+	return 0; // (the caller lets go of the tie walk's host arrays once the stream has passed this point: walk_scratch_release)
+}
+
+extern "C" int mahip_hits_download(mahip_ctx_t *c, ma_hit_t *out, size_t *n_out)
+{
+	size_t n_live = 0;
+	CHK(hits_export_dev(c, &n_live));
+	if (n_out) *n_out = n_live;
+	if (n_live) CHK(xfer_copy(c, c->key[0].p, out, n_live * sizeof(ma_hit_t), 0));
 	walk_scratch_release(c);
 	return 0;
 }

@@ -318,6 +318,7 @@ extern "C" void mahip_destroy(mahip_ctx_t *c)
 	clean_free(c);
 	ug_free(c);
 	useq_free(c);
+	text_free(c);
 	xfer_pool_free(c);
 	free(c->gzip_rows);
 	dev_pool_destroy(c); // after everybody gave its buffers back
@@ -446,3 +447,6 @@ extern "C" int mahip_prof_get(mahip_ctx_t *c, mahip_prof_t *out, int max)
 	}
 	return n;
 }
+
+// ---- the device text writer of the record dumps: kernels and entries live in a header of their own, this is the one translation unit that includes it
+#include "text_dev.hpp"

@@ -104,6 +104,7 @@ struct mahip_ctx {
 	void *clean = nullptr;    // scratch of the graph cleaners (clean.hip)
 	void *ug = nullptr;       // unitig arrays (ug.hip)
 	void *useq = nullptr;     // unitig sequence arena (useq.hip)
+	void *text = nullptr;     // buffers of the device text writer (text_dev.hpp)
 
 	// ---- scratch ----
 	DevBuf keep, pos;         // u32 flags / scanned positions
@@ -224,6 +225,10 @@ int xfer_copy(mahip_ctx *c, void *dev_ptr, void *host_ptr, size_t bytes, int to_
 void xfer_pool_free(mahip_ctx *c);
 int xfer_from_fd(mahip_ctx *c, void *dev_ptr, int fd, size_t bytes);
 int xfer_from_fd_at(mahip_ctx *c, void *dev_ptr, int fd, size_t off, size_t bytes);
+// the device halves of mahip_hits_download (hits.hip) and mahip_asg_download (graph.hip): the dense records in c->key[0]
+int hits_export_dev(mahip_ctx *c, size_t *n_live);
+int asg_export_dev(mahip_ctx *c, size_t *n_arc, uint32_t *n_seq, size_t *off_seq, size_t *off_idx);
+void text_free(mahip_ctx *c); // text_dev.hpp (mahip_api.hip)
 void paf_free(mahip_ctx *c);
 // the text buffers of the two readers, for a loader that fills them on the device (xfer.hip: the BGZF road): reserve as mahip_paf_load_fd / mahip_fastx_load_fd
 // do (same padding, same caps), then say that the text is there

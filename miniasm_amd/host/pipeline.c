@@ -47,6 +47,33 @@ static void print_hits(size_t n_hits, const ma_hit_t *hit, const sdict_t *d, con
 	}
 }
 
+/* ---- the record dumps written on the device (csrc/text_dev.hpp): the view's names go up as one blob, the device formats the records where they are, the slabs
+ * of text come back and go to the stream.  The host formatters above (and ma_sg_print) stay for MA_TEXT_DEVICE=0 and for a device that has no room. */
+static int text_kind(const char *outfmt) { return strcmp(outfmt, "paf") == 0 ? MAHIP_TEXT_PAF : strcmp(outfmt, "sg") == 0 ? MAHIP_TEXT_SG : strcmp(outfmt, "bed") == 0 ? MAHIP_TEXT_BED : 0; }
+
+static int text_names_upload(mahip_ctx_t *c, const sdict_t *view, int with_del) /* O(name bytes of the view) */
+{
+	const uint32_t n = view->n_seq;
+	uint64_t *off = (uint64_t*)malloc(((size_t)n + 1) * 8), total = 0;
+	uint8_t *del = with_del ? (uint8_t*)malloc(n ? n : 1) : 0;
+	char *blob;
+	uint32_t i;
+	int rc;
+	if (off == 0 || (with_del && del == 0)) { free(off); free(del); return 1; }
+	for (i = 0; i < n; ++i) { off[i] = total; total += strlen(view->seq[i].name); if (del) del[i] = view->seq[i].del; }
+	off[n] = total;
+	blob = (char*)malloc(total ? total : 1);
+	if (blob == 0) { free(off); free(del); return 1; }
+	for (i = 0; i < n; ++i) memcpy(blob + off[i], view->seq[i].name, off[i + 1] - off[i]);
+	rc = mahip_text_names(c, blob, off, n, del);
+	free(blob); free(off); free(del);
+	return rc;
+}
+
+static const char *text_reason(int reason) { return reason == MAHIP_TEXT_SWITCHED_OFF ? "MA_TEXT_DEVICE is not 1" : reason == MAHIP_TEXT_NOMEM ? "no memory for its buffers" : reason == MAHIP_TEXT_NO_NAMES ? "the names are not on the device" : "ok"; }
+
+static int text_sink_file(void *arg, const char *p, size_t n) { return fwrite(p, 1, n, (FILE*)arg) == n ? 0 : -1; } /* (the stream keeps its error flag: the exit status, as with the host formatters) */
+
 /* Device passes up to (and including) transitive reduction + symm.  c holds the unsorted hits (uploaded or
  * adopted).  st[0] = have_sub, st[1] = squeezed, st[2] = n_reduced, st[3] = graph built. */
 int ma_pipeline_head(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, const char *outfmt, int stage, int flags, uint32_t st[4])
@@ -249,7 +276,10 @@ static void dev_clean(mahip_ctx_t *c, const ma_opt_t *opt, int stage, int symm_d
  * host what the text writer needs: the surviving reads (a shallow view of d: names shared), their kept intervals, and the unitigs
  * (or the cleaned string graph, or the hits for a paf dump).  It is the last thing that touches the device: a caller that
  * processes a stream of inputs can start the next one's device passes right after it.  ma_pipeline_tail_finish() is pure host
- * work: unitig sequences (-f) and the GFA / string-graph / bed / paf text; it frees the job.  d is not modified. */
+ * work: unitig sequences (-f) and the GFA / string-graph / bed / paf text; it frees the job.  d is not modified.
+ * One exception: with MA_TEXT_DEVICE=1 the text of a paf / sg / bed dump is written on the device.  The fetch then uploads the view's names and prepares the dump
+ * (records exported, every line's length, every buffer: the road is decided there, all or nothing) instead of bringing the records down, and the finish runs the
+ * write kernels and copies the slabs of text: it still uses the context, which must stay idle in between. */
 struct ma_tail_job {
 	ma_opt_t opt;
 	const sdict_t *d;
@@ -262,6 +292,8 @@ struct ma_tail_job {
 	ma_hit_t *hit;
 	asg_t *sg;
 	ma_ug_t *ug;
+	mahip_ctx_t *text_ctx; /* the device writes the text of this record dump (prepared by the fetch): finish still needs the context */
+	mahip_text_info_t text;
 	double t_fetch[5];
 };
 
@@ -279,6 +311,8 @@ static void *view_worker(void *arg)
 	for (k = v->lo; k < v->hi; ++k) v->dst[k] = v->src[v->old[k]], v->dst[k].del = 0, v->dst[k].aux = 0;
 	return 0;
 }
+
+static int tail_text_prepare(ma_tail_job_t *j, mahip_ctx_t *c, int kind);
 
 ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, const char *outfmt, int stage, const uint32_t st[4])
 {
@@ -314,7 +348,11 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 		GPU(mahip_sub_download(c, 0, j->sub, j->squeezed));
 	}
 	j->t_fetch[1] = sys_realtime();
-	if (strcmp(outfmt, "paf") == 0) {
+	if (strcmp(outfmt, "bed") == 0) {
+		tail_text_prepare(j, c, MAHIP_TEXT_BED);
+	} else if (strcmp(outfmt, "paf") == 0 && tail_text_prepare(j, c, MAHIP_TEXT_PAF)) {
+		/* the hits stay where they are */
+	} else if (strcmp(outfmt, "paf") == 0) {
 		j->n_hit = mahip_hits_live(c);
 		j->hit = (ma_hit_t*)malloc((j->n_hit ? j->n_hit : 1) * sizeof(ma_hit_t));
 		GPU(mahip_hits_download(c, j->hit, &j->n_hit));
@@ -325,7 +363,7 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 		if (strcmp(outfmt, "ug") == 0) {
 			fprintf(MA_LOG, "[M::%s] ===> Step 5: generating unitigs <===\n", "main");
 			j->ug = ma_ug_from_device(c);
-		} else {
+		} else if (!tail_text_prepare(j, c, MAHIP_TEXT_SG)) {
 			j->sg = asg_init();
 			GPU(mahip_asg_download(c, j->sg));
 			if (j->sg->n_seq != j->view.n_seq) { fprintf(stderr, "[E::%s] squeeze mismatch: host %u vs device %u reads\n", __func__, j->view.n_seq, j->sg->n_seq); exit(1); }
@@ -336,6 +374,22 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 	if (ma_timing_level() >= 1 && j->have_graph && strcmp(outfmt, "paf") != 0 && strcmp(outfmt, "bed") != 0)
 		fprintf(stderr, "[T::tail] names+sub %.3f  device cleaners %.3f  unitigs/graph to host %.3f ms\n", (j->t_fetch[1]-j->t_fetch[0])*1e3, (j->t_fetch[2]-j->t_fetch[1])*1e3, (j->t_fetch[3]-j->t_fetch[2])*1e3);
 	return j;
+}
+
+/* paf / sg / bed: the names go up and the device prepares the dump; 1 = the device road is taken (nothing has to come down), 0 = the host formatter runs */
+static int tail_text_prepare(ma_tail_job_t *j, mahip_ctx_t *c, int kind)
+{
+	int rc;
+	memset(&j->text, 0, sizeof(j->text));
+	j->text.kind = kind; j->text.road = MAHIP_TEXT_ROAD_HOST; j->text.reason = MAHIP_TEXT_SWITCHED_OFF;
+	if (!mahip_text_enabled()) return 0;
+	rc = text_names_upload(c, &j->view, kind == MAHIP_TEXT_BED && !j->squeezed);
+	if (rc > 0) { j->text.reason = MAHIP_TEXT_NOMEM; return 0; }
+	if (rc < 0) ma_gpu_fail(__func__);
+	GPU(mahip_text_prepare(c, kind, j->sub != 0, &j->text));
+	if (j->text.road != MAHIP_TEXT_ROAD_DEVICE) return 0;
+	j->text_ctx = c;
+	return 1;
 }
 
 /* out != 0: the text goes to the stream; out == 0: into one malloc'ed block (*buf, *len) -- the unitig GFA, tens of MB on a graph-heavy input, is put together by
@@ -351,7 +405,9 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	double t0 = sys_realtime();
 	FILE *ms = 0;
 	if (out == 0 && !(j->ug && strcmp(outfmt, "bed") != 0 && strcmp(outfmt, "paf") != 0)) { ms = open_memstream(buf, len); if (ms == 0) return -1; out = ms; }
-	if (strcmp(outfmt, "bed") == 0) {
+	if (j->text_ctx) { /* the device road: decided by the fetch, before the first byte */
+		if (mahip_text_emit(j->text_ctx, text_sink_file, out, &j->text) != 0 && !ferror(out)) ma_gpu_fail(__func__);
+	} else if (strcmp(outfmt, "bed") == 0) {
 		if (sub) print_subs(view, sub, out);
 	} else if (strcmp(outfmt, "paf") == 0) {
 		if (sub) print_hits(j->n_hit, j->hit, view, sub, out);
@@ -367,6 +423,13 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	if (ms) fclose(ms);
 	g_tail_laps[3] = (sys_realtime() - t0) * 1e3; g_tail_laps[4] = g_fmt_laps[0]; g_tail_laps[5] = g_fmt_laps[1];
 	if (timing) fprintf(stderr, "[T::tail] text %.3f ms\n", (sys_realtime() - t0) * 1e3);
+	if (timing && text_kind(outfmt)) {
+		const mahip_text_info_t *ti = &j->text;
+		if (j->text_ctx) fprintf(stderr, "[T::text] %s device: %llu slabs of %llu records, %llu lines, %llu bytes, %llu slow lines; names %.3f  export %.3f  format %.3f  copy+write %.3f ms\n", outfmt,
+		                         (unsigned long long)ti->n_slabs, (unsigned long long)ti->slab_records, (unsigned long long)ti->n_lines, (unsigned long long)ti->text_bytes, (unsigned long long)ti->n_slow_lines,
+		                         ti->laps_ms[0], ti->laps_ms[1], ti->laps_ms[2], ti->laps_ms[3]);
+		else fprintf(stderr, "[T::text] %s host (%s)\n", outfmt, text_reason(ti->reason));
+	}
 	ma_ug_destroy(j->ug);
 	asg_destroy(j->sg);
 	free(j->hit);
