@@ -23,7 +23,7 @@ HOST_OBJ  = $(addprefix $(B)/,$(addsuffix .o,$(HOST_SRC)))
 
 LIB       = $(PKG)/lib/libminiasm_amd.so
 BIN       = $(PKG)/bin/miniasm $(PKG)/bin/pafgen $(PKG)/bin/readgen
-CORE_TEST = $(PKG)/lib/libma_core_host.so $(PKG)/lib/libclean_host.so $(PKG)/lib/libtext_core_host.so
+CORE_TEST = $(PKG)/lib/libma_core_host.so $(PKG)/lib/libclean_host.so $(PKG)/lib/libtext_core_host.so $(PKG)/lib/libtext_ug_host.so
 
 .PHONY: all lib oracle dropin clean
 all: lib $(BIN) $(CORE_TEST) oracle dropin
@@ -63,6 +63,10 @@ $(PKG)/lib/libclean_host.so: tests/clean_host.cpp $(CSRC)/clean_core.h $(CSRC)/u
 # text_core.h compiled for the host: the dump lines' length pass and write pass run on the CPU in the tests
 $(PKG)/lib/libtext_core_host.so: tests/text_core_host.c $(CSRC)/text_core.h | $(PKG)/lib
 	$(CC) -O2 -g -Wall -fPIC -shared -I$(CSRC) -o $@ tests/text_core_host.c
+
+# its unitig-GFA routines next to the reference's own fprintf calls (which hand a uint32_t to %d: no format warnings wanted)
+$(PKG)/lib/libtext_ug_host.so: tests/text_ug_host.c $(CSRC)/text_core.h | $(PKG)/lib
+	$(CC) -O2 -g -Wall -Wno-format -fPIC -shared -I$(CSRC) -o $@ tests/text_ug_host.c
 
 oracle:
 	$(MAKE) -C oracle all

@@ -329,6 +329,7 @@ int mahip_clean_last(mahip_ctx_t *c, mahip_clean_info_t *out);
  * offset of its members; members = vertex << 32 | length to the next read; uarcs = the unitig arcs in push order (the
  * reference sorts them with its own sort afterwards, asm.c:208). */
 int mahip_ug_gen(mahip_ctx_t *c, uint32_t *n_utg, uint32_t *n_members, uint32_t *n_uarc);
+/* (a destination that is NULL is left out) */
 int mahip_ug_download(mahip_ctx_t *c, uint32_t *u_n, uint32_t *u_len, uint32_t *u_start, uint32_t *u_end, uint32_t *u_off, uint64_t *members, asg_arc_t *uarcs);
 /* asm.c:216-290 ma_ug_seq as a device byte gather (csrc/useq.hip).  Host reader (gzip, stdin, files outside the regular form below): it reads the sequence file and hands the bases of the
  * reads that sit on a unitig over in batches; a job copies `len` bases from the batch buffer to the unitig arena -- the first `len`
@@ -336,7 +337,7 @@ int mahip_ug_download(mahip_ctx_t *c, uint32_t *u_n, uint32_t *u_len, uint32_t *
 typedef struct { uint64_t src_off, dst_off; uint32_t src_len, len; uint32_t rev, pad; } mahip_useq_job_t;
 int mahip_useq_begin(mahip_ctx_t *c, size_t arena_bytes);          /* arena of all unitig strings, filled with 'N' */
 int mahip_useq_batch(mahip_ctx_t *c, const char *h_seq, size_t seq_bytes, const mahip_useq_job_t *h_jobs, size_t n_jobs);
-int mahip_useq_end(mahip_ctx_t *c, char *h_arena);                 /* the arena back to the host */
+int mahip_useq_end(mahip_ctx_t *c, char *h_arena);                 /* the arena back to the host; h_arena == NULL: no download, the finished arena stays in HBM until the next mahip_useq_begin (mahip_text_prepare_ug reads it) */
 /* The reads file read on the device (csrc/useq.hip, replaces kseq.h:192-232 kseq_read + sdict.c sd_get + the copy loops of asm.c:262-284 for files in the
  * REGULAR FORM): the whole text goes to HBM, a newline census and a scan give every line its start, one pass over the lines checks the form, the wanted reads'
  * names go into a hash table that every record's name is looked up in, and the bases are copied from the text into the arena of mahip_useq_begin.
@@ -628,27 +629,37 @@ int mahip_comm_all_gather_u64(mahip_ctx_t *c, const uint64_t *h_vals, size_t n, 
 int mahip_comm_barrier(mahip_ctx_t *c);
 int mahip_xbuf(mahip_ctx_t *c, int slot, size_t bytes, void **d_ptr);                                  /* exchange buffers (slot 0 / 1) */
 
-/* ---- text of the record dumps (-p paf, -p sg, -p bed) written on the device (csrc/text_dev.hpp over csrc/text_core.h) ---- */
+/* ---- text of the record dumps (-p paf, -p sg, -p bed) and of the unitig GFA (-p ug) written on the device (csrc/text_dev.hpp over csrc/text_core.h) ---- */
 /* A length per record, the device-wide scan, one byte string per record, in slabs of records; every slab's text goes to the host and to a sink.
- * Byte for byte what the host formatters (host/pipeline.c: print_hits, print_subs; host/unitig_gfa.c: ma_sg_print) and the reference write. */
+ * Byte for byte what the host formatters (host/pipeline.c: print_hits, print_subs; host/unitig_gfa.c: ma_sg_print, ma_ug_print) and the reference write.
+ * The unitig GFA (asm.c:77-116) is three blocks in one record space: units (per unitig its S line with the circularising links of a circular unitig, then one `a`
+ * record per member), links (one L record per unitig arc), summary (one x record per unitig).  With sequences an S line is cut into a head record, chunk records of
+ * seq_chunk bases each (no formatting: bytes of the unitig arena) and a tail record, so that no record is longer than a line and the slabs keep their size. */
 #define MAHIP_TEXT_PAF 1
 #define MAHIP_TEXT_SG  2
 #define MAHIP_TEXT_BED 3
+#define MAHIP_TEXT_UG  4
 #define MAHIP_TEXT_ROAD_HOST   1   /* nothing was written: the caller formats on the host */
 #define MAHIP_TEXT_ROAD_DEVICE 2
 #define MAHIP_TEXT_OK        0
 #define MAHIP_TEXT_SWITCHED_OFF 1  /* MA_TEXT_DEVICE is 0 or unset (the default is the host formatter: DESIGN section 7 has the measurement behind it) */
 #define MAHIP_TEXT_NOMEM     2     /* a device or host buffer could not be had */
 #define MAHIP_TEXT_NO_NAMES  3     /* mahip_text_names has not described the reads the records name */
+#define MAHIP_TEXT_NO_UG     4     /* the context holds no unitigs (mahip_ug_gen has not run, or found none) */
+#define MAHIP_TEXT_NO_SEQ    5     /* sequences were asked for, but this context holds no finished arena of these unitigs (mahip_useq_end(c, NULL)) */
+#define MAHIP_TEXT_SEQ_NUL   6     /* a NUL byte in the arena: the reference's %s would end the S line there, which is not imitated */
+#define MAHIP_TEXT_TOO_MANY  7     /* the record space of the unitig GFA does not fit 32 bits */
 typedef struct {
 	int kind, road, reason;
-	uint64_t n_records;      /* hits, arcs or reads looked at */
-	uint64_t n_lines;        /* lines written (a bed dump skips reads) */
+	uint64_t n_records;      /* hits, arcs or reads looked at; ug: records of its record space = unitigs + members + links + unitigs, and with sequences one more per unitig and chunk */
+	uint64_t n_lines;        /* lines written (a bed dump skips reads); ug: the '\n' bytes of the text */
 	uint64_t text_bytes;
 	uint64_t n_slabs, slab_records;
 	uint64_t max_name;       /* longest name of the dictionary, bytes */
-	uint64_t n_slow_lines;   /* lines of waves whose 64 lines did not fit the LDS tile: written byte by byte straight to device memory */
+	uint64_t n_slow_lines;   /* lines of waves whose 64 lines did not fit the LDS tile: written byte by byte straight to device memory (ug: RECORDS of such waves, chunks included) */
 	double laps_ms[4];       /* names upload, export of the records, format (lengths + scan + write kernels), copy to the host + sink */
+	uint64_t n_seq_bytes;    /* ug with sequences: bases copied into S lines */
+	uint64_t seq_chunk;      /* ug: bases per chunk record (MA_TEXT_SEQ_CHUNK); 0 for the record dumps */
 } mahip_text_info_t;
 /* 0 = ok; anything else ends the dump and becomes its return value */
 typedef int (*mahip_text_sink_t)(void *arg, const char *text, size_t n);
@@ -663,10 +674,23 @@ int mahip_text_prepare(mahip_ctx_t *c, int kind, int have_sub, mahip_text_info_t
 int mahip_text_emit(mahip_ctx_t *c, mahip_text_sink_t sink, void *arg, mahip_text_info_t *info);
 int mahip_text_dump(mahip_ctx_t *c, int kind, int have_sub, mahip_text_sink_t sink, void *arg, mahip_text_info_t *info);
 int mahip_text_last(mahip_ctx_t *c, mahip_text_info_t *info);
+/* prepare for the unitig GFA: works from the unitigs mahip_ug_gen left in the context (the members never come down), the names of mahip_text_names and the kept
+ * intervals of slot 0 (squeezed as for the sg kind).  links: the unitig arcs in the reference's order -- mahip_ug_download(c, 0, 0, 0, 0, 0, 0, arcs) then
+ * ma_refsort_arcs, as asg_cleanup leaves them (equal keys included, that order stays the host's); the per-end arc counts of the x lines are counted from them.
+ * with_seq: the S lines carry the unitigs' bases, taken from the arena mahip_useq_end(c, NULL) left in THIS context (anything else: road HOST, reason NO_SEQ).
+ * The same all-or-nothing decision as mahip_text_prepare, followed by the same mahip_text_emit. */
+int mahip_text_prepare_ug(mahip_ctx_t *c, int have_sub, const asg_arc_t *links, uint32_t n_links, int with_seq, mahip_text_info_t *info);
 /* stage entry (tests): hand-made records (ma_hit_t / asg_arc_t; none for bed, where n_records = n_seq), kept intervals (ma_sub_t, n_seq of them, or 0), del flags and
  * names from host memory, formatted on the device whatever MA_TEXT_DEVICE says, in slabs of `slab` records (0: the default); *text is malloc'ed */
 int mahip_text_format_mem(mahip_ctx_t *c, int kind, const void *records, uint64_t n_records, const void *sub, uint32_t n_seq, const uint8_t *del,
                           const char *blob, const uint64_t *off, uint64_t slab, char **text, size_t *len, mahip_text_info_t *info);
+/* stage entry (tests) for the unitig GFA: n_utg hand-made unitigs (u_n members each, back to back in `members`; u_start == 0xffffffff: circular), link records in
+ * output order, counts[2 i + e] = arcs leaving end e of unitig i, kept intervals (or 0); with_seq != 0: the S lines carry bases from `arena`, an image laid out as
+ * ma_ug_seq lays it out (unitig strings back to back, one spare byte behind each; arena == 0: refused with NO_SEQ).  Formats on the device whatever MA_TEXT_DEVICE
+ * says.  A refusal returns 0 with info->road = HOST, a reason and *text = NULL. */
+int mahip_text_format_ug_mem(mahip_ctx_t *c, uint32_t n_utg, const uint32_t *u_n, const uint32_t *u_len, const uint32_t *u_start, const uint32_t *u_end, const uint64_t *members,
+                             const asg_arc_t *links, uint32_t n_links, const uint32_t *counts, const void *sub, uint32_t n_seq, int with_seq, const char *arena, uint64_t arena_bytes,
+                             const char *blob, const uint64_t *off, uint64_t slab, char **text, size_t *len, mahip_text_info_t *info);
 /* MA_TEXT_DEVICE: 1 on, 0 off; unset: off (the device road wins by far where the text is gigabytes, stays inside the noise where it is megabytes) */
 int mahip_text_enabled(void);
 

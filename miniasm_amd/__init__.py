@@ -188,12 +188,13 @@ XFER_ROADS = {0: None, 1: "runtime", 2: "staged_mem", 3: "staged_file"}  # MAHIP
 
 class TextInfo(C.Structure):  # include/mahip.h: mahip_text_info_t
     _fields_ = [("kind", C.c_int), ("road", C.c_int), ("reason", C.c_int), ("n_records", C.c_uint64), ("n_lines", C.c_uint64), ("text_bytes", C.c_uint64), ("n_slabs", C.c_uint64),
-                ("slab_records", C.c_uint64), ("max_name", C.c_uint64), ("n_slow_lines", C.c_uint64), ("laps_ms", C.c_double * 4)]
+                ("slab_records", C.c_uint64), ("max_name", C.c_uint64), ("n_slow_lines", C.c_uint64), ("laps_ms", C.c_double * 4), ("n_seq_bytes", C.c_uint64),
+                ("seq_chunk", C.c_uint64)]
 
 
-TEXT_KINDS = {"paf": 1, "sg": 2, "bed": 3}  # MAHIP_TEXT_*
+TEXT_KINDS = {"paf": 1, "sg": 2, "bed": 3, "ug": 4}  # MAHIP_TEXT_*
 TEXT_ROADS = {0: None, 1: "host", 2: "device"}
-TEXT_REASONS = ["OK", "SWITCHED_OFF", "NOMEM", "NO_NAMES"]
+TEXT_REASONS = ["OK", "SWITCHED_OFF", "NOMEM", "NO_NAMES", "NO_UG", "NO_SEQ", "SEQ_NUL", "TOO_MANY"]
 
 
 def _text_dict(t):
@@ -330,6 +331,7 @@ def lib():
         L.mahip_gzip_items_download.argtypes = [vp, C.POINTER(GzipItem), C.c_uint64]
         L.mahip_text_format_mem.argtypes = [vp, i32, vp, C.c_uint64, vp, u32, vp, vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(sz), C.POINTER(TextInfo)]
         L.mahip_text_last.argtypes = [vp, C.POINTER(TextInfo)]
+        L.mahip_text_format_ug_mem.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, i32, vp, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(sz), C.POINTER(TextInfo)]
         L.mahip_scan_forms.argtypes = [vp, C.POINTER(C.c_uint64 * 3)]
         L.mahip_scan_forms.restype = None
         L.ma_opt_init.argtypes = [C.POINTER(MaOpt)]
@@ -754,6 +756,42 @@ class Ctx:
         out = C.string_at(buf, ln.value)
         lib().free_buf(buf)
         return out, _text_dict(info)
+
+    def text_format_ug(self, units, links, counts, names, sub=None, seqs=None, slab=None):
+        """hand-made unitigs as a GFA formatted on the device.  units: one (len, start, end, members) per unitig -- start == end == 0xffffffff: circular; members: the
+        member words (vertex << 32 | length to the next read); links: ARC_DT records in output order; counts: (arcs leaving end 0, end 1) per unitig; names: one bytes
+        object per read; sub: SUB_DT per read or None; seqs: None (S lines carry "*"), or one bytes object per unitig, len(seqs[i]) == units[i][0] -- or a ready arena
+        image as one bytes object, or False: sequences are asked for but there is no arena; slab: records per slab (None: the default).
+        Returns (text, info dict); text is None when the writer refused (info["road"] == "host", info["reason"] says why)"""
+        U, n_seq = len(units), len(names)
+        off = np.zeros(n_seq + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        u_len = np.array([u[0] for u in units], dtype=np.uint32)
+        u_start = np.array([u[1] for u in units], dtype=np.uint32)
+        u_end = np.array([u[2] for u in units], dtype=np.uint32)
+        u_n = np.array([len(u[3]) for u in units], dtype=np.uint32)
+        mem = np.array([m for u in units for m in u[3]], dtype=np.uint64)
+        lk = np.ascontiguousarray(links if links is not None else [], dtype=ARC_DT)
+        cnt = np.ascontiguousarray(np.array(counts, dtype=np.uint32).reshape(-1))
+        assert len(cnt) == 2 * U
+        sub = None if sub is None else np.ascontiguousarray(sub, dtype=SUB_DT)
+        assert sub is None or len(sub) == n_seq
+        arena = None
+        if seqs is not None and seqs is not False:
+            img = seqs if isinstance(seqs, (bytes, bytearray)) else b"".join(bytes(x) + b"N" for x in seqs)
+            arena = np.frombuffer(bytes(img) + b"\0", dtype=np.uint8)  # (the byte behind the image is never looked at)
+            arena_bytes = len(img)
+        buf, ln, info = C.c_void_p(0), C.c_size_t(0), TextInfo()
+        _chk(lib().mahip_text_format_ug_mem(self.h, U, u_n.ctypes.data, u_len.ctypes.data, u_start.ctypes.data, u_end.ctypes.data, mem.ctypes.data, lk.ctypes.data, len(lk), cnt.ctypes.data,
+                                            None if sub is None else sub.ctypes.data, n_seq, 0 if seqs is None else 1, None if arena is None else arena.ctypes.data,
+                                            0 if arena is None else arena_bytes, blob.ctypes.data, off.ctypes.data, slab or 0, C.byref(buf), C.byref(ln), C.byref(info)), "text_format_ug")
+        d = _text_dict(info)
+        if not buf.value:
+            return None, d
+        out = C.string_at(buf, ln.value)
+        lib().free_buf(buf)
+        return out, d
 
     def text_last(self):
         """what the context's last dump through the device text writer did (or why the host formatter ran)"""

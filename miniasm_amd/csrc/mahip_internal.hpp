@@ -239,6 +239,11 @@ void fx_text_loaded(mahip_ctx *c);
 void clean_free(mahip_ctx *c);
 void ug_free(mahip_ctx *c);
 void useq_free(mahip_ctx *c);
+// for the device text writer (text_dev.hpp): the unitigs the last mahip_ug_gen left in the context (false: none), and the unitig arena when mahip_useq_end
+// finished it without a download (false: there is no finished arena in HBM)
+struct UgDevView { uint32_t U, M, n_uarc; const uint32_t *u_n, *u_len, *u_start, *u_end, *u_off; const uint64_t *mem; const void *uarcs; };
+bool ug_dev_view(mahip_ctx *c, UgDevView *v);
+bool useq_dev_arena(mahip_ctx *c, const char **arena, size_t *bytes);
 
 // bits needed for x (0 for 0): the width of a radix key that holds values up to x
 static inline int bitlen_u64(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }

@@ -217,7 +217,18 @@ extern "C" int mahip_ug_gen(mahip_ctx_t *c, uint32_t *n_utg, uint32_t *n_members
 	if (n_uarc) *n_uarc = n_ua;
 	return 0;
 }
-// host copies: per unitig {n, len, start, end} (start == end == 0xffffffff: circular), the offsets, the members, the (unsorted) unitig arcs in push order
+bool ug_dev_view(mahip_ctx *c, UgDevView *v)
+{
+	UgBufs *b = (UgBufs*)c->ug;
+	if (!b || b->n_utg == 0) return false;
+	v->U = b->n_utg; v->M = b->n_mem; v->n_uarc = b->n_uarc;
+	v->u_n = P<uint32_t>(b->u_n); v->u_len = P<uint32_t>(b->u_len); v->u_start = P<uint32_t>(b->u_start); v->u_end = P<uint32_t>(b->u_end); v->u_off = P<uint32_t>(b->u_off);
+	v->mem = (const uint64_t*)b->ua.p; v->uarcs = b->arcs.p;
+	return true;
+}
+
+// host copies: per unitig {n, len, start, end} (start == end == 0xffffffff: circular), the offsets, the members, the (unsorted) unitig arcs in push order;
+// a destination that is NULL is left out (the device text writer fetches the unitig arcs alone)
 extern "C" int mahip_ug_download(mahip_ctx_t *c, uint32_t *u_n, uint32_t *u_len, uint32_t *u_start, uint32_t *u_end, uint32_t *u_off, uint64_t *members, asg_arc_t *uarcs)
 {
 	HIPCHK(hipSetDevice(c->dev));
@@ -225,14 +236,14 @@ extern "C" int mahip_ug_download(mahip_ctx_t *c, uint32_t *u_n, uint32_t *u_len,
 	if (!b) { mahip_set_error("mahip_ug_download: no unitigs"); return -1; }
 	const size_t U = b->n_utg;
 	if (U) {
-		HIPCHK(hipMemcpyAsync(u_n, b->u_n.p, U * 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipMemcpyAsync(u_len, b->u_len.p, U * 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipMemcpyAsync(u_start, b->u_start.p, U * 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipMemcpyAsync(u_end, b->u_end.p, U * 4, hipMemcpyDeviceToHost, c->st));
-		HIPCHK(hipMemcpyAsync(u_off, b->u_off.p, U * 4, hipMemcpyDeviceToHost, c->st));
+		if (u_n) HIPCHK(hipMemcpyAsync(u_n, b->u_n.p, U * 4, hipMemcpyDeviceToHost, c->st));
+		if (u_len) HIPCHK(hipMemcpyAsync(u_len, b->u_len.p, U * 4, hipMemcpyDeviceToHost, c->st));
+		if (u_start) HIPCHK(hipMemcpyAsync(u_start, b->u_start.p, U * 4, hipMemcpyDeviceToHost, c->st));
+		if (u_end) HIPCHK(hipMemcpyAsync(u_end, b->u_end.p, U * 4, hipMemcpyDeviceToHost, c->st));
+		if (u_off) HIPCHK(hipMemcpyAsync(u_off, b->u_off.p, U * 4, hipMemcpyDeviceToHost, c->st));
 	}
-	if (b->n_mem) HIPCHK(hipMemcpyAsync(members, b->ua.p, (size_t)b->n_mem * 8, hipMemcpyDeviceToHost, c->st));
-	if (b->n_uarc) HIPCHK(hipMemcpyAsync(uarcs, b->arcs.p, (size_t)b->n_uarc * 16, hipMemcpyDeviceToHost, c->st));
+	if (b->n_mem && members) HIPCHK(hipMemcpyAsync(members, b->ua.p, (size_t)b->n_mem * 8, hipMemcpyDeviceToHost, c->st));
+	if (b->n_uarc && uarcs) HIPCHK(hipMemcpyAsync(uarcs, b->arcs.p, (size_t)b->n_uarc * 16, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(hipStreamSynchronize(c->st));
 	return 0;
 }

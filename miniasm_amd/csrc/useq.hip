@@ -8,6 +8,7 @@
 
 struct UseqBufs {
 	DevBuf arena, seq, jobs; size_t arena_bytes = 0;
+	bool arena_kept = false; // mahip_useq_end(c, NULL): the finished arena stays in HBM for the device text writer
 	// the reads file as text (second half of this file): the text, newline counts of the granules and their scan, line starts, FASTA header flags and their
 	// scan, header line of every record, counters; the wanted reads, their names, hashes, the table over them and the record each of them takes
 	DevBuf fx_text, fx_gcnt, fx_gpos, fx_ls, fx_hdr, fx_hpos, fx_recl, fx_ctr, fx_want, fx_wname, fx_whash, fx_tab, fx_win;
@@ -67,7 +68,7 @@ extern "C" int mahip_useq_begin(mahip_ctx_t *c, size_t arena_bytes)
 	HIPCHK(hipSetDevice(c->dev));
 	UseqBufs *b = useq_bufs(c);
 	CHK(dev_reserve(c, b->arena, arena_bytes + 64));
-	b->arena_bytes = arena_bytes;
+	b->arena_bytes = arena_bytes; b->arena_kept = false;
 	if (arena_bytes) HIPCHK(hipMemsetAsync(b->arena.p, 'N', arena_bytes, c->st)); // asm.c:246: positions no read covers stay 'N'
 	return 0;
 }
@@ -91,8 +92,17 @@ extern "C" int mahip_useq_end(mahip_ctx_t *c, char *h_arena)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	UseqBufs *b = useq_bufs(c);
+	if (!h_arena) { b->arena_kept = true; return 0; } // no download: the placement is queued on the context's stream, and so is everything that reads the arena
 	if (b->arena_bytes) CHK(xfer_copy(c, b->arena.p, h_arena, b->arena_bytes, 0));
 	return 0;
+}
+
+bool useq_dev_arena(mahip_ctx *c, const char **arena, size_t *bytes)
+{
+	UseqBufs *b = (UseqBufs*)c->useq;
+	if (!b || !b->arena_kept) return false;
+	*arena = (const char*)b->arena.p; *bytes = b->arena_bytes;
+	return true;
 }
 
 // ================================================================================================ the reads file on the device

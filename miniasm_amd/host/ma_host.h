@@ -47,6 +47,14 @@ int ma_pipeline_run_sharded(const ma_opt_t *opt, const char *fn, const char *out
 /* one rank's part of it, for a context that already has a communicator of any kind (collective; rank 0 writes `out`) */
 int ma_pipeline_run_rank(mahip_ctx_t *c, const ma_opt_t *opt, const char *fn, const char *outfmt, int stage, int flags, FILE *out, int share_gpu);
 ma_ug_t *ma_ug_from_device(mahip_ctx_t *c); /* unitigs of the graph resident in c (unitig_gfa.c over csrc/ug.hip) */
+ma_ug_t *ma_ug_unpack(mahip_ctx_t *c, uint32_t U, uint32_t M, uint32_t NA); /* its second half: the unitigs mahip_ug_gen left in c (its three counts), unpacked */
+asg_arc_t *ma_ug_links_from_device(mahip_ctx_t *c, uint32_t NA); /* the unitig arcs alone, in the reference's order (free() them): what the device text writer needs on the host */
+/* ma_ug_seq in two steps (unitig_gfa.c): place = up to the finished arena, which stays in HBM; then fetch (download + one string per unitig) or drop (the device wrote the S lines) */
+typedef struct ma_ug_seq_job ma_ug_seq_job_t;
+int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn, ma_ug_seq_job_t **job);
+void ma_ug_seq_fetch(ma_ug_t *g, ma_ug_seq_job_t *job);
+void ma_ug_seq_drop(ma_ug_seq_job_t *job);
+mahip_ctx_t *ma_ug_seq_ctx(const ma_ug_seq_job_t *job); /* the context the arena lies in (ma_gpu()) */
 void ma_ug_print_mem(const ma_ug_t *ug, const sdict_t *d, const ma_sub_t *sub, char **buf, size_t *len); /* ma_ug_print's text in one malloc'ed block */
 void ma_sd_reindex(sdict_t *d);    /* build the name index from seq[] (for dictionaries assembled by hand) */
 void ma_sd_drop_index(sdict_t *d);

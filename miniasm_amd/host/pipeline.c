@@ -70,7 +70,12 @@ static int text_names_upload(mahip_ctx_t *c, const sdict_t *view, int with_del) 
 	return rc;
 }
 
-static const char *text_reason(int reason) { return reason == MAHIP_TEXT_SWITCHED_OFF ? "MA_TEXT_DEVICE is not 1" : reason == MAHIP_TEXT_NOMEM ? "no memory for its buffers" : reason == MAHIP_TEXT_NO_NAMES ? "the names are not on the device" : "ok"; }
+static const char *text_reason(int reason)
+{
+	return reason == MAHIP_TEXT_SWITCHED_OFF ? "MA_TEXT_DEVICE is not 1" : reason == MAHIP_TEXT_NOMEM ? "no memory for its buffers" : reason == MAHIP_TEXT_NO_NAMES ? "the names are not on the device" :
+	       reason == MAHIP_TEXT_NO_UG ? "no unitigs on the device" : reason == MAHIP_TEXT_NO_SEQ ? "no finished sequence arena in this context" : reason == MAHIP_TEXT_SEQ_NUL ? "a NUL byte in the sequences" :
+	       reason == MAHIP_TEXT_TOO_MANY ? "too many records" : "ok";
+}
 
 static int text_sink_file(void *arg, const char *p, size_t n) { return fwrite(p, 1, n, (FILE*)arg) == n ? 0 : -1; } /* (the stream keeps its error flag: the exit status, as with the host formatters) */
 
@@ -279,7 +284,11 @@ static void dev_clean(mahip_ctx_t *c, const ma_opt_t *opt, int stage, int symm_d
  * work: unitig sequences (-f) and the GFA / string-graph / bed / paf text; it frees the job.  d is not modified.
  * One exception: with MA_TEXT_DEVICE=1 the text of a paf / sg / bed dump is written on the device.  The fetch then uploads the view's names and prepares the dump
  * (records exported, every line's length, every buffer: the road is decided there, all or nothing) instead of bringing the records down, and the finish runs the
- * write kernels and copies the slabs of text: it still uses the context, which must stay idle in between. */
+ * write kernels and copies the slabs of text: it still uses the context, which must stay idle in between.
+ * The unitig GFA (-p ug) takes the same road under MA_TEXT_DEVICE=1: without -f the fetch runs mahip_ug_gen, brings down and sorts the unitig arcs alone and prepares
+ * (the members never come down, j->ug stays 0); with -f the host still needs the unitigs for the placement plan, so the fetch is the usual one and the finish
+ * places the reads' bases, keeps the arena in HBM and prepares with the sequences -- when the arena lies in the tail's own context (ma_gpu()), otherwise the host
+ * formats (NO_SEQ).  Any refusal leaves what happens today: ma_ug_t on the host, ma_ug_seq's download, ma_ug_print. */
 struct ma_tail_job {
 	ma_opt_t opt;
 	const sdict_t *d;
@@ -292,6 +301,7 @@ struct ma_tail_job {
 	ma_hit_t *hit;
 	asg_t *sg;
 	ma_ug_t *ug;
+	mahip_ctx_t *ctx;      /* the tail's context */
 	mahip_ctx_t *text_ctx; /* the device writes the text of this record dump (prepared by the fetch): finish still needs the context */
 	mahip_text_info_t text;
 	double t_fetch[5];
@@ -313,12 +323,13 @@ static void *view_worker(void *arg)
 }
 
 static int tail_text_prepare(ma_tail_job_t *j, mahip_ctx_t *c, int kind);
+static int tail_text_prepare_ug(ma_tail_job_t *j, mahip_ctx_t *c, const asg_arc_t *links, uint32_t n_links, int with_seq);
 
 ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const sdict_t *d, const char *outfmt, int stage, const uint32_t st[4])
 {
 	ma_tail_job_t *j = (ma_tail_job_t*)calloc(1, sizeof(ma_tail_job_t));
 	const uint32_t R = d->n_seq;
-	j->opt = *opt; j->d = d; j->stage = stage;
+	j->opt = *opt; j->d = d; j->stage = stage; j->ctx = c;
 	if (strlen(outfmt) < sizeof(j->outfmt)) strcpy(j->outfmt, outfmt); /* a longer -p value names no output mode: the empty string matches none either */
 	j->have_sub = st[0]; j->squeezed = st[1]; j->n_red = st[2]; j->have_graph = st[3];
 	j->t_fetch[0] = sys_realtime();
@@ -362,7 +373,11 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 		j->t_fetch[2] = sys_realtime();
 		if (strcmp(outfmt, "ug") == 0) {
 			fprintf(MA_LOG, "[M::%s] ===> Step 5: generating unitigs <===\n", "main");
-			j->ug = ma_ug_from_device(c);
+			if (mahip_text_enabled()) {
+				uint32_t U = 0, M = 0, NA = 0;
+				GPU(mahip_ug_gen(c, &U, &M, &NA));
+				if (g_reads_fn != 0 || !tail_text_prepare_ug(j, c, 0, NA, 0)) j->ug = ma_ug_unpack(c, U, M, NA); /* (-f: the placement plan needs the members; finish decides) */
+			} else j->ug = ma_ug_from_device(c);
 		} else if (!tail_text_prepare(j, c, MAHIP_TEXT_SG)) {
 			j->sg = asg_init();
 			GPU(mahip_asg_download(c, j->sg));
@@ -392,6 +407,25 @@ static int tail_text_prepare(ma_tail_job_t *j, mahip_ctx_t *c, int kind)
 	return 1;
 }
 
+/* the unitig GFA: links = the unitig arcs in the reference's order (0: fetched and sorted here); with_seq: the S lines take their bases from the arena in c */
+static int tail_text_prepare_ug(ma_tail_job_t *j, mahip_ctx_t *c, const asg_arc_t *links, uint32_t n_links, int with_seq)
+{
+	asg_arc_t *own = 0;
+	int rc;
+	memset(&j->text, 0, sizeof(j->text));
+	j->text.kind = MAHIP_TEXT_UG; j->text.road = MAHIP_TEXT_ROAD_HOST; j->text.reason = MAHIP_TEXT_SWITCHED_OFF;
+	if (!mahip_text_enabled()) return 0;
+	rc = text_names_upload(c, &j->view, 0);
+	if (rc > 0) { j->text.reason = MAHIP_TEXT_NOMEM; return 0; }
+	if (rc < 0) ma_gpu_fail(__func__);
+	if (links == 0) links = own = ma_ug_links_from_device(c, n_links);
+	GPU(mahip_text_prepare_ug(c, j->sub != 0, links, n_links, with_seq, &j->text));
+	free(own);
+	if (j->text.road != MAHIP_TEXT_ROAD_DEVICE) return 0;
+	j->text_ctx = c;
+	return 1;
+}
+
 /* out != 0: the text goes to the stream; out == 0: into one malloc'ed block (*buf, *len) -- the unitig GFA, tens of MB on a graph-heavy input, is put together by
  * the formatter's own threads (ma_ug_print_mem), everything else through a memory stream */
 static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
@@ -404,7 +438,20 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime();
 	FILE *ms = 0;
-	if (out == 0 && !(j->ug && strcmp(outfmt, "bed") != 0 && strcmp(outfmt, "paf") != 0)) { ms = open_memstream(buf, len); if (ms == 0) return -1; out = ms; }
+	if (j->ug && g_reads_fn) { /* main.c:193; the survivor view needs a name index of its own for sd_get */
+		if (squeezed) ma_sd_reindex(view);
+		if (mahip_text_enabled()) { /* the bases are placed, the arena stays in HBM; the device writes the S lines from it, or (a refusal) it comes down as ever */
+			ma_ug_seq_job_t *sq = 0;
+			const int placed = ma_ug_seq_place(j->ug, squeezed ? view : d, sub, g_reads_fn, &sq) == 0; /* (a reads file that cannot be opened: "*") */
+			if (placed && ma_ug_seq_ctx(sq) != j->ctx) {
+				memset(&j->text, 0, sizeof(j->text));
+				j->text.kind = MAHIP_TEXT_UG; j->text.road = MAHIP_TEXT_ROAD_HOST; j->text.reason = MAHIP_TEXT_NO_SEQ;
+			} else tail_text_prepare_ug(j, j->ctx, j->ug->g->arc, j->ug->g->n_arc, placed);
+			if (sq) { if (j->text_ctx) ma_ug_seq_drop(sq); else ma_ug_seq_fetch(j->ug, sq); }
+		} else ma_ug_seq(j->ug, squeezed ? view : d, sub, g_reads_fn);
+		if (squeezed) ma_sd_drop_index(view);
+	}
+	if (out == 0 && (j->text_ctx || !(j->ug && strcmp(outfmt, "bed") != 0 && strcmp(outfmt, "paf") != 0))) { ms = open_memstream(buf, len); if (ms == 0) return -1; out = ms; }
 	if (j->text_ctx) { /* the device road: decided by the fetch, before the first byte */
 		if (mahip_text_emit(j->text_ctx, text_sink_file, out, &j->text) != 0 && !ferror(out)) ma_gpu_fail(__func__);
 	} else if (strcmp(outfmt, "bed") == 0) {
@@ -412,18 +459,19 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	} else if (strcmp(outfmt, "paf") == 0) {
 		if (sub) print_hits(j->n_hit, j->hit, view, sub, out);
 	} else if (j->ug) {
-		if (g_reads_fn) { /* main.c:193; the survivor view needs a name index of its own for sd_get */
-			if (squeezed) ma_sd_reindex(view);
-			ma_ug_seq(j->ug, squeezed ? view : d, sub, g_reads_fn);
-			if (squeezed) ma_sd_drop_index(view);
-		}
 		if (out) ma_ug_print(j->ug, view, sub, out);
 		else ma_ug_print_mem(j->ug, view, sub, buf, len);
 	} else if (j->sg) ma_sg_print(j->sg, view, sub, out);
 	if (ms) fclose(ms);
 	g_tail_laps[3] = (sys_realtime() - t0) * 1e3; g_tail_laps[4] = g_fmt_laps[0]; g_tail_laps[5] = g_fmt_laps[1];
 	if (timing) fprintf(stderr, "[T::tail] text %.3f ms\n", (sys_realtime() - t0) * 1e3);
-	if (timing && text_kind(outfmt)) {
+	if (timing && j->text.kind == MAHIP_TEXT_UG) { /* (only with MA_TEXT_DEVICE on: otherwise a -p ug run prints what it always printed) */
+		const mahip_text_info_t *ti = &j->text;
+		if (j->text_ctx) fprintf(stderr, "[T::text] %s device: %llu slabs of %llu records, %llu lines, %llu bytes, %llu sequence bytes, %llu slow lines; names %.3f  export %.3f  format %.3f  copy+write %.3f ms\n", outfmt,
+		                         (unsigned long long)ti->n_slabs, (unsigned long long)ti->slab_records, (unsigned long long)ti->n_lines, (unsigned long long)ti->text_bytes, (unsigned long long)ti->n_seq_bytes,
+		                         (unsigned long long)ti->n_slow_lines, ti->laps_ms[0], ti->laps_ms[1], ti->laps_ms[2], ti->laps_ms[3]);
+		else fprintf(stderr, "[T::text] %s host (%s)\n", outfmt, text_reason(ti->reason));
+	} else if (timing && text_kind(outfmt)) {
 		const mahip_text_info_t *ti = &j->text;
 		if (j->text_ctx) fprintf(stderr, "[T::text] %s device: %llu slabs of %llu records, %llu lines, %llu bytes, %llu slow lines; names %.3f  export %.3f  format %.3f  copy+write %.3f ms\n", outfmt,
 		                         (unsigned long long)ti->n_slabs, (unsigned long long)ti->slab_records, (unsigned long long)ti->n_lines, (unsigned long long)ti->text_bytes, (unsigned long long)ti->n_slow_lines,

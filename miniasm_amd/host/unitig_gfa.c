@@ -105,11 +105,18 @@ void ma_ug_destroy(ma_ug_t *ug)
  * ma_ug_t and finishes the (small) unitig graph: asg_cleanup = the reference's sort order + index (asm.c:208). */
 ma_ug_t *ma_ug_from_device(mahip_ctx_t *c)
 {
+	uint32_t U = 0, M = 0, NA = 0;
+	GPU(mahip_ug_gen(c, &U, &M, &NA));
+	return ma_ug_unpack(c, U, M, NA);
+}
+
+/* the second half of ma_ug_from_device: the unitigs mahip_ug_gen left in the context (its three counts), unpacked */
+ma_ug_t *ma_ug_unpack(mahip_ctx_t *c, uint32_t U, uint32_t M, uint32_t NA)
+{
 	ma_ug_t *ug = (ma_ug_t*)calloc(1, sizeof(ma_ug_t));
-	uint32_t U = 0, M = 0, NA = 0, *u_n, *u_len, *u_start, *u_end, *u_off, k;
+	uint32_t *u_n, *u_len, *u_start, *u_end, *u_off, k;
 	uint64_t *mem;
 	ug->g = asg_init();
-	GPU(mahip_ug_gen(c, &U, &M, &NA));
 	u_n = (uint32_t*)malloc(((size_t)U + 1) * 4 * 5);
 	u_len = u_n + U; u_start = u_len + U; u_end = u_start + U; u_off = u_end + U;
 	mem = (uint64_t*)malloc(((size_t)M + 1) * 8);
@@ -133,6 +140,16 @@ ma_ug_t *ma_ug_from_device(mahip_ctx_t *c)
 	free(u_n); free(mem);
 	asg_cleanup(ug->g);
 	return ug;
+}
+
+/* the unitig arcs alone, in the reference's order (what asg_cleanup makes of them above: no arc is deleted, so it is the sort): all the device text writer needs
+ * on the host.  free() the result */
+asg_arc_t *ma_ug_links_from_device(mahip_ctx_t *c, uint32_t NA)
+{
+	asg_arc_t *a = (asg_arc_t*)malloc(((size_t)NA + 1) * sizeof(asg_arc_t));
+	GPU(mahip_ug_download(c, 0, 0, 0, 0, 0, 0, a));
+	ma_refsort_arcs(a, a + NA);
+	return a;
 }
 
 ma_ug_t *ma_ug_gen(asg_t *g) /* per-symbol form: the caller's host graph goes up first */
@@ -631,32 +648,38 @@ static void __attribute__((noinline)) ug_seq_host(mahip_ctx_t *c, const sdict_t 
 	free(batch); free(jobs); free(in_batch); free(name.s); free(seq.s); free(f.buf);
 }
 
-int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
-{
+/* ma_ug_seq in two steps.  ma_ug_seq_place: everything up to the finished arena, which stays in HBM (mahip_useq_end(c, NULL)); -1: the reads file cannot be opened.
+ * Then EITHER ma_ug_seq_fetch (the arena comes down and is cut into one string per unitig: what ma_ug_seq always did) OR ma_ug_seq_drop (the device text writer
+ * took the bases from the arena: nothing comes down).  Both print the timing line and free the job. */
+struct ma_ug_seq_job {
 	mahip_ctx_t *c;
 	fq_stream_t f;
-	utg_place_t *pl;
-	uint64_t *uoff, tot = 0;
-	char *arena;
-	uint32_t i, j;
-	int on_device = 0;
+	uint64_t *uoff, tot;
+	int on_device, streamed;
+	size_t piece_bytes;
 	mahip_useq_info_t ui;
-	double laps[N_LAPS] = {0, 0, 0, 0, 0}, t_dl, slaps[N_SLAPS] = {0, 0, 0, 0, 0, 0};
-	const int stream_mode = ma_fastx_stream_mode();
-	const size_t piece_bytes = ma_fastx_piece();
-	int forced, streamed = 0;
 	mahip_useq_stream_report_t sr;
 	stream_keep_t keep;
-	static const char *const fmt_name[] = {"?", "fasta", "fastq"};
-	memset(&f, 0, sizeof(f));
-	memset(&ui, 0, sizeof(ui));
-	memset(&sr, 0, sizeof(sr));
-	memset(&keep, 0, sizeof(keep));
-	f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
-	if (f.fp == 0) return -1;                                                      /*  nothing is read through it unless the host reader runs) */
-	c = ma_gpu();
+	double laps[N_LAPS], slaps[N_SLAPS];
+};
+
+int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn, ma_ug_seq_job_t **job)
+{
+	ma_ug_seq_job_t *q = (ma_ug_seq_job_t*)calloc(1, sizeof(ma_ug_seq_job_t));
+	mahip_ctx_t *c;
+	utg_place_t *pl;
+	uint64_t *uoff, tot = 0;
+	uint32_t i, j;
+	int on_device = 0;
+	const int stream_mode = ma_fastx_stream_mode();
+	int forced, streamed = 0;
+	*job = 0;
+	q->piece_bytes = ma_fastx_piece();
+	q->f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
+	if (q->f.fp == 0) { free(q); return -1; }                                         /*  nothing is read through it unless the host reader runs) */
+	c = q->c = ma_gpu();
 	pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
-	uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
+	uoff = q->uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
 	for (i = 0; i < g->u.n; ++i) { /* where every read lands; unitig strings back to back, each with its terminator */
 		const ma_utg_t *u = &g->u.a[i];
 		uint32_t l = 0;
@@ -669,49 +692,82 @@ int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
 			l += t->len;
 		}
 	}
+	q->tot = tot;
 	GPU(mahip_useq_begin(c, (size_t)tot));
 	{ const char *e = getenv("MA_FASTX_HOST"); forced = e && atoi(e) != 0; }
 	if (forced || stream_mode != 2) { /* the whole-file device reader first, as ever */
-		on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &ui, laps);
+		on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &q->ui, q->laps);
 		if (on_device < 0) ma_gpu_fail(__func__);
 	}
-	if (!forced && !on_device && (stream_mode == 2 || (stream_mode == 1 && (ui.reason == MAHIP_FASTX_NOT_PLAIN || ui.reason == MAHIP_FASTX_NOMEM)))) { /* the streamed device reader */
-		memset(&ui, 0, sizeof(ui));
+	if (!forced && !on_device && (stream_mode == 2 || (stream_mode == 1 && (q->ui.reason == MAHIP_FASTX_NOT_PLAIN || q->ui.reason == MAHIP_FASTX_NOMEM)))) { /* the streamed device reader */
+		memset(&q->ui, 0, sizeof(q->ui));
 		streamed = 1;
-		on_device = ug_seq_stream(c, d, sub, &f, pl, uoff, piece_bytes, &ui, &sr, slaps, &keep);
+		on_device = ug_seq_stream(c, d, sub, &q->f, pl, uoff, q->piece_bytes, &q->ui, &q->sr, q->slaps, &q->keep);
 		if (on_device < 0) ma_gpu_fail(__func__);
 	}
-	ui.reader = streamed ? MAHIP_USEQ_STREAM : on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
-	mahip_useq_note(c, &ui);
+	q->ui.reader = streamed ? MAHIP_USEQ_STREAM : on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
+	mahip_useq_note(c, &q->ui);
 	if (!on_device) {
-		if (streamed) fprintf(stderr, "[W::%s] reads file handed to the host reader at piece %lld: %s\n", __func__, (long long)sr.refused_piece, mahip_fastx_reason_name(ui.reason));
-		else fprintf(stderr, "[W::%s] reads file read on the host: %s\n", __func__, mahip_fastx_reason_name(ui.reason));
+		if (streamed) fprintf(stderr, "[W::%s] reads file handed to the host reader at piece %lld: %s\n", "ma_ug_seq", (long long)q->sr.refused_piece, mahip_fastx_reason_name(q->ui.reason));
+		else fprintf(stderr, "[W::%s] reads file read on the host: %s\n", "ma_ug_seq", mahip_fastx_reason_name(q->ui.reason));
 	}
-	if (!on_device) ug_seq_host(c, d, sub, &f, pl, uoff);
-	arena = (char*)malloc(tot ? tot : 1);
-	t_dl = sys_realtime();
-	GPU(mahip_useq_end(c, arena));
-	laps[LAP_DOWNLOAD] = (sys_realtime() - t_dl) * 1e3;
+	if (!on_device) ug_seq_host(c, d, sub, &q->f, pl, uoff);
+	GPU(mahip_useq_end(c, 0)); /* finished; it stays in HBM */
+	q->on_device = on_device; q->streamed = streamed;
+	free(pl);
+	*job = q;
+	return 0;
+}
+
+static void ug_seq_close(ma_ug_seq_job_t *q)
+{
+	static const char *const fmt_name[] = {"?", "fasta", "fastq"};
+	const mahip_useq_info_t ui = q->ui;
+	const mahip_useq_stream_report_t sr = q->sr;
+	const double *laps = q->laps, *slaps = q->slaps;
 	if (ma_timing_level() >= 1) {
-		if (streamed) {
+		if (q->streamed) {
 			char ho[32];
 			if (sr.refused_piece < 0) strcpy(ho, "none"); else snprintf(ho, sizeof(ho), "%lld", (long long)sr.refused_piece);
 			fprintf(stderr, "[T::ug_seq] reader=stream format=%s pieces=%llu piece=%llu B records=%llu matched=%llu dup=%llu handover=%s reason=%d : producer %.3f upload %.3f index %.3f lookup %.3f place %.3f waited-for-input %.3f download %.3f ms\n",
-			        fmt_name[ui.format], (unsigned long long)sr.n_pieces, (unsigned long long)piece_bytes, (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, ho, ui.reason,
+			        fmt_name[ui.format], (unsigned long long)sr.n_pieces, (unsigned long long)q->piece_bytes, (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, ho, ui.reason,
 			        slaps[SLAP_PRODUCER], slaps[SLAP_UPLOAD], slaps[SLAP_INDEX], slaps[SLAP_LOOKUP], slaps[SLAP_PLACE], slaps[SLAP_WAIT], laps[LAP_DOWNLOAD]);
-		} else if (on_device) fprintf(stderr, "[T::ug_seq] reader=device format=%s records=%llu matched=%llu dup=%llu : load %.3f index %.3f lookup %.3f place %.3f download %.3f ms\n", fmt_name[ui.format],
+		} else if (q->on_device) fprintf(stderr, "[T::ug_seq] reader=device format=%s records=%llu matched=%llu dup=%llu : load %.3f index %.3f lookup %.3f place %.3f download %.3f ms\n", fmt_name[ui.format],
 		                       (unsigned long long)ui.n_records, (unsigned long long)ui.n_matched, (unsigned long long)ui.n_dup, laps[LAP_LOAD], laps[LAP_INDEX], laps[LAP_LOOKUP], laps[LAP_PLACE], laps[LAP_DOWNLOAD]);
 		else fprintf(stderr, "[T::ug_seq] reader=host reason=%d format=%s records=%llu : download %.3f ms\n", ui.reason, fmt_name[ui.format], (unsigned long long)ui.n_records, laps[LAP_DOWNLOAD]);
 	}
+	free(q->uoff);
+	if (q->keep.q_live) ma_stream_q_destroy(&q->keep.q);
+	free(q->keep.window);
+	if (q->f.fp) gzclose(q->f.fp);
+	free(q);
+}
+
+mahip_ctx_t *ma_ug_seq_ctx(const ma_ug_seq_job_t *q) { return q->c; }
+
+void ma_ug_seq_drop(ma_ug_seq_job_t *q) { ug_seq_close(q); }
+
+void ma_ug_seq_fetch(ma_ug_t *g, ma_ug_seq_job_t *q)
+{
+	char *arena = (char*)malloc(q->tot ? q->tot : 1);
+	const double t_dl = sys_realtime();
+	uint32_t i;
+	GPU(mahip_useq_end(q->c, arena));
+	q->laps[LAP_DOWNLOAD] = (sys_realtime() - t_dl) * 1e3;
 	for (i = 0; i < g->u.n; ++i) { /* ma_ug_destroy frees every string on its own */
 		ma_utg_t *u = &g->u.a[i];
 		u->s = (char*)malloc((size_t)u->len + 1);
-		memcpy(u->s, arena + uoff[i], u->len);
+		memcpy(u->s, arena + q->uoff[i], u->len);
 		u->s[u->len] = 0;
 	}
-	free(arena); free(uoff); free(pl);
-	if (keep.q_live) ma_stream_q_destroy(&keep.q);
-	free(keep.window);
-	if (f.fp) gzclose(f.fp);
+	free(arena);
+	ug_seq_close(q);
+}
+
+int ma_ug_seq(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn)
+{
+	ma_ug_seq_job_t *q;
+	if (ma_ug_seq_place(g, d, sub, fn, &q) != 0) return -1;
+	ma_ug_seq_fetch(g, q);
 	return 0;
 }

@@ -7,7 +7,7 @@ random line borders into pieces (empty and single-line pieces included) through 
 and the reference library; and through the command line with MA_INGEST_STREAM=1 and a random MA_INGEST_PIECE, compared with the reference binary.  Each such case
 also runs with -R: the same pieces through mahip_paf_stream_begin_excl with the case's (max_hang, int_frac) (the comparison is
 tests/test_gpu_ingest_stream_excl.py's), and the command line with -R added under MA_STREAM_NOCONT=1.  With --dumps every case asks for a record dump (-p paf,
--p sg or -p bed at a random -S) and runs with the device text writer forced (MA_TEXT_DEVICE=1, a random MA_TEXT_SLAB): csrc/text_dev.hpp against the
+-p sg, -p bed or -p ug at a random -S) and runs with the device text writer forced (MA_TEXT_DEVICE=1, a random MA_TEXT_SLAB): csrc/text_dev.hpp against the
 reference's fprintf; the road each run took is tallied."""
 import argparse
 import gzip
@@ -275,7 +275,7 @@ def main():
     ap.add_argument("--stream", action="store_true", help="the streamed ingest: the text cut at random line borders through mahip_paf_stream_* (against the whole parse, the host reader, the reference library), and the command line under MA_INGEST_STREAM=1 with a random MA_INGEST_PIECE")
     ap.add_argument("--gzip", action="store_true", help="every case also runs on its PAF text as a plain gzip file (random level, memLevel, strategy, flush points, header fields) with MA_GZIP_DEVICE=1 and a random MA_GZIP_CHUNK: the chunked device inflater; the road taken is tallied by reason")
     ap.add_argument("--seq", action="store_true", help="unitig sequences: every case also gets a random reads file and runs with -f (ma_ug_seq; the device byte gather)")
-    ap.add_argument("--dumps", action="store_true", help="every case asks for -p paf / -p sg / -p bed at a random -S and runs with the device text writer forced (MA_TEXT_DEVICE=1, random MA_TEXT_SLAB)")
+    ap.add_argument("--dumps", action="store_true", help="every case asks for -p paf / -p sg / -p bed / -p ug at a random -S and runs with the device text writer forced (MA_TEXT_DEVICE=1, random MA_TEXT_SLAB)")
     ap.add_argument("--text", action="store_true", help="damage the PAF text (reader / dictionary semantics) instead of varying the options")
     ap.add_argument("--cases", type=int, default=100)
     ap.add_argument("--seed", type=int, default=1)
@@ -310,7 +310,8 @@ def main():
             open(paf, "wb").write(data)
             args = rng.choice([["-p", "paf", "-S2"], ["-p", "paf"], ["-p", "bed"], ["-p", "sg"], [], ["-R", "-p", "paf"], ["-B", "-p", "paf", "-S2"], ["-s", "0", "-m", "0", "-p", "paf", "-S2"]])
         if a.dumps:
-            dump = rng.choice([["-p", "paf", "-S%d" % rng.randrange(2, 6)], ["-p", "paf"], ["-p", "sg", "-S%d" % rng.randrange(1, 12)], ["-p", "sg"], ["-p", "bed", "-S%d" % rng.randrange(2, 6)], ["-p", "bed"]])
+            dump = rng.choice([["-p", "paf", "-S%d" % rng.randrange(2, 6)], ["-p", "paf"], ["-p", "sg", "-S%d" % rng.randrange(1, 12)], ["-p", "sg"], ["-p", "bed", "-S%d" % rng.randrange(2, 6)], ["-p", "bed"],
+                               ["-p", "ug", "-S%d" % rng.randrange(5, 12)], ["-p", "ug"]])  # (the unitig GFA goes the same road: the ug kind of the device text writer)
             args = [x for x in args if x not in ("-p", "sg", "paf", "bed", "ug") and not x.startswith("-S")] + dump
         if a.seq:
             reads = os.path.join(tmp, "reads.fx")

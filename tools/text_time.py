@@ -4,7 +4,9 @@
 never this build's own host road.  Input: the BASELINE configs[2] stand-in (pafgen -r 1200000 -n 40000000 -s 4, divided by --div), or with --small the 80 000-line
 input of the tests (pafgen -r 3000 -n 80000 -s 41).  Per dump the settings alternate: the parent's command line; this build with MA_TEXT_DEVICE=0 (nothing changed:
 within the parent's own spread); this build with MA_TEXT_DEVICE=1 for every MA_TEXT_SLAB of --slabs (Mi records).  --reps rounds (at least 5 for a result that
-decides anything); median and min-max of each setting are reported, with the [T::text] line, the child's ru_maxrss and the CRC-32 of the output, which must be the
+decides anything).  The unitig GFA (--dumps ug,ug_S6,ug_f; DESIGN 3.20, the ug kind) has inputs of its own: `ug` runs on the graph-heavy input (pafgen -L fixed,
+50 lines per read: -r 2000000 -n 100000000 -s 4, divided by --div), `ug_S6` and `ug_f` (-p ug -f <a FASTQ readgen makes for that PAF>) on the noisy input
+(-r 1000000 -n 50000000 -s 3 -L uniform -d 0.35 -x 0.03, divided by --div); median and min-max of each setting are reported, with the [T::text] line, the child's ru_maxrss and the CRC-32 of the output, which must be the
 same in every setting.  Stdout of every run goes to one file in the work directory.  Every GPU step runs under its own `timeout -k 10`; the first one that fails
 ends the script.  Result: one JSON line, also written to --out (merged into what --out already holds for other --div / dumps).
 
@@ -20,7 +22,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "miniasm_amd", "bin")
-DUMPS = {"paf_S2": ["-p", "paf", "-S2"], "paf": ["-p", "paf"], "sg_S5": ["-p", "sg", "-S5"], "sg": ["-p", "sg"], "bed": ["-p", "bed"]}
+DUMPS = {"paf_S2": ["-p", "paf", "-S2"], "paf": ["-p", "paf"], "sg_S5": ["-p", "sg", "-S5"], "sg": ["-p", "sg"], "bed": ["-p", "bed"],
+         "ug": ["-p", "ug"], "ug_S6": ["-p", "ug", "-S6"], "ug_f": ["-p", "ug"]}
+UG_INPUT = {"ug": "graph", "ug_S6": "noisy", "ug_f": "noisy"}  # the unitig GFA's own inputs; ug_f adds -f <reads>
 
 
 def timed(cmd, env, out_path, limit):
@@ -55,11 +59,13 @@ def text_line(log):
         return None
     m = re.match(r"\[T::text\] (\S+) (device|host)", t[0])
     out = {"road": m.group(2)}
-    m = re.search(r"(\d+) slabs of (\d+) records, (\d+) lines, (\d+) bytes, (\d+) slow lines; names ([\d.]+)  export ([\d.]+)  format ([\d.]+)  copy\+write ([\d.]+) ms", t[0])
+    m = re.search(r"(\d+) slabs of (\d+) records, (\d+) lines, (\d+) bytes, (?:(\d+) sequence bytes, )?(\d+) slow lines; names ([\d.]+)  export ([\d.]+)  format ([\d.]+)  copy\+write ([\d.]+) ms", t[0])
     if m:
         g = m.groups()
-        out.update(slabs=int(g[0]), slab_records=int(g[1]), lines=int(g[2]), bytes=int(g[3]), slow_lines=int(g[4]),
-                   laps_ms={"names": float(g[5]), "export": float(g[6]), "format": float(g[7]), "copy_write": float(g[8])})
+        out.update(slabs=int(g[0]), slab_records=int(g[1]), lines=int(g[2]), bytes=int(g[3]), slow_lines=int(g[5]),
+                   laps_ms={"names": float(g[6]), "export": float(g[7]), "format": float(g[8]), "copy_write": float(g[9])})
+        if g[4] is not None:
+            out["seq_bytes"] = int(g[4])
     return out
 
 
@@ -78,24 +84,41 @@ def main():
     a = ap.parse_args()
     base = os.path.join(a.tmp, "text_time_%d" % os.getpid())
     paf, out_path = base + ".paf", base + ".out"
+    extra = {"graph": base + ".graph.paf", "noisy": base + ".noisy.paf", "reads": base + ".noisy.fq"}
+    extra_gen = {"graph": ["-r", str(2000000 // a.div), "-n", str(100000000 // a.div), "-s", "4", "-L", "fixed"],
+                 "noisy": ["-r", str(1000000 // a.div), "-n", str(50000000 // a.div), "-s", "3", "-L", "uniform", "-d", "0.35", "-x", "0.03"]}
     gen = ["-r", "3000", "-n", "80000", "-s", "41"] if a.small else ["-r", str(1200000 // a.div), "-n", str(40000000 // a.div), "-s", "4"]
     key = "small" if a.small else "div%d" % a.div
     slabs = [int(x) for x in a.slabs.split(",") if x]
     try:
-        subprocess.run([os.path.join(BIN, "pafgen")] + gen + ["-o", paf], check=True, stderr=subprocess.DEVNULL)
-        res = {"pafgen": " ".join(gen), "reps": a.reps, "paf_bytes": os.path.getsize(paf), "dumps": {}}
+        if any(d not in UG_INPUT for d in a.dumps.split(",")):
+            subprocess.run([os.path.join(BIN, "pafgen")] + gen + ["-o", paf], check=True, stderr=subprocess.DEVNULL)
+        res = {"pafgen": " ".join(gen), "reps": a.reps, "paf_bytes": os.path.getsize(paf) if os.path.exists(paf) else 0, "dumps": {}}
         print("input ready: %d bytes" % res["paf_bytes"], flush=True)
         for dump in a.dumps.split(","):
+            paf_d, tail = paf, []
+            if dump in UG_INPUT:  # made when the first dump asks for it
+                paf_d = extra[UG_INPUT[dump]]
+                if not os.path.exists(paf_d):
+                    subprocess.run([os.path.join(BIN, "pafgen")] + extra_gen[UG_INPUT[dump]] + ["-o", paf_d], check=True, stderr=subprocess.DEVNULL)
+                    res.setdefault("pafgen_" + UG_INPUT[dump], " ".join(extra_gen[UG_INPUT[dump]]))
+                if dump == "ug_f":
+                    if not os.path.exists(extra["reads"]):
+                        subprocess.run([os.path.join(BIN, "readgen"), "-q", "-s", "7", "-o", extra["reads"], paf_d], check=True, stderr=subprocess.DEVNULL)
+                    tail = ["-f", extra["reads"]]
             settings = [("parent", a.parent, {}), ("device_off", a.miniasm, {"MA_TEXT_DEVICE": "0"})]
             settings += [("device_%dMi" % s, a.miniasm, {"MA_TEXT_DEVICE": "1", "MA_TEXT_SLAB": str(s << 20)}) for s in slabs]
             runs = {name: {"wall_s": [], "maxrss_kib": [], "text": None} for name, _, _ in settings}
             crcs, sizes = set(), set()
             for rep in range(a.reps):
                 for name, binary, env in settings:
-                    dt, log, crc, n, rss = timed([binary] + DUMPS[dump] + [paf], env, out_path, a.limit)
+                    dt, log, crc, n, rss = timed([binary] + DUMPS[dump] + tail + [paf_d], env, out_path, a.limit)
                     crcs.add(crc), sizes.add(n)
                     t = text_line(log)
-                    if name.startswith("device_") and (t is None or t["road"] != ("host" if name == "device_off" else "device")):
+                    if name == "device_off" and dump in UG_INPUT:  # (with the switch off a -p ug run prints what the parent prints: no [T::text] line)
+                        if t is not None:
+                            sys.exit("%s %s: a [T::text] line with the switch off:\n%s" % (dump, name, log[-2000:]))
+                    elif name.startswith("device_") and (t is None or t["road"] != ("host" if name == "device_off" else "device")):
                         sys.exit("%s %s: the wrong formatter ran:\n%s" % (dump, name, log[-2000:]))
                     runs[name]["wall_s"].append(round(dt, 4))
                     runs[name]["maxrss_kib"].append(rss)
@@ -124,7 +147,7 @@ def main():
                 json.dump(whole, f, indent=1, sort_keys=True)
                 f.write("\n")
     finally:
-        for p in (paf, out_path):
+        for p in (paf, out_path) + tuple(extra.values()):
             if os.path.exists(p):
                 os.remove(p)
 
