@@ -422,6 +422,53 @@ int mahip_useq_stream_window_download(mahip_ctx_t *c, void *dst, uint64_t *nbyte
 int mahip_useq_stream_end(mahip_ctx_t *c);   /* waits for the last placement; the arena is mahip_useq_end's */
 int mahip_useq_stream_abort(mahip_ctx_t *c); /* legal without a stream */
 int mahip_useq_stream_last(mahip_ctx_t *c, mahip_useq_stream_report_t *out); /* valid from begin until the next begin */
+/* The placement plan on the device (csrc/useq.hip): asm.c:248-260 -- where every unitig's string starts in the arena and where every read that sits
+ * on a unitig lands on it -- plus the wanted table of the device readers (host/unitig_gfa.c: ug_seq_wanted), from the unitigs mahip_ug_gen left in the context, the
+ * names of mahip_text_names and the kept intervals of slot 0, in the numbering mahip_text_prepare_ug uses.  No member word comes down.
+ *   uoff[i]   = sum over j < i of (u_len[j] + 1), 64 bits (asm.c:250: `tot`, one terminator per string); arena_bytes = uoff[n_utg]
+ *   per read  : utg, ori = m >> 32 & 1, len = (uint32_t)m, start = the sum mod 2^32 of the low words of the members in front of it on its unitig (asm.c:252-258,
+ *               the reference's uint32_t l: the same number the `a` lines print, csrc/text_core.h: tc_ug_member_start); a read on no unitig has len 0
+ *   wanted    : the reads with len != 0 and a name that is not empty, in ascending read id: dst_off = uoff[utg] + start (64 bits), len, rev = ori, whole = !have_sub,
+ *               s / e = the kept interval (0 without), name_off / name_len = the read's name IN THE BLOB OF mahip_text_names -- the names are not copied; the table
+ *               is valid until the next mahip_text_names, mahip_ug_gen or plan of the context.
+ * A read that is a member more than once makes the reference assert (asm.c:255); here the plan refuses (MULTI) and the caller keeps its host plan.
+ * Returns 0 with info->road = DEVICE; or 0 with road = HOST and a reason: no plan is held then, and nothing else in the context -- arena, loaded text, the tables of
+ * the host-table entries -- has changed; or -1 (error: a member names a read outside the dictionary, a HIP error). */
+enum { MAHIP_PLAN_ROAD_HOST = 1, MAHIP_PLAN_ROAD_DEVICE = 2 };
+enum { MAHIP_PLAN_OK = 0, MAHIP_PLAN_NO_UG,  /* the context holds no unitigs (mahip_ug_gen has not run, or found none) */
+       MAHIP_PLAN_NO_NAMES,                  /* mahip_text_names has not described the reads the members name */
+       MAHIP_PLAN_MULTI,                     /* a read is a member more than once */
+       MAHIP_PLAN_NOMEM,                     /* no device memory for the plan */
+       MAHIP_PLAN_FORCED };                  /* MA_USEQ_PLAN_HOST=1 */
+typedef struct { uint32_t utg, start, len, ori; } mahip_useq_place_t; /* one per read: host/unitig_gfa.c: utg_place_t with its fields as words */
+typedef struct {
+	int road, reason;
+	uint64_t n_utg, n_members, n_reads;
+	uint64_t n_wanted;       /* entries of the wanted table */
+	uint64_t name_bytes;     /* bytes of the wanted reads' names */
+	uint64_t blob_bytes;     /* bytes of the blob the table's name_off point into (mahip_useq_plan_download: `names`) */
+	uint64_t arena_bytes;    /* uoff[n_utg] */
+	uint64_t n_multi;        /* members that found their read taken already */
+	uint64_t uoff_tiles;     /* tiles of the 64-bit scan (more than one: block sums, their scan, the down sweep) */
+	double ms;               /* wall time of the plan, its one wait for the device included */
+} mahip_useq_plan_info_t;
+int mahip_useq_plan(mahip_ctx_t *c, int have_sub, mahip_useq_plan_info_t *info);
+int mahip_useq_plan_last(mahip_ctx_t *c, mahip_useq_plan_info_t *info); /* the info of the last plan, refused ones included */
+const char *mahip_useq_plan_reason_name(int reason);
+/* stage entry (tests), the counterpart of mahip_text_format_ug_mem: hand-made unitigs (u_n members each, back to back in `members`), n_seq names (blob / off as
+ * mahip_text_names takes them, which it calls; blob == 0: NO_NAMES) and kept intervals (ma_sub_t, n_seq of them, or 0) from host memory.  Allocates no arena, so
+ * u_len may be anything.  Whatever MA_TEXT_DEVICE says; MA_USEQ_PLAN_HOST=1 refuses here too. */
+int mahip_useq_plan_mem(mahip_ctx_t *c, uint32_t n_utg, const uint32_t *u_n, const uint32_t *u_len, const uint64_t *members, uint32_t n_seq, const char *blob, const uint64_t *off,
+                        const void *sub, mahip_useq_plan_info_t *info);
+/* the plan to the host: uoff[n_utg + 1], pl[n_reads], want[n_wanted], names[blob_bytes]; a destination that is NULL is left out.  For the host reader, which needs
+ * pl and uoff (asm.c:262-284), for ma_ug_seq_fetch, which cuts the arena with uoff, and for the tests. */
+int mahip_useq_plan_download(mahip_ctx_t *c, uint64_t *uoff, mahip_useq_place_t *pl, mahip_useq_want_t *want, char *names);
+/* the planned forms: mahip_useq_begin with the plan's arena_bytes; mahip_useq_place_text and mahip_useq_stream_begin with the plan's wanted table, which is on the
+ * device already (asm.c:248-260 as that table; everything behind the upload is the host-table entries' own code).  -1 without a plan, or when the arena is not the
+ * plan's (mahip_useq_begin_planned), or when an entry of the table reaches outside it. */
+int mahip_useq_begin_planned(mahip_ctx_t *c);
+int mahip_useq_place_text_planned(mahip_ctx_t *c, uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms);
+int mahip_useq_stream_begin_planned(mahip_ctx_t *c);
 /* ---- bgzip-compressed (BGZF) input inflated on the device (csrc/xfer.hip: k_bgzf_inflate, csrc/inflate_core.h; the member walk: host/ingest_gpu.c).
  * A BGZF file is a chain of gzip members of at most 64 KiB of text each, every one with its compressed size in a `BC` extra subfield and its inflated size in
  * its trailer: the host walks the chain once (one small read per member) into a table -- where each member's deflate bytes lie, its CRC and ISIZE, and where
@@ -678,7 +725,8 @@ int mahip_text_last(mahip_ctx_t *c, mahip_text_info_t *info);
  * intervals of slot 0 (squeezed as for the sg kind).  links: the unitig arcs in the reference's order -- mahip_ug_download(c, 0, 0, 0, 0, 0, 0, arcs) then
  * ma_refsort_arcs, as asg_cleanup leaves them (equal keys included, that order stays the host's); the per-end arc counts of the x lines are counted from them.
  * with_seq: the S lines carry the unitigs' bases, taken from the arena mahip_useq_end(c, NULL) left in THIS context (anything else: road HOST, reason NO_SEQ).
- * The same all-or-nothing decision as mahip_text_prepare, followed by the same mahip_text_emit. */
+ * Where every unitig's bases start in it (asm.c:250) is the uoff of mahip_useq_plan when the context holds a plan of these unitigs; otherwise the lengths come down,
+ * are summed up on the host and the offsets go up.  The same all-or-nothing decision as mahip_text_prepare, followed by the same mahip_text_emit. */
 int mahip_text_prepare_ug(mahip_ctx_t *c, int have_sub, const asg_arc_t *links, uint32_t n_links, int with_seq, mahip_text_info_t *info);
 /* stage entry (tests): hand-made records (ma_hit_t / asg_arc_t; none for bed, where n_records = n_seq), kept intervals (ma_sub_t, n_seq of them, or 0), del flags and
  * names from host memory, formatted on the device whatever MA_TEXT_DEVICE says, in slabs of `slab` records (0: the default); *text is malloc'ed */

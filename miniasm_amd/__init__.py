@@ -83,6 +83,23 @@ class UseqInfo(C.Structure):  # include/mahip.h: mahip_useq_info_t
                 ("n_short", C.c_uint64)]
 
 
+class UseqPlanInfo(C.Structure):  # include/mahip.h: mahip_useq_plan_info_t
+    _fields_ = [("road", C.c_int), ("reason", C.c_int), ("n_utg", C.c_uint64), ("n_members", C.c_uint64), ("n_reads", C.c_uint64), ("n_wanted", C.c_uint64), ("name_bytes", C.c_uint64),
+                ("blob_bytes", C.c_uint64), ("arena_bytes", C.c_uint64), ("n_multi", C.c_uint64), ("uoff_tiles", C.c_uint64), ("ms", C.c_double)]
+
+
+PLAN_ROADS = {0: None, 1: "host", 2: "device"}
+PLAN_REASONS = ["OK", "NO_UG", "NO_NAMES", "MULTI", "NOMEM", "FORCED"]
+WANT_DT = np.dtype([("dst_off", "<u8"), ("name_off", "<u8"), ("name_len", "<u4"), ("len", "<u4"), ("s", "<u4"), ("e", "<u4"), ("rev", "<u4"), ("whole", "<u4")])  # mahip_useq_want_t
+PLACE_DT = np.dtype([("utg", "<u4"), ("start", "<u4"), ("len", "<u4"), ("ori", "<u4")])  # mahip_useq_place_t
+
+
+def _plan_dict(p):
+    d = {k: getattr(p, k) for k, _ in UseqPlanInfo._fields_}
+    d.update(road=PLAN_ROADS.get(p.road), reason=PLAN_REASONS[p.reason])
+    return d
+
+
 class UseqStreamVerdict(C.Structure):  # include/mahip.h: mahip_useq_stream_verdict_t
     _fields_ = [("reason", C.c_int), ("n_records", C.c_uint64), ("bytes_consumed", C.c_uint64), ("carry_bytes", C.c_uint64), ("n_placed", C.c_uint64)]
 
@@ -312,6 +329,13 @@ def lib():
         L.mahip_useq_stream_end.argtypes = [vp]
         L.mahip_useq_stream_abort.argtypes = [vp]
         L.mahip_useq_stream_last.argtypes = [vp, C.POINTER(UseqStreamReport)]
+        L.mahip_useq_plan.argtypes = [vp, i32, C.POINTER(UseqPlanInfo)]
+        L.mahip_useq_plan_mem.argtypes = [vp, u32, vp, vp, vp, u32, vp, vp, vp, C.POINTER(UseqPlanInfo)]
+        L.mahip_useq_plan_last.argtypes = [vp, C.POINTER(UseqPlanInfo)]
+        L.mahip_useq_plan_download.argtypes = [vp, vp, vp, vp, vp]
+        L.mahip_useq_begin_planned.argtypes = [vp]
+        L.mahip_useq_place_text_planned.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+        L.mahip_useq_stream_begin_planned.argtypes = [vp]
         L.mahip_bgzf_load_fd.argtypes = [vp, i32, sz, i32, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_load_mem.argtypes = [vp, vp, sz, i32, C.POINTER(BgzfInfo)]
         L.mahip_bgzf_inflate_mem.argtypes = [vp, vp, sz, vp, sz, C.POINTER(BgzfInfo)]
@@ -623,6 +647,11 @@ class Ctx:
         _chk(L.mahip_fastx_release(self.h), "fastx_release")  # (a window buffer of the size the pieces ask for: the growths are the stream's own)
         _chk(L.mahip_useq_begin(self.h, arena_bytes), "useq_begin")
         _chk(L.mahip_useq_stream_begin(self.h, C.addressof(arr), len(wanted), blob, len(blob)), "useq_stream_begin")
+        return self._useq_stream_pieces(pieces, arena_bytes, each)
+
+    def _useq_stream_pieces(self, pieces, arena_bytes, each):
+        """the pieces through the stream that was begun, then the arena"""
+        L = lib()
         verdicts = []
         try:
             for k, p in enumerate(pieces):
@@ -650,6 +679,65 @@ class Ctx:
 
     def useq_stream_abort(self):
         _chk(lib().mahip_useq_stream_abort(self.h), "useq_stream_abort")
+
+    # ---- the placement plan on the device (csrc/useq.hip): for stage tests
+    def useq_plan_mem(self, units, names, sub=None):
+        """hand-made unitigs planned on the device.  units: one (len, start, end, members) per unitig as text_format_ug takes them (start / end are not looked at);
+        names: one bytes object per read, or None (no names: the plan refuses); sub: SUB_DT per read or None.  Returns the info dict (useq_plan_last)"""
+        U = len(units)
+        u_len = np.array([u[0] for u in units], dtype=np.uint32)
+        u_n = np.array([len(u[3]) for u in units], dtype=np.uint32)
+        mem = np.array([m for u in units for m in u[3]], dtype=np.uint64)
+        if names is not None:
+            n_seq = len(names)
+            off = np.zeros(n_seq + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64)
+            blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        else:
+            n_seq = 0 if sub is None else len(sub)
+        sub = None if sub is None else np.ascontiguousarray(sub, dtype=SUB_DT)
+        assert sub is None or len(sub) == n_seq
+        info = UseqPlanInfo()
+        _chk(lib().mahip_useq_plan_mem(self.h, U, u_n.ctypes.data, u_len.ctypes.data, mem.ctypes.data, n_seq, None if names is None else blob.ctypes.data,
+                                       None if names is None else off.ctypes.data, None if sub is None else sub.ctypes.data, C.byref(info)), "useq_plan_mem")
+        return _plan_dict(info)
+
+    def useq_plan_last(self):
+        """the info of the context's last placement plan (a refused one included): road, reason, n_utg, n_members, n_reads, n_wanted, name_bytes, blob_bytes,
+        arena_bytes, n_multi, uoff_tiles, ms"""
+        p = UseqPlanInfo()
+        _chk(lib().mahip_useq_plan_last(self.h, C.byref(p)), "useq_plan_last")
+        return _plan_dict(p)
+
+    def useq_plan_download(self):
+        """the plan the context holds -> (uoff [n_utg + 1] u64, per-read plan PLACE_DT, wanted table WANT_DT, the blob its name_off point into)"""
+        p = self.useq_plan_last()
+        uoff = np.zeros(p["n_utg"] + 1, dtype=np.uint64)
+        pl = np.zeros(max(p["n_reads"], 1), dtype=PLACE_DT)
+        want = np.zeros(max(p["n_wanted"], 1), dtype=WANT_DT)
+        names = C.create_string_buffer(max(p["blob_bytes"], 1))
+        _chk(lib().mahip_useq_plan_download(self.h, uoff.ctypes.data, pl.ctypes.data, want.ctypes.data, names), "useq_plan_download")
+        return uoff, pl[:p["n_reads"]], want[:p["n_wanted"]], names.raw[:p["blob_bytes"]]
+
+    def useq_place_text_planned(self):
+        """useq_place_text with the arena and the wanted table of the plan the context holds -> (arena bytes, n_matched, n_dup, n_short)"""
+        L = lib()
+        arena_bytes = self.useq_plan_last()["arena_bytes"]
+        _chk(L.mahip_useq_begin_planned(self.h), "useq_begin_planned")
+        nm, nd, ns = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(L.mahip_useq_place_text_planned(self.h, C.byref(nm), C.byref(nd), C.byref(ns), None), "useq_place_text_planned")
+        out = C.create_string_buffer(max(arena_bytes, 1))
+        _chk(L.mahip_useq_end(self.h, out), "useq_end")
+        return out.raw[:arena_bytes], nm.value, nd.value, ns.value
+
+    def useq_stream_planned(self, pieces, each=None):
+        """useq_stream with the arena and the wanted table of the plan the context holds"""
+        L = lib()
+        arena_bytes = self.useq_plan_last()["arena_bytes"]
+        _chk(L.mahip_fastx_release(self.h), "fastx_release")
+        _chk(L.mahip_useq_begin_planned(self.h), "useq_begin_planned")
+        _chk(L.mahip_useq_stream_begin_planned(self.h), "useq_stream_begin_planned")
+        return self._useq_stream_pieces(list(pieces), arena_bytes, each)
 
     def useq_last(self):
         """which reader the context's last ma_ug_seq used, and why"""

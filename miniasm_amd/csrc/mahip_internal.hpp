@@ -244,6 +244,14 @@ void useq_free(mahip_ctx *c);
 struct UgDevView { uint32_t U, M, n_uarc; const uint32_t *u_n, *u_len, *u_start, *u_end, *u_off; const uint64_t *mem; const void *uarcs; };
 bool ug_dev_view(mahip_ctx *c, UgDevView *v);
 bool useq_dev_arena(mahip_ctx *c, const char **arena, size_t *bytes);
+// the placement plan (useq.hip) and the text writer (text_dev.hpp) read each other's state: the plan takes the names as mahip_text_names left them on the device
+// (gen: how often they were replaced; false: none), the kept intervals of slot 0 in the records' numbering (1: no device memory) and the scan of the members' low
+// words (text_core.h: tc_ug_member_start); the writer takes the plan's uoff when the context holds a plan of the U unitigs with M members that mahip_ug_gen left
+bool text_dev_names(mahip_ctx *c, const char **blob, const uint64_t **off, uint32_t *n_seq, uint64_t *blob_bytes, uint64_t *gen);
+int text_dev_sub(mahip_ctx *c, uint32_t Rn, const uint32_t **d_sub);
+int text_ug_member_scan(mahip_ctx *c, const uint64_t *mem, uint32_t M, uint32_t *low, uint32_t *mscan);
+bool useq_plan_uoff(mahip_ctx *c, uint32_t U, uint32_t M, const uint64_t **d_uoff, uint64_t *tot);
+void useq_plan_drop(mahip_ctx *c); // mahip_ug_gen: the unitigs a plan was made of are gone
 
 // bits needed for x (0 for 0): the width of a radix key that holds values up to x
 static inline int bitlen_u64(uint64_t x) { int b = 0; while (x) ++b, x >>= 1; return b; }

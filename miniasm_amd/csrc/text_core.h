@@ -249,6 +249,10 @@ typedef struct {
 #define TC_FIXED_UG_X (2 + TC_UTG_MAX + 4 * (1 + 11) + 2 * (1 + (1 + 11 + 1 + 11) + 1 + 1) + 1)
 #define TC_FIXED_UG   TC_FIXED_UG_X
 
+/* where member m starts on the unitig whose first member is m0: the reference's uint32_t l, mod 2^32 -- what the `a` lines print (asm.c:100-103) and where the
+ * member's bases go (asm.c:252-258; csrc/useq.hip: the placement plan) */
+TC_HD uint32_t tc_ug_member_start(const uint32_t *mscan, uint32_t m0, uint32_t m) { return mscan[m] - mscan[m0]; }
+
 /* record r of the unitig GFA; returns the '\n' bytes it holds */
 TC_HD uint32_t tc_line_ug(tc_emit_t *e, const tc_ug_t *g, uint64_t r, const tc_names_t *nm, const uint32_t *sub)
 {
@@ -272,7 +276,7 @@ TC_HD uint32_t tc_line_ug(tc_emit_t *e, const tc_ug_t *g, uint64_t r, const tc_n
 		} else if (k == 0) { tc_ug_s(e, i + 1u, (int)circ, len); return circ ? 3u : 1u; }
 		{
 			const uint32_t m0 = g->moff[i], m = m0 + (k - 1u);
-			tc_ug_a(e, i + 1u, (int)circ, g->mscan[m] - g->mscan[m0], g->mem[m], nm, sub);
+			tc_ug_a(e, i + 1u, (int)circ, tc_ug_member_start(g->mscan, m0, m), g->mem[m], nm, sub);
 		}
 		return 1;
 	}

@@ -117,6 +117,14 @@ __global__ __launch_bounds__(256) void k_text_ug_low(const uint64_t *__restrict_
 	for (size_t m = (size_t)blockIdx.x * 256 + threadIdx.x; m < M; m += (size_t)gridDim.x * 256) low[m] = (uint32_t)mem[m];
 }
 
+// low[] and its scan for the members of a set of unitigs: what tc_ug_member_start reads, for the `a` lines and for the placement plan (useq.hip)
+int text_ug_member_scan(mahip_ctx *c, const uint64_t *mem, uint32_t M, uint32_t *low, uint32_t *mscan)
+{
+	hipLaunchKernelGGL(k_text_ug_low, dim3(grid_for(M, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, mem, M, low);
+	HIPCHK(hipGetLastError());
+	return scan_exclusive_u32(c, low, mscan, M, nullptr);
+}
+
 // ctr[3] += 8-byte words (single bytes in front of the first and behind the last aligned address) of a[0 .. n) that hold a NUL byte
 __global__ __launch_bounds__(256) void k_text_count_nul(const char *__restrict__ a, uint64_t n, unsigned long long *ctr)
 {
@@ -146,8 +154,9 @@ struct TextState {
 	hipEvent_t ev[2][2] = {};
 	bool ev_ready = false;
 	uint32_t n_seq = 0;
-	uint64_t max_name = 0;
+	uint64_t max_name = 0, names_bytes = 0;
 	bool names = false, has_del = false;
+	uint64_t names_gen = 0; // mahip_text_names calls so far: the placement plan's table points into the blob (useq.hip)
 	double names_ms = 0;
 	// what prepare left for emit
 	bool planned = false;
@@ -190,7 +199,7 @@ extern "C" int mahip_text_names(mahip_ctx_t *c, const char *blob, const uint64_t
 	HIPCHK(hipSetDevice(c->dev));
 	TextState *t = text_of(c);
 	const double t0 = TieLaps::now();
-	t->names = false;
+	t->names = false; ++t->names_gen;
 	const uint64_t bytes = n_seq ? off[n_seq] : 0;
 	uint64_t mx = 0;
 	for (uint32_t i = 0; i < n_seq; ++i) { const uint64_t l = off[i + 1] - off[i]; if (l > mx) mx = l; }
@@ -203,7 +212,7 @@ extern "C" int mahip_text_names(mahip_ctx_t *c, const char *blob, const uint64_t
 		CHK(dev_reserve(c, t->del, (size_t)n_seq + 16));
 		CHK(xfer_copy(c, t->del.p, (void*)del, n_seq, 1));
 	}
-	t->n_seq = n_seq; t->max_name = mx; t->names = true;
+	t->n_seq = n_seq; t->max_name = mx; t->names_bytes = bytes; t->names = true;
 	t->names_ms = (TieLaps::now() - t0) * 1e3;
 	return 0;
 }
@@ -292,6 +301,17 @@ static int text_sub_export(mahip_ctx *c, TextState *t, uint32_t Rn, const uint32
 	return 0;
 }
 
+// ---- what the placement plan (useq.hip) reads of the writer's state: the names as they lie on the device, the kept intervals as the records see them
+bool text_dev_names(mahip_ctx *c, const char **blob, const uint64_t **off, uint32_t *n_seq, uint64_t *blob_bytes, uint64_t *gen)
+{
+	TextState *t = (TextState*)c->text;
+	if (gen) *gen = t ? t->names_gen : 0;
+	if (!t || !t->names) return false;
+	*blob = (const char*)t->blob.p; *off = (const uint64_t*)t->off.p; *n_seq = t->n_seq; *blob_bytes = t->names_bytes;
+	return true;
+}
+int text_dev_sub(mahip_ctx *c, uint32_t Rn, const uint32_t **d_sub) { return text_sub_export(c, text_of(c), Rn, d_sub); }
+
 extern "C" int mahip_text_prepare(mahip_ctx_t *c, int kind, int have_sub, mahip_text_info_t *info)
 {
 	HIPCHK(hipSetDevice(c->dev));
@@ -336,7 +356,8 @@ extern "C" int mahip_text_prepare(mahip_ctx_t *c, int kind, int have_sub, mahip_
 
 // ---- the unitig GFA
 // unitigs on the device (moff == 0: computed here from u_n), the arena (0: none), both as the caller holds them
-struct TextUgSrc { uint32_t U, M; const uint32_t *u_n, *u_len, *u_start, *u_end, *moff; const uint64_t *mem; const char *arena; uint64_t arena_bytes; };
+// plan_uoff: where every unitig's bases start, on the device already -- the placement plan of these unitigs (useq.hip); 0: made here
+struct TextUgSrc { uint32_t U, M; const uint32_t *u_n, *u_len, *u_start, *u_end, *moff; const uint64_t *mem; const char *arena; uint64_t arena_bytes; const uint64_t *plan_uoff; uint64_t plan_tot; };
 
 // links: the unitig arcs in the reference's order (host); counts: 2 U words, arcs leaving each unitig end (host; 0: counted here from the links).  The record space of
 // text_core.h: tc_ug_t is built on the device, the refusals are decided, then text_plan runs as for every kind
@@ -347,7 +368,10 @@ static int text_plan_ug(mahip_ctx *c, TextState *t, const TextUgSrc &s, const as
 	const uint32_t U = s.U, M = s.M;
 	info->seq_chunk = MA_TEXT_SEQ_CHUNK;
 	std::vector<uint64_t> uoff;
-	if (with_seq) { // where every unitig's bases start: the lengths come down (4 U bytes), the offsets go up
+	if (with_seq && s.plan_uoff) { // where every unitig's bases start: the plan that placed them holds it
+		if (!s.arena || s.arena_bytes != s.plan_tot) return text_host_road(t, info, MAHIP_TEXT_NO_SEQ, "sequences were asked for, but this context holds no finished arena of these unitigs");
+		info->n_seq_bytes = s.plan_tot - U;
+	} else if (with_seq) { // no plan: the lengths come down (4 U bytes), the offsets go up
 		std::vector<uint32_t> len(U);
 		uint64_t tot = 0;
 		if (U) HIPCHK(hipMemcpyAsync(len.data(), s.u_len, (size_t)U * 4, hipMemcpyDeviceToHost, c->st));
@@ -375,14 +399,13 @@ static int text_plan_ug(mahip_ctx *c, TextState *t, const TextUgSrc &s, const as
 	CHK(scan_exclusive_u32(c, P<uint32_t>(t->ug_cnt), P<uint32_t>(t->ug_rbase), U, nullptr));
 	const uint32_t *d_moff = s.moff;
 	if (!d_moff) { CHK(scan_exclusive_u32(c, s.u_n, P<uint32_t>(t->ug_moff), U, nullptr)); d_moff = P<uint32_t>(t->ug_moff); }
-	hipLaunchKernelGGL(k_text_ug_low, dim3(grid_for(M, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, s.mem, M, P<uint32_t>(t->ug_low));
-	CHK(scan_exclusive_u32(c, P<uint32_t>(t->ug_low), P<uint32_t>(t->ug_mscan), M, nullptr));
+	CHK(text_ug_member_scan(c, s.mem, M, P<uint32_t>(t->ug_low), P<uint32_t>(t->ug_mscan)));
 	if (with_seq && s.arena_bytes) // (asm.c:84 prints the sequence with %s: a NUL byte would end the S line early -- not imitated, the host road takes such an arena)
 		hipLaunchKernelGGL(k_text_count_nul, dim3(grid_for(s.arena_bytes / 8 + 1, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, s.arena, s.arena_bytes, ctr);
 	HIPCHK(hipGetLastError());
 	if (n_links) CHK(xfer_copy(c, t->ug_links.p, (void*)links, (size_t)n_links * 16, 1));
 	if (U) CHK(xfer_copy(c, t->ug_ecnt.p, (void*)counts, (size_t)2 * U * 4, 1));
-	if (with_seq) CHK(xfer_copy(c, t->ug_uoff.p, (void*)uoff.data(), ((size_t)U + 1) * 8, 1));
+	if (with_seq && !s.plan_uoff) CHK(xfer_copy(c, t->ug_uoff.p, (void*)uoff.data(), ((size_t)U + 1) * 8, 1));
 	unsigned long long h_ctr[4] = {0, 0, 0, 0};
 	HIPCHK(hipMemcpyAsync(h_ctr, t->ctr.p, 32, hipMemcpyDeviceToHost, c->st));
 	HIPCHK(hipStreamSynchronize(c->st));
@@ -392,7 +415,7 @@ static int text_plan_ug(mahip_ctx *c, TextState *t, const TextUgSrc &s, const as
 	tc_ug_t &g = t->in.ug;
 	g.U = U; g.n_links = n_links; g.chunk = MA_TEXT_SEQ_CHUNK; g.n_unit_rec = h_ctr[2];
 	g.u_n = s.u_n; g.u_len = s.u_len; g.u_start = s.u_start; g.u_end = s.u_end; g.moff = d_moff; g.rbase = P<uint32_t>(t->ug_rbase); g.mscan = P<uint32_t>(t->ug_mscan);
-	g.links = P<uint32_t>(t->ug_links); g.cnt = P<uint32_t>(t->ug_ecnt); g.mem = s.mem; g.uoff = with_seq ? (const uint64_t*)t->ug_uoff.p : nullptr; g.arena = with_seq ? s.arena : nullptr;
+	g.links = P<uint32_t>(t->ug_links); g.cnt = P<uint32_t>(t->ug_ecnt); g.mem = s.mem; g.uoff = !with_seq ? nullptr : s.plan_uoff ? s.plan_uoff : (const uint64_t*)t->ug_uoff.p; g.arena = with_seq ? s.arena : nullptr;
 	info->laps_ms[1] += (TieLaps::now() - t0) * 1e3;
 	return text_plan(c, t, MAHIP_TEXT_UG, nullptr, n, d_sub, slab_req, info);
 }
@@ -418,8 +441,9 @@ extern "C" int mahip_text_prepare_ug(mahip_ctx_t *c, int have_sub, const asg_arc
 		if (rc < 0) return -1;
 		if (rc > 0) return text_host_road(t, info, MAHIP_TEXT_NOMEM, "no device memory for the kept intervals");
 	}
-	TextUgSrc s = {v.U, v.M, v.u_n, v.u_len, v.u_start, v.u_end, v.u_off, v.mem, nullptr, 0};
+	TextUgSrc s = {v.U, v.M, v.u_n, v.u_len, v.u_start, v.u_end, v.u_off, v.mem, nullptr, 0, nullptr, 0};
 	if (with_seq) { size_t bytes = 0; if (useq_dev_arena(c, &s.arena, &bytes)) s.arena_bytes = bytes; else s.arena = nullptr; }
+	if (with_seq && !useq_plan_uoff(c, v.U, v.M, &s.plan_uoff, &s.plan_tot)) s.plan_uoff = nullptr;
 	info->laps_ms[1] = (TieLaps::now() - t0) * 1e3;
 	return text_plan_ug(c, t, s, links, n_links, nullptr, d_sub, with_seq, 0, info);
 }
@@ -551,7 +575,7 @@ extern "C" int mahip_text_format_ug_mem(mahip_ctx_t *c, uint32_t n_utg, const ui
 	}
 	info->laps_ms[1] = (TieLaps::now() - t0) * 1e3;
 	TextUgSrc s = {n_utg, (uint32_t)M, P<uint32_t>(t->ug_un), P<uint32_t>(t->ug_ulen), P<uint32_t>(t->ug_ustart), P<uint32_t>(t->ug_uend), nullptr, (const uint64_t*)t->ug_mem.p,
-	               arena ? (const char*)t->ug_arena.p : nullptr, arena ? arena_bytes : 0};
+	               arena ? (const char*)t->ug_arena.p : nullptr, arena ? arena_bytes : 0, nullptr, 0};
 	CHK(text_plan_ug(c, t, s, links, n_links, counts, sub ? P<uint32_t>(t->sub) : nullptr, with_seq, slab, info));
 	if (info->road != MAHIP_TEXT_ROAD_DEVICE) return 0; // a refusal: info->reason says why, there is no text
 	TextMemSink m = {(char*)malloc(1), 0, 1};

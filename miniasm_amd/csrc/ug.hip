@@ -123,6 +123,7 @@ extern "C" int mahip_ug_gen(mahip_ctx_t *c, uint32_t *n_utg, uint32_t *n_members
 	const uint32_t R = graph_nseq(c), V = 2 * R;
 	const size_t A = c->n_arc;
 	b->n_utg = b->n_mem = b->n_uarc = 0;
+	useq_plan_drop(c); // (a placement plan of the unitigs before)
 	if (n_utg) *n_utg = 0;
 	if (n_members) *n_members = 0;
 	if (n_uarc) *n_uarc = 0;

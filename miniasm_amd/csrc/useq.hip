@@ -5,6 +5,7 @@
 // complement through a 128-entry table in LDS.  HBM-bound by construction (bytes in = bytes out); the unitig arena stays in
 // HBM until the last batch and comes back once.
 #include "mahip_internal.hpp"
+#include "text_core.h"
 
 struct UseqBufs {
 	DevBuf arena, seq, jobs; size_t arena_bytes = 0;
@@ -18,6 +19,14 @@ struct UseqBufs {
 	DevBuf fw_ctr, fw_list, fw_seen;
 	bool fw_active = false, fw_ended = false; size_t fw_n_want = 0, fw_n = 0, fw_carry_off = 0, fw_carry = 0, fw_cap = 0; uint32_t fw_mask = 0; double fw_t_place = 0;
 	mahip_useq_stream_report_t fw_rep = {};
+	// the wanted table the lookup and the placement read: the uploaded one (fx_want, fx_wname) or the plan's (pl_want, the blob of mahip_text_names)
+	const mahip_useq_want_t *w_want = nullptr; const unsigned char *w_names = nullptr;
+	// the placement plan (third part of this file): unitig offsets and the tile sums of their scan, first member of every unitig, the members' low words and their
+	// scan, per read its member count and its place, wanted flags and their scan, the wanted table, counters; hand-made unitigs and intervals of the stage entry
+	DevBuf pl_uoff, pl_bsum, pl_moff, pl_low, pl_mscan, pl_cnt, pl_place, pl_flag, pl_pos, pl_want, pl_ctr, pl_un, pl_ulen, pl_mem, pl_sub;
+	bool pl_valid = false, pl_ctx = false; // pl_ctx: made of the unitigs mahip_ug_gen left in the context (mahip_useq_plan), not of hand-made ones
+	uint64_t pl_names_gen = 0, pl_bad = 0; const unsigned char *pl_blob = nullptr;
+	mahip_useq_plan_info_t pl_info = {};
 };
 static void fx_drop(mahip_ctx *c, UseqBufs *b);
 
@@ -32,6 +41,8 @@ void useq_free(mahip_ctx *c)
 	UseqBufs *b = (UseqBufs*)c->useq;
 	if (!b) return;
 	dev_free(c, b->arena); dev_free(c, b->seq); dev_free(c, b->jobs);
+	DevBuf *plan[] = {&b->pl_uoff, &b->pl_bsum, &b->pl_moff, &b->pl_low, &b->pl_mscan, &b->pl_cnt, &b->pl_place, &b->pl_flag, &b->pl_pos, &b->pl_want, &b->pl_ctr, &b->pl_un, &b->pl_ulen, &b->pl_mem, &b->pl_sub};
+	for (DevBuf *d : plan) dev_free(c, *d);
 	fx_drop(c, b);
 	delete b;
 	c->useq = nullptr;
@@ -459,6 +470,7 @@ static void fx_drop(mahip_ctx *c, UseqBufs *b)
 	DevBuf *all[] = {&b->fx_text, &b->fx_gcnt, &b->fx_gpos, &b->fx_ls, &b->fx_hdr, &b->fx_hpos, &b->fx_recl, &b->fx_ctr, &b->fx_want, &b->fx_wname, &b->fx_whash, &b->fx_tab, &b->fx_win, &b->fw_ctr, &b->fw_list, &b->fw_seen};
 	for (DevBuf *d : all) dev_free(c, *d);
 	b->fx_n = 0; b->fx_loaded = b->fx_regular = false; b->fw_active = false;
+	b->w_want = nullptr; b->w_names = nullptr;
 }
 
 static int fx_reserve_text(mahip_ctx *c, size_t nbytes)
@@ -616,7 +628,25 @@ extern "C" int mahip_fastx_name_spans(mahip_ctx_t *c, uint64_t *off, uint32_t *l
 
 static double fx_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + ts.tv_nsec * 1e-9; }
 
-// the wanted reads, their names and the table over them on the device (once per file, once per stream); win[] starts all zero.  *cap = slots of the table
+// the table over the wanted reads b->w_want / b->w_names, which are on the device (uploaded below, or the plan's); win[] starts all zero.  *cap = slots of the table
+static int fx_want_table(mahip_ctx *c, UseqBufs *b, const char *who, size_t n_wanted, uint32_t *cap_out)
+{
+	if (n_wanted >= 0x40000000ull) { mahip_set_error("%s: too many wanted reads", who); return -1; }
+	uint32_t cap = 64; while (cap < 2 * n_wanted) cap <<= 1;
+	CHK(dev_reserve(c, b->fx_whash, (n_wanted ? n_wanted : 1) * 8));
+	CHK(dev_reserve(c, b->fx_tab, (size_t)cap * 4)); CHK(dev_reserve(c, b->fx_win, (n_wanted ? n_wanted : 1) * 4));
+	HIPCHK(hipMemsetAsync(b->fx_tab.p, 0, (size_t)cap * 4, c->st));
+	if (n_wanted) HIPCHK(hipMemsetAsync(b->fx_win.p, 0, n_wanted * 4, c->st));
+	if (n_wanted) {
+		ProfScope ps(c, "k_fx_tab_build", 0);
+		hipLaunchKernelGGL(k_fx_tab_build, dim3(grid_for(n_wanted, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, b->w_want, b->w_names, (uint32_t)n_wanted,
+		                   P<uint64_t>(b->fx_whash), P<uint32_t>(b->fx_tab), cap - 1);
+		HIPCHK(hipGetLastError());
+	}
+	*cap_out = cap;
+	return 0;
+}
+// the wanted reads and their names from host memory to the device (once per file, once per stream), then the table
 static int fx_want_upload(mahip_ctx *c, UseqBufs *b, const char *who, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes, uint32_t *cap_out)
 {
 	if (n_wanted >= 0x40000000ull) { mahip_set_error("%s: too many wanted reads", who); return -1; }
@@ -624,23 +654,15 @@ static int fx_want_upload(mahip_ctx *c, UseqBufs *b, const char *who, const mahi
 		if (wanted[w].name_off + wanted[w].name_len > name_bytes || wanted[w].dst_off + wanted[w].len > b->arena_bytes || (!wanted[w].whole && wanted[w].s > wanted[w].e)) {
 			mahip_set_error("%s: wanted read %zu reaches outside the names or the arena", who, w); return -1;
 		}
-	uint32_t cap = 64; while (cap < 2 * n_wanted) cap <<= 1;
-	CHK(dev_reserve(c, b->fx_want, (n_wanted ? n_wanted : 1) * sizeof(mahip_useq_want_t))); CHK(dev_reserve(c, b->fx_wname, name_bytes + 64)); CHK(dev_reserve(c, b->fx_whash, (n_wanted ? n_wanted : 1) * 8));
-	CHK(dev_reserve(c, b->fx_tab, (size_t)cap * 4)); CHK(dev_reserve(c, b->fx_win, (n_wanted ? n_wanted : 1) * 4));
+	CHK(dev_reserve(c, b->fx_want, (n_wanted ? n_wanted : 1) * sizeof(mahip_useq_want_t))); CHK(dev_reserve(c, b->fx_wname, name_bytes + 64));
 	if (n_wanted) HIPCHK(hipMemcpyAsync(b->fx_want.p, wanted, n_wanted * sizeof(mahip_useq_want_t), hipMemcpyHostToDevice, c->st));
 	if (name_bytes) HIPCHK(hipMemcpyAsync(b->fx_wname.p, names, name_bytes, hipMemcpyHostToDevice, c->st));
-	HIPCHK(hipMemsetAsync(b->fx_tab.p, 0, (size_t)cap * 4, c->st));
-	if (n_wanted) HIPCHK(hipMemsetAsync(b->fx_win.p, 0, n_wanted * 4, c->st));
-	if (n_wanted) {
-		ProfScope ps(c, "k_fx_tab_build", 0);
-		hipLaunchKernelGGL(k_fx_tab_build, dim3(grid_for(n_wanted, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (uint32_t)n_wanted,
-		                   P<uint64_t>(b->fx_whash), P<uint32_t>(b->fx_tab), cap - 1);
-		HIPCHK(hipGetLastError());
-	}
-	*cap_out = cap;
-	return 0;
+	b->w_want = (const mahip_useq_want_t*)b->fx_want.p; b->w_names = (const unsigned char*)b->fx_wname.p;
+	return fx_want_table(c, b, who, n_wanted, cap_out);
 }
+static int pl_want_planned(mahip_ctx *c, UseqBufs *b, const char *who, size_t *n_wanted, uint32_t *cap_out); // the plan's table in their place (third part of this file)
 
+static int fx_place_wanted(mahip_ctx *c, UseqBufs *b, size_t n_wanted, uint32_t cap, double t0, uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms);
 extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes,
                                      uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms)
 {
@@ -654,11 +676,30 @@ extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wa
 	const double t0 = fx_now();
 	uint32_t cap = 0;
 	CHK(fx_want_upload(c, b, "mahip_useq_place_text", wanted, n_wanted, names, name_bytes, &cap));
+	return fx_place_wanted(c, b, n_wanted, cap, t0, n_matched, n_dup, n_short, laps_ms);
+}
+extern "C" int mahip_useq_place_text_planned(mahip_ctx_t *c, uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	if (!b->fx_regular) { mahip_set_error("mahip_useq_place_text_planned: no text in the regular form (mahip_fastx_index)"); return -1; }
+	*n_matched = *n_dup = *n_short = 0;
+	if (laps_ms) laps_ms[0] = laps_ms[1] = 0;
+	const double t0 = fx_now();
+	size_t n_wanted = 0;
+	uint32_t cap = 0;
+	CHK(pl_want_planned(c, b, "mahip_useq_place_text_planned", &n_wanted, &cap));
+	if (n_wanted == 0 || b->fx_R == 0) return 0;
+	return fx_place_wanted(c, b, n_wanted, cap, t0, n_matched, n_dup, n_short, laps_ms);
+}
+// everything behind the table: lookup, the SHORT_READ verdict, placement
+static int fx_place_wanted(mahip_ctx *c, UseqBufs *b, size_t n_wanted, uint32_t cap, double t0, uint64_t *n_matched, uint64_t *n_dup, uint64_t *n_short, double *laps_ms)
+{
 	HIPCHK(hipMemsetAsync(b->fx_ctr.p, 0, FX_NCTR * 8, c->st));
 	const FxText x = fx_view(b);
 	{
 		ProfScope ps(c, "k_fx_probe", 0);
-		hipLaunchKernelGGL(k_fx_probe, dim3(grid_for(b->fx_R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p, (const uint64_t*)b->fx_whash.p,
+		hipLaunchKernelGGL(k_fx_probe, dim3(grid_for(b->fx_R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, b->w_want, b->w_names, (const uint64_t*)b->fx_whash.p,
 		                   (const uint32_t*)b->fx_tab.p, cap - 1, P<uint32_t>(b->fx_win), P<unsigned long long>(b->fx_ctr));
 		HIPCHK(hipGetLastError());
 	}
@@ -670,7 +711,7 @@ extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wa
 	if (h[FX_SHORT]) return 0; // the caller falls back: nothing has touched the arena
 	{
 		ProfScope ps(c, "k_fx_place", 0);
-		hipLaunchKernelGGL(k_fx_place, dim3(grid_for(n_wanted, 1, 65536)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (uint32_t)n_wanted, (const uint32_t*)b->fx_win.p, (unsigned char*)b->arena.p);
+		hipLaunchKernelGGL(k_fx_place, dim3(grid_for(n_wanted, 1, 65536)), dim3(256), 0, c->st, x, b->w_want, (uint32_t)n_wanted, (const uint32_t*)b->fx_win.p, (unsigned char*)b->arena.p);
 		HIPCHK(hipGetLastError());
 	}
 	if (laps_ms) { HIPCHK(hipStreamSynchronize(c->st)); laps_ms[1] = (fx_now() - t1) * 1e3; }
@@ -678,6 +719,7 @@ extern "C" int mahip_useq_place_text(mahip_ctx_t *c, const mahip_useq_want_t *wa
 }
 
 // ------------------------------------------------------------------------------------------------ the streamed reader (include/mahip.h)
+static int fxw_begin(mahip_ctx *c, UseqBufs *b, size_t n_wanted, uint32_t cap);
 extern "C" int mahip_useq_stream_begin(mahip_ctx_t *c, const mahip_useq_want_t *wanted, size_t n_wanted, const char *names, size_t name_bytes)
 {
 	HIPCHK(hipSetDevice(c->dev));
@@ -686,6 +728,22 @@ extern "C" int mahip_useq_stream_begin(mahip_ctx_t *c, const mahip_useq_want_t *
 	b->fw_active = false;
 	uint32_t cap = 0;
 	CHK(fx_want_upload(c, b, "mahip_useq_stream_begin", wanted, n_wanted, names, name_bytes, &cap));
+	return fxw_begin(c, b, n_wanted, cap);
+}
+extern "C" int mahip_useq_stream_begin_planned(mahip_ctx_t *c)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	b->fx_loaded = b->fx_regular = false;
+	b->fw_active = false;
+	size_t n_wanted = 0;
+	uint32_t cap = 0;
+	CHK(pl_want_planned(c, b, "mahip_useq_stream_begin_planned", &n_wanted, &cap));
+	return fxw_begin(c, b, n_wanted, cap);
+}
+// a stream over the table that is in place: the names seen so far, the window's state
+static int fxw_begin(mahip_ctx *c, UseqBufs *b, size_t n_wanted, uint32_t cap)
+{
 	CHK(dev_reserve(c, b->fw_ctr, FXW_NCTR * 8)); CHK(dev_reserve(c, b->fw_seen, n_wanted ? n_wanted : 1));
 	HIPCHK(hipMemsetAsync(b->fw_seen.p, 0, n_wanted ? n_wanted : 1, c->st));
 	HIPCHK(hipStreamSynchronize(c->st)); // the caller may reuse wanted / names
@@ -804,7 +862,7 @@ extern "C" int mahip_useq_stream_piece_mem(mahip_ctx_t *c, const void *text, siz
 		HIPCHK(hipGetLastError());
 		rep->laps_ms[1] += ((t1 = fx_now()) - t0) * 1e3; t0 = t1;
 		// ---- the names of the prefix's records against the table; the wanted reads that matched go to the list
-		hipLaunchKernelGGL(k_fxw_probe, dim3(grid_for(fq ? L / 4 : L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const unsigned char*)b->fx_wname.p,
+		hipLaunchKernelGGL(k_fxw_probe, dim3(grid_for(fq ? L / 4 : L, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, x, b->w_want, b->w_names,
 		                   (const uint64_t*)b->fx_whash.p, (const uint32_t*)b->fx_tab.p, b->fw_mask, P<uint32_t>(b->fx_win), (const unsigned char*)b->fw_seen.p, P<uint32_t>(b->fw_list), ctr);
 		HIPCHK(hipGetLastError());
 		CHK(fxw_counters(c, b, h));
@@ -822,7 +880,7 @@ extern "C" int mahip_useq_stream_piece_mem(mahip_ctx_t *c, const void *text, siz
 		if (h[FXW_NLIST] >= list_cap) { mahip_set_error("mahip_useq_stream_piece_mem: the match list overflowed"); return -1; } // (cannot happen: see list_cap)
 		if (h[FXW_NLIST]) {
 			ProfScope pp(c, "k_fxw_place", 0);
-			hipLaunchKernelGGL(k_fxw_place, dim3(grid_for(h[FXW_NLIST], 1, 65536)), dim3(256), 0, c->st, x, (const mahip_useq_want_t*)b->fx_want.p, (const uint32_t*)b->fw_list.p, (uint32_t)h[FXW_NLIST],
+			hipLaunchKernelGGL(k_fxw_place, dim3(grid_for(h[FXW_NLIST], 1, 65536)), dim3(256), 0, c->st, x, b->w_want, (const uint32_t*)b->fw_list.p, (uint32_t)h[FXW_NLIST],
 			                   P<uint32_t>(b->fx_win), P<unsigned char>(b->fw_seen), (unsigned char*)b->arena.p);
 			HIPCHK(hipGetLastError());
 		}
@@ -865,6 +923,314 @@ extern "C" int mahip_useq_stream_abort(mahip_ctx_t *c)
 	return 0;
 }
 extern "C" int mahip_useq_stream_last(mahip_ctx_t *c, mahip_useq_stream_report_t *out) { *out = useq_bufs(c)->fw_rep; return 0; }
+
+// ================================================================================================ the placement plan on the device (include/mahip.h)
+// asm.c:248-260 and host/unitig_gfa.c: ug_seq_wanted over arrays that lie in HBM already: unitigs (u_len, first member, member words), names (blob, off), kept
+// intervals.  Index work only:
+//   uoff    exclusive scan of u_len[i] + 1 in 64 bits: one tile of 2048 values per block -- every thread sums 8, a wave scan over the thread sums (both halves of the
+//           word travel through the cross-lane shifts together), the four wave totals through LDS.  More than one tile: the tile sums first, ONE block scans them
+//           in place (256 at a time, carrying the running total), then every tile scans its values on top of its base
+//   start   tc_ug_member_start over the scan of the members' low words (text_dev.hpp: text_ug_member_scan), as the `a` lines
+//   scatter one thread per member: its unitig by bisection over the first-member array, its read's counter up by one (vector atomic); the first member to arrive
+//           writes the read's place, any other is counted: MULTI
+//   wanted  a flag per read (len != 0 and a name), scan_exclusive_u32, one table entry per flagged read at its scanned position: ascending read id
+// The table's names stay where mahip_text_names put them: name_off is the read's offset in THAT blob, and the lookup kernels read `names + name_off` whichever
+// blob `names` is (k_fx_tab_build, fx_lookup).
+#define PL_ITEMS 8u
+#define PL_TILE (256u * PL_ITEMS)
+enum { PL_TOT = 0, PL_MULTI, PL_BAD, PL_NAMEB, PL_OOB, PL_NCTR = 8 };
+
+__device__ __forceinline__ uint64_t wv_scan_incl_u64(uint64_t x, unsigned lane)
+{
+	for (int o = 1; o < 64; o <<= 1) { // (every lane of the wave is here)
+		const uint32_t lo = __shfl_up((uint32_t)x, o, 64), hi = __shfl_up((uint32_t)(x >> 32), o, 64);
+		if (lane >= (unsigned)o) x += (uint64_t)hi << 32 | lo;
+	}
+	return x;
+}
+// block-wide exclusive scan of one u64 per thread (256 threads); s_wave: 4 words of LDS
+__device__ __forceinline__ uint64_t block_excl_scan_u64(uint64_t x, uint64_t *s_wave, uint64_t *total)
+{
+	const unsigned lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const uint64_t incl = wv_scan_incl_u64(x, lane);
+	if (lane == 63) s_wave[wave] = incl;
+	__syncthreads();
+	uint64_t base = 0, tot = 0;
+	for (unsigned w = 0; w < 4; ++w) { const uint64_t v = s_wave[w]; if (w < wave) base += v; tot += v; }
+	__syncthreads();
+	*total = tot;
+	return base + incl - x;
+}
+// the 8 values of this thread in tile blockIdx.x: u_len[i] + 1, 0 behind the end; returns their sum
+__device__ __forceinline__ uint64_t pl_tile_load(const uint32_t *__restrict__ u_len, uint32_t U, uint64_t v[PL_ITEMS])
+{
+	const uint64_t base = (uint64_t)blockIdx.x * PL_TILE + threadIdx.x * PL_ITEMS;
+	uint64_t s = 0;
+	for (uint32_t k = 0; k < PL_ITEMS; ++k) { v[k] = base + k < U ? (uint64_t)u_len[base + k] + 1u : 0u; s += v[k]; }
+	return s;
+}
+__global__ __launch_bounds__(256) void k_pl_uoff_sums(const uint32_t *__restrict__ u_len, uint32_t U, uint64_t *__restrict__ bsum)
+{
+	__shared__ uint64_t s_wave[4];
+	uint64_t v[PL_ITEMS], tot;
+	block_excl_scan_u64(pl_tile_load(u_len, U, v), s_wave, &tot);
+	if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
+}
+__global__ __launch_bounds__(256) void k_pl_uoff_bases(uint64_t *__restrict__ bsum, uint32_t nb) // one block, in place
+{
+	__shared__ uint64_t s_wave[4];
+	uint64_t run = 0;
+	for (uint32_t b0 = 0; b0 < nb; b0 += 256) { // (the whole block)
+		const uint32_t i = b0 + threadIdx.x;
+		const uint64_t x = i < nb ? bsum[i] : 0;
+		uint64_t tot;
+		const uint64_t ex = block_excl_scan_u64(x, s_wave, &tot);
+		if (i < nb) bsum[i] = run + ex;
+		run += tot;
+	}
+}
+// uoff[i] for the tile's unitigs; the thread that holds the last unitig also writes uoff[U] = ctr[PL_TOT] = the arena's bytes.  bbase == 0: a single tile
+__global__ __launch_bounds__(256) void k_pl_uoff_down(const uint32_t *__restrict__ u_len, uint32_t U, const uint64_t *__restrict__ bbase, uint64_t *__restrict__ uoff, unsigned long long *__restrict__ ctr)
+{
+	__shared__ uint64_t s_wave[4];
+	uint64_t v[PL_ITEMS], tot;
+	const uint64_t base = (uint64_t)blockIdx.x * PL_TILE + threadIdx.x * PL_ITEMS;
+	uint64_t run = block_excl_scan_u64(pl_tile_load(u_len, U, v), s_wave, &tot) + (bbase ? bbase[blockIdx.x] : 0);
+	for (uint32_t k = 0; k < PL_ITEMS; ++k) {
+		if (base + k < U) uoff[base + k] = run;
+		run += v[k];
+		if (base + k + 1 == U) { uoff[U] = run; ctr[PL_TOT] = run; }
+	}
+}
+// cnt[read] += 1 per member; place[read] = (utg, start, len, ori) by the member that came first
+__global__ __launch_bounds__(256) void k_pl_scatter(const uint64_t *__restrict__ mem, uint32_t M, const uint32_t *__restrict__ moff, uint32_t U, const uint32_t *__restrict__ mscan, uint32_t n_reads,
+                                                    uint32_t *__restrict__ cnt, uint4 *__restrict__ place, unsigned long long *__restrict__ ctr)
+{
+	uint64_t multi = 0, bad = 0;
+	for (uint64_t m = (uint64_t)blockIdx.x * 256u + threadIdx.x; m < M; m += (uint64_t)gridDim.x * 256u) {
+		const uint64_t w = mem[m];
+		const uint32_t read = (uint32_t)(w >> 33);
+		uint32_t lo = 0, hi = U; // the last unitig whose first member is not behind m (a unitig without members shares its successor's first member and lies in front of it)
+		while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (moff[mid] <= m) lo = mid; else hi = mid; }
+		if (read >= n_reads) { ++bad; continue; }
+		if (atomicAdd(&cnt[read], 1u) != 0u) { ++multi; continue; } // asm.c:255 asserts here
+		place[read] = make_uint4(lo, tc_ug_member_start(mscan, moff[lo], (uint32_t)m), (uint32_t)w, (uint32_t)(w >> 32) & 1u); // asm.c:254-258
+	}
+	blk_add_u64(ctr + PL_MULTI, multi);
+	blk_add_u64(ctr + PL_BAD, bad);
+}
+// flag[r] = read r is wanted: it sits on a unitig with len != 0 and has a name (host/unitig_gfa.c: ug_seq_wanted); ctr[PL_NAMEB] += the bytes of their names
+__global__ __launch_bounds__(256) void k_pl_flag(const uint4 *__restrict__ place, const uint64_t *__restrict__ off, uint32_t n_reads, uint32_t *__restrict__ flag, unsigned long long *__restrict__ ctr)
+{
+	uint64_t nb = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * 256u) {
+		const uint64_t l = off[r + 1] - off[r];
+		const uint32_t f = place[r].z != 0u && l != 0u;
+		flag[r] = f;
+		if (f) nb += l;
+	}
+	blk_add_u64(ctr + PL_NAMEB, nb);
+}
+// the table entry of every wanted read at its scanned position; ctr[PL_OOB] += entries that reach outside the arena or whose interval is upside down (the planned
+// readers refuse such a plan: the placement trusts the table).  sub: word 2 r = s | del << 31, word 2 r + 1 = e; 0: whole records
+__global__ __launch_bounds__(256) void k_pl_want(const uint4 *__restrict__ place, const uint64_t *__restrict__ off, const uint64_t *__restrict__ uoff, const uint32_t *__restrict__ sub,
+                                                 const uint32_t *__restrict__ flag, const uint32_t *__restrict__ pos, uint32_t n_reads, uint32_t U, mahip_useq_want_t *__restrict__ want,
+                                                 unsigned long long *__restrict__ ctr)
+{
+	const uint64_t tot = uoff[U];
+	uint64_t oob = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x; r < n_reads; r += (uint64_t)gridDim.x * 256u) {
+		if (!flag[r]) continue;
+		const uint4 p = place[r];
+		mahip_useq_want_t w;
+		w.dst_off = uoff[p.x] + p.y; w.name_off = off[r]; w.name_len = (uint32_t)(off[r + 1] - off[r]);
+		w.len = p.z; w.s = sub ? sub[2 * r] & 0x7fffffffu : 0u; w.e = sub ? sub[2 * r + 1] : 0u; w.rev = p.w; w.whole = sub == nullptr;
+		oob += w.dst_off + w.len > tot || w.s > w.e;
+		want[pos[r]] = w;
+	}
+	blk_add_u64(ctr + PL_OOB, oob);
+}
+
+extern "C" const char *mahip_useq_plan_reason_name(int reason)
+{
+	static const char *const nm[] = {"ok", "no unitigs on the device", "the names are not on the device", "a read sits on a unitig more than once", "no device memory for the plan", "MA_USEQ_PLAN_HOST is set"};
+	return reason >= 0 && reason < (int)(sizeof(nm) / sizeof(nm[0])) ? nm[reason] : "?";
+}
+void useq_plan_drop(mahip_ctx *c) { if (c->useq) ((UseqBufs*)c->useq)->pl_valid = false; }
+static bool pl_forced() { const char *e = getenv("MA_USEQ_PLAN_HOST"); return e && atoi(e) != 0; }
+static int pl_refuse(UseqBufs *b, mahip_useq_plan_info_t *info, int reason, double t0)
+{
+	info->road = MAHIP_PLAN_ROAD_HOST; info->reason = reason; info->ms = (fx_now() - t0) * 1e3;
+	b->pl_valid = false; b->pl_info = *info;
+	return 0;
+}
+
+struct PlanSrc { uint32_t U, M, n_reads; const uint32_t *u_len, *moff; const uint64_t *mem; const unsigned char *blob; const uint64_t *off; uint64_t blob_bytes, names_gen; const uint32_t *sub; bool ctx; };
+
+// the plan itself: everything is queued, the host waits once (for the counters)
+static int pl_run(mahip_ctx *c, UseqBufs *b, const PlanSrc &s, mahip_useq_plan_info_t *info, double t0)
+{
+	const uint32_t U = s.U, M = s.M, R = s.n_reads, nb = (U + PL_TILE - 1) / PL_TILE;
+	const size_t most = M < R ? M : R; // wanted reads at the most
+	info->n_utg = U; info->n_members = M; info->n_reads = R; info->blob_bytes = s.blob_bytes; info->uoff_tiles = nb;
+	if (dev_reserve(c, b->pl_uoff, ((size_t)U + 2) * 8) != 0 || dev_reserve(c, b->pl_bsum, ((size_t)nb + 2) * 8) != 0 || dev_reserve(c, b->pl_low, ((size_t)M + 16) * 4) != 0 ||
+	    dev_reserve(c, b->pl_mscan, ((size_t)M + 16) * 4) != 0 || dev_reserve(c, b->pl_cnt, ((size_t)R + 16) * 4) != 0 || dev_reserve(c, b->pl_place, ((size_t)R + 1) * 16) != 0 ||
+	    dev_reserve(c, b->pl_flag, ((size_t)R + 16) * 4) != 0 || dev_reserve(c, b->pl_pos, ((size_t)R + 16) * 4) != 0 || dev_reserve(c, b->pl_want, (most + 1) * sizeof(mahip_useq_want_t)) != 0 ||
+	    dev_reserve(c, b->pl_ctr, PL_NCTR * 8) != 0)
+		return pl_refuse(b, info, MAHIP_PLAN_NOMEM, t0);
+	unsigned long long *ctr = P<unsigned long long>(b->pl_ctr);
+	uint4 *place = (uint4*)b->pl_place.p;
+	HIPCHK(hipMemsetAsync(ctr, 0, PL_NCTR * 8, c->st));
+	HIPCHK(hipMemsetAsync(b->pl_cnt.p, 0, ((size_t)R + 16) * 4, c->st));
+	HIPCHK(hipMemsetAsync(place, 0, ((size_t)R + 1) * 16, c->st)); // a read on no unitig: len 0
+	{
+		ProfScope ps(c, "k_pl_uoff", 12.0 * (double)U);
+		if (nb > 1) {
+			hipLaunchKernelGGL(k_pl_uoff_sums, dim3(nb), dim3(256), 0, c->st, s.u_len, U, P<uint64_t>(b->pl_bsum));
+			hipLaunchKernelGGL(k_pl_uoff_bases, dim3(1), dim3(256), 0, c->st, P<uint64_t>(b->pl_bsum), nb);
+		}
+		hipLaunchKernelGGL(k_pl_uoff_down, dim3(nb), dim3(256), 0, c->st, s.u_len, U, nb > 1 ? (const uint64_t*)b->pl_bsum.p : (const uint64_t*)nullptr, P<uint64_t>(b->pl_uoff), ctr);
+		HIPCHK(hipGetLastError());
+	}
+	CHK(text_ug_member_scan(c, s.mem, M, P<uint32_t>(b->pl_low), P<uint32_t>(b->pl_mscan)));
+	{
+		ProfScope ps(c, "k_pl_scatter", 28.0 * (double)M);
+		hipLaunchKernelGGL(k_pl_scatter, dim3(grid_for(M, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, s.mem, M, s.moff, U, (const uint32_t*)b->pl_mscan.p, R, P<uint32_t>(b->pl_cnt), place, ctr);
+		HIPCHK(hipGetLastError());
+	}
+	{
+		ProfScope ps(c, "k_pl_flag", 28.0 * (double)R);
+		hipLaunchKernelGGL(k_pl_flag, dim3(grid_for(R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint4*)place, s.off, R, P<uint32_t>(b->pl_flag), ctr);
+		HIPCHK(hipGetLastError());
+	}
+	CHK(scan_exclusive_u32(c, P<uint32_t>(b->pl_flag), P<uint32_t>(b->pl_pos), R, P<uint32_t>(b->pl_pos) + R));
+	{
+		ProfScope ps(c, "k_pl_want", 40.0 * (double)R);
+		hipLaunchKernelGGL(k_pl_want, dim3(grid_for(R, 256, MA_STREAM_BLOCKS)), dim3(256), 0, c->st, (const uint4*)place, s.off, (const uint64_t*)b->pl_uoff.p, s.sub, (const uint32_t*)b->pl_flag.p,
+		                   (const uint32_t*)b->pl_pos.p, R, U, (mahip_useq_want_t*)b->pl_want.p, ctr);
+		HIPCHK(hipGetLastError());
+	}
+	unsigned long long h[PL_NCTR];
+	uint32_t n_want = 0;
+	HIPCHK(hipMemcpyAsync(h, ctr, PL_NCTR * 8, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipMemcpyAsync(&n_want, P<uint32_t>(b->pl_pos) + R, 4, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	info->n_multi = h[PL_MULTI]; info->arena_bytes = h[PL_TOT];
+	if (h[PL_BAD]) { b->pl_valid = false; mahip_set_error("mahip_useq_plan: %llu members name a read outside the %u reads of the names", h[PL_BAD], R); return -1; }
+	if (h[PL_MULTI]) return pl_refuse(b, info, MAHIP_PLAN_MULTI, t0);
+	info->n_wanted = n_want; info->name_bytes = h[PL_NAMEB];
+	info->road = MAHIP_PLAN_ROAD_DEVICE; info->reason = MAHIP_PLAN_OK; info->ms = (fx_now() - t0) * 1e3;
+	b->pl_valid = true; b->pl_ctx = s.ctx; b->pl_names_gen = s.names_gen; b->pl_bad = h[PL_OOB]; b->pl_blob = s.blob;
+	b->pl_info = *info;
+	return 0;
+}
+
+uint32_t graph_nseq(const mahip_ctx *c); // graph.hip
+
+extern "C" int mahip_useq_plan(mahip_ctx_t *c, int have_sub, mahip_useq_plan_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	mahip_useq_plan_info_t tmp;
+	if (!info) info = &tmp;
+	memset(info, 0, sizeof(*info));
+	const double t0 = fx_now();
+	b->pl_valid = false;
+	if (pl_forced()) return pl_refuse(b, info, MAHIP_PLAN_FORCED, t0);
+	UgDevView v;
+	if (!ug_dev_view(c, &v)) return pl_refuse(b, info, MAHIP_PLAN_NO_UG, t0);
+	PlanSrc s = {v.U, v.M, graph_nseq(c), v.u_len, v.u_off, v.mem, nullptr, nullptr, 0, 0, nullptr, true};
+	const char *blob = nullptr;
+	uint32_t n_names = 0;
+	if (!text_dev_names(c, &blob, &s.off, &n_names, &s.blob_bytes, &s.names_gen) || n_names != s.n_reads) return pl_refuse(b, info, MAHIP_PLAN_NO_NAMES, t0);
+	s.blob = (const unsigned char*)blob;
+	if (have_sub) { // slot 0, as mahip_sub_download hands it over
+		const int rc = text_dev_sub(c, s.n_reads, &s.sub);
+		if (rc < 0) return -1;
+		if (rc > 0) return pl_refuse(b, info, MAHIP_PLAN_NOMEM, t0);
+	}
+	return pl_run(c, b, s, info, t0);
+}
+
+extern "C" int mahip_useq_plan_mem(mahip_ctx_t *c, uint32_t n_utg, const uint32_t *u_n, const uint32_t *u_len, const uint64_t *members, uint32_t n_seq, const char *blob, const uint64_t *off,
+                                   const void *sub, mahip_useq_plan_info_t *info)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	mahip_useq_plan_info_t tmp;
+	if (!info) info = &tmp;
+	memset(info, 0, sizeof(*info));
+	const double t0 = fx_now();
+	b->pl_valid = false;
+	if (pl_forced()) return pl_refuse(b, info, MAHIP_PLAN_FORCED, t0);
+	if (n_utg == 0) return pl_refuse(b, info, MAHIP_PLAN_NO_UG, t0);
+	if (!blob || !off) return pl_refuse(b, info, MAHIP_PLAN_NO_NAMES, t0);
+	uint64_t M = 0;
+	for (uint32_t i = 0; i < n_utg; ++i) M += u_n[i];
+	if (M > 0xffffffffull) { mahip_set_error("mahip_useq_plan_mem: the members do not fit 32 bits"); return -1; }
+	CHK(mahip_text_names(c, blob, off, n_seq, nullptr));
+	struct { DevBuf *b; const void *src; size_t bytes; } up[] = {{&b->pl_un, u_n, (size_t)n_utg * 4}, {&b->pl_ulen, u_len, (size_t)n_utg * 4}, {&b->pl_mem, members, (size_t)M * 8}, {&b->pl_sub, sub, sub ? (size_t)n_seq * 8 : 0}};
+	for (auto &u : up) {
+		if (dev_reserve(c, *u.b, u.bytes + 16) != 0) return pl_refuse(b, info, MAHIP_PLAN_NOMEM, t0);
+		if (u.bytes) CHK(xfer_copy(c, u.b->p, (void*)u.src, u.bytes, 1));
+	}
+	if (dev_reserve(c, b->pl_moff, ((size_t)n_utg + 16) * 4) != 0) return pl_refuse(b, info, MAHIP_PLAN_NOMEM, t0);
+	CHK(scan_exclusive_u32(c, P<uint32_t>(b->pl_un), P<uint32_t>(b->pl_moff), n_utg, nullptr));
+	PlanSrc s = {n_utg, (uint32_t)M, n_seq, P<uint32_t>(b->pl_ulen), P<uint32_t>(b->pl_moff), (const uint64_t*)b->pl_mem.p, nullptr, nullptr, 0, 0, sub ? P<uint32_t>(b->pl_sub) : nullptr, false};
+	const char *d_blob = nullptr;
+	uint32_t n_names = 0;
+	if (!text_dev_names(c, &d_blob, &s.off, &n_names, &s.blob_bytes, &s.names_gen)) { mahip_set_error("mahip_useq_plan_mem: the names did not reach the device"); return -1; }
+	s.blob = (const unsigned char*)d_blob;
+	return pl_run(c, b, s, info, t0);
+}
+
+extern "C" int mahip_useq_plan_last(mahip_ctx_t *c, mahip_useq_plan_info_t *info) { *info = useq_bufs(c)->pl_info; return 0; }
+
+// a plan is there, and the names its table points into are still the ones it was made of
+static int pl_have(mahip_ctx *c, UseqBufs *b, const char *who)
+{
+	const char *blob; const uint64_t *off; uint32_t n; uint64_t bytes, gen = 0;
+	if (!b->pl_valid) { mahip_set_error("%s: the context holds no placement plan (mahip_useq_plan)", who); return -1; }
+	if (!text_dev_names(c, &blob, &off, &n, &bytes, &gen) || gen != b->pl_names_gen) { mahip_set_error("%s: the names the plan points into were replaced (mahip_text_names)", who); return -1; }
+	return 0;
+}
+bool useq_plan_uoff(mahip_ctx *c, uint32_t U, uint32_t M, const uint64_t **d_uoff, uint64_t *tot)
+{
+	UseqBufs *b = (UseqBufs*)c->useq;
+	if (!b || !b->pl_valid || !b->pl_ctx || b->pl_info.n_utg != U || b->pl_info.n_members != M) return false;
+	*d_uoff = (const uint64_t*)b->pl_uoff.p; *tot = b->pl_info.arena_bytes;
+	return true;
+}
+
+extern "C" int mahip_useq_plan_download(mahip_ctx_t *c, uint64_t *uoff, mahip_useq_place_t *pl, mahip_useq_want_t *want, char *names)
+{
+	HIPCHK(hipSetDevice(c->dev));
+	UseqBufs *b = useq_bufs(c);
+	CHK(pl_have(c, b, "mahip_useq_plan_download"));
+	const mahip_useq_plan_info_t &pi = b->pl_info;
+	if (uoff) HIPCHK(hipMemcpyAsync(uoff, b->pl_uoff.p, ((size_t)pi.n_utg + 1) * 8, hipMemcpyDeviceToHost, c->st));
+	if (pl && pi.n_reads) HIPCHK(hipMemcpyAsync(pl, b->pl_place.p, (size_t)pi.n_reads * sizeof(mahip_useq_place_t), hipMemcpyDeviceToHost, c->st));
+	if (want && pi.n_wanted) HIPCHK(hipMemcpyAsync(want, b->pl_want.p, (size_t)pi.n_wanted * sizeof(mahip_useq_want_t), hipMemcpyDeviceToHost, c->st));
+	if (names && pi.blob_bytes) HIPCHK(hipMemcpyAsync(names, b->pl_blob, (size_t)pi.blob_bytes, hipMemcpyDeviceToHost, c->st));
+	HIPCHK(hipStreamSynchronize(c->st));
+	return 0;
+}
+
+extern "C" int mahip_useq_begin_planned(mahip_ctx_t *c)
+{
+	UseqBufs *b = useq_bufs(c);
+	CHK(pl_have(c, b, "mahip_useq_begin_planned"));
+	return mahip_useq_begin(c, (size_t)b->pl_info.arena_bytes);
+}
+static int pl_want_planned(mahip_ctx *c, UseqBufs *b, const char *who, size_t *n_wanted, uint32_t *cap_out)
+{
+	CHK(pl_have(c, b, who));
+	if (b->arena_bytes != b->pl_info.arena_bytes) { mahip_set_error("%s: the arena is not the plan's (mahip_useq_begin_planned)", who); return -1; }
+	if (b->pl_bad) { mahip_set_error("%s: %llu entries of the plan's table reach outside the arena or hold an interval with s > e", who, (unsigned long long)b->pl_bad); return -1; } // (the kernels trust the table)
+	b->w_want = (const mahip_useq_want_t*)b->pl_want.p; b->w_names = b->pl_blob;
+	*n_wanted = (size_t)b->pl_info.n_wanted;
+	return fx_want_table(c, b, who, *n_wanted, cap_out);
+}
 
 extern "C" void mahip_useq_note(mahip_ctx_t *c, const mahip_useq_info_t *in) { useq_bufs(c)->last = *in; }
 extern "C" int mahip_useq_last(mahip_ctx_t *c, mahip_useq_info_t *out) { *out = useq_bufs(c)->last; return 0; }

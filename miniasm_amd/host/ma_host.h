@@ -52,6 +52,9 @@ asg_arc_t *ma_ug_links_from_device(mahip_ctx_t *c, uint32_t NA); /* the unitig a
 /* ma_ug_seq in two steps (unitig_gfa.c): place = up to the finished arena, which stays in HBM; then fetch (download + one string per unitig) or drop (the device wrote the S lines) */
 typedef struct ma_ug_seq_job ma_ug_seq_job_t;
 int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn, ma_ug_seq_job_t **job);
+/* the planned form: no ma_ug_t -- the placement plan is made on the device from the unitigs mahip_ug_gen left in c (mahip_useq_plan).  0: placed; -1: the reads
+ * file cannot be opened; 1: the plan was refused (pi says why), nothing happened */
+int ma_ug_seq_place_planned(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, const char *fn, mahip_useq_plan_info_t *pi, ma_ug_seq_job_t **job);
 void ma_ug_seq_fetch(ma_ug_t *g, ma_ug_seq_job_t *job);
 void ma_ug_seq_drop(ma_ug_seq_job_t *job);
 mahip_ctx_t *ma_ug_seq_ctx(const ma_ug_seq_job_t *job); /* the context the arena lies in (ma_gpu()) */

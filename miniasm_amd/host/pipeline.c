@@ -286,9 +286,12 @@ static void dev_clean(mahip_ctx_t *c, const ma_opt_t *opt, int stage, int symm_d
  * (records exported, every line's length, every buffer: the road is decided there, all or nothing) instead of bringing the records down, and the finish runs the
  * write kernels and copies the slabs of text: it still uses the context, which must stay idle in between.
  * The unitig GFA (-p ug) takes the same road under MA_TEXT_DEVICE=1: without -f the fetch runs mahip_ug_gen, brings down and sorts the unitig arcs alone and prepares
- * (the members never come down, j->ug stays 0); with -f the host still needs the unitigs for the placement plan, so the fetch is the usual one and the finish
- * places the reads' bases, keeps the arena in HBM and prepares with the sequences -- when the arena lies in the tail's own context (ma_gpu()), otherwise the host
- * formats (NO_SEQ).  Any refusal leaves what happens today: ma_ug_t on the host, ma_ug_seq's download, ma_ug_print. */
+ * (the members never come down, j->ug stays 0); with -f, when the arena lies in the tail's own context (ma_gpu() == c), the fetch brings down nothing either: the
+ * finish has the placement plan made on the device from the unitigs where they lie (mahip_useq_plan), places the reads' bases, keeps the arena in HBM, fetches and
+ * sorts the unitig arcs and prepares with the sequences.  A plan that is refused (MA_USEQ_PLAN_HOST=1 among the reasons) unpacks ma_ug_t at that moment and goes on as
+ * before the plan existed: the host plan, the same readers, the same prepare; an arena in another context makes the host format (NO_SEQ).  A prepare that is refused
+ * behind a planned placement (SEQ_NUL, TOO_MANY, NOMEM) unpacks ma_ug_t then -- the unitigs are still in the context -- and the arena comes down and is cut with the
+ * plan's offsets.  Any refusal leaves what happened before: ma_ug_t on the host, ma_ug_seq's download, ma_ug_print. */
 struct ma_tail_job {
 	ma_opt_t opt;
 	const sdict_t *d;
@@ -304,6 +307,8 @@ struct ma_tail_job {
 	mahip_ctx_t *ctx;      /* the tail's context */
 	mahip_ctx_t *text_ctx; /* the device writes the text of this record dump (prepared by the fetch): finish still needs the context */
 	mahip_text_info_t text;
+	int plan_try, names_up;  /* -p ug -f on the device road: the finish plans the placement on the device (ug stays 0 until a refusal); the view's names are on the device */
+	uint32_t ug_n[3];        /* what mahip_ug_gen counted: unitigs, members, unitig arcs (a late ma_ug_unpack) */
 	double t_fetch[5];
 };
 
@@ -376,7 +381,9 @@ ma_tail_job_t *ma_pipeline_tail_fetch(mahip_ctx_t *c, const ma_opt_t *opt, const
 			if (mahip_text_enabled()) {
 				uint32_t U = 0, M = 0, NA = 0;
 				GPU(mahip_ug_gen(c, &U, &M, &NA));
-				if (g_reads_fn != 0 || !tail_text_prepare_ug(j, c, 0, NA, 0)) j->ug = ma_ug_unpack(c, U, M, NA); /* (-f: the placement plan needs the members; finish decides) */
+				j->ug_n[0] = U; j->ug_n[1] = M; j->ug_n[2] = NA;
+				if (g_reads_fn != 0 && ma_gpu() == c) j->plan_try = 1; /* (-f: the finish plans on the device; the members come down only if that is refused) */
+				else if (g_reads_fn != 0 || !tail_text_prepare_ug(j, c, 0, NA, 0)) j->ug = ma_ug_unpack(c, U, M, NA); /* (-f with the arena elsewhere: the host plan needs the members) */
 			} else j->ug = ma_ug_from_device(c);
 		} else if (!tail_text_prepare(j, c, MAHIP_TEXT_SG)) {
 			j->sg = asg_init();
@@ -415,7 +422,7 @@ static int tail_text_prepare_ug(ma_tail_job_t *j, mahip_ctx_t *c, const asg_arc_
 	memset(&j->text, 0, sizeof(j->text));
 	j->text.kind = MAHIP_TEXT_UG; j->text.road = MAHIP_TEXT_ROAD_HOST; j->text.reason = MAHIP_TEXT_SWITCHED_OFF;
 	if (!mahip_text_enabled()) return 0;
-	rc = text_names_upload(c, &j->view, 0);
+	rc = j->names_up ? 0 : text_names_upload(c, &j->view, 0);
 	if (rc > 0) { j->text.reason = MAHIP_TEXT_NOMEM; return 0; }
 	if (rc < 0) ma_gpu_fail(__func__);
 	if (links == 0) links = own = ma_ug_links_from_device(c, n_links);
@@ -423,6 +430,33 @@ static int tail_text_prepare_ug(ma_tail_job_t *j, mahip_ctx_t *c, const asg_arc_
 	free(own);
 	if (j->text.road != MAHIP_TEXT_ROAD_DEVICE) return 0;
 	j->text_ctx = c;
+	return 1;
+}
+
+/* -p ug -f with the plan made on the device (host/unitig_gfa.c: ma_ug_seq_place_planned).  1: done -- the bases are placed (or the reads file cannot be opened: "*")
+ * and the text is prepared, or the host formatter has its ma_ug_t with the strings; 0: the plan was refused, j->ug is unpacked and the caller goes on as ever.
+ * dict: the dictionary of the view, indexed */
+static int tail_place_planned(ma_tail_job_t *j, const sdict_t *dict)
+{
+	mahip_ctx_t *c = j->ctx;
+	mahip_useq_plan_info_t pi;
+	ma_ug_seq_job_t *sq = 0;
+	int rc = text_names_upload(c, &j->view, 0), placed;
+	if (rc < 0) ma_gpu_fail(__func__);
+	memset(&pi, 0, sizeof(pi));
+	pi.road = MAHIP_PLAN_ROAD_HOST; pi.reason = MAHIP_PLAN_NOMEM;
+	j->names_up = rc == 0;
+	rc = rc > 0 ? 1 : ma_ug_seq_place_planned(c, dict, j->sub, g_reads_fn, &pi, &sq);
+	if (ma_timing_level() >= 1 && rc >= 0) {
+		if (rc == 0) fprintf(stderr, "[T::ug_plan] device: %llu unitigs, %llu members, %llu wanted reads, %llu name bytes, %llu arena bytes; %.3f ms\n", (unsigned long long)pi.n_utg,
+		                     (unsigned long long)pi.n_members, (unsigned long long)pi.n_wanted, (unsigned long long)pi.name_bytes, (unsigned long long)pi.arena_bytes, pi.ms);
+		else fprintf(stderr, "[T::ug_plan] host (%s)\n", mahip_useq_plan_reason_name(pi.reason));
+	}
+	if (rc > 0) { j->ug = ma_ug_unpack(c, j->ug_n[0], j->ug_n[1], j->ug_n[2]); return 0; }
+	placed = rc == 0;
+	tail_text_prepare_ug(j, c, 0, j->ug_n[2], placed);
+	if (!j->text_ctx) j->ug = ma_ug_unpack(c, j->ug_n[0], j->ug_n[1], j->ug_n[2]); /* the late fetch: the host formatter needs ma_ug_t, and with a placement the strings */
+	if (sq) { if (j->text_ctx) ma_ug_seq_drop(sq); else ma_ug_seq_fetch(j->ug, sq); }
 	return 1;
 }
 
@@ -438,11 +472,14 @@ static int tail_finish_to(ma_tail_job_t *j, FILE *out, char **buf, size_t *len)
 	const int timing = ma_timing_level() >= 1;
 	double t0 = sys_realtime();
 	FILE *ms = 0;
-	if (j->ug && g_reads_fn) { /* main.c:193; the survivor view needs a name index of its own for sd_get */
+	if ((j->ug || j->plan_try) && g_reads_fn) { /* main.c:193; the survivor view needs a name index of its own for sd_get */
 		if (squeezed) ma_sd_reindex(view);
-		if (mahip_text_enabled()) { /* the bases are placed, the arena stays in HBM; the device writes the S lines from it, or (a refusal) it comes down as ever */
+		if (j->plan_try && tail_place_planned(j, squeezed ? view : d)) {
+			/* planned on the device, placed, prepared */
+		} else if (mahip_text_enabled()) { /* the bases are placed, the arena stays in HBM; the device writes the S lines from it, or (a refusal) it comes down as ever */
 			ma_ug_seq_job_t *sq = 0;
 			const int placed = ma_ug_seq_place(j->ug, squeezed ? view : d, sub, g_reads_fn, &sq) == 0; /* (a reads file that cannot be opened: "*") */
+			if (timing && !j->plan_try) fprintf(stderr, "[T::ug_plan] host (%s)\n", "the arena's context is not the tail's");
 			if (placed && ma_ug_seq_ctx(sq) != j->ctx) {
 				memset(&j->text, 0, sizeof(j->text));
 				j->text.kind = MAHIP_TEXT_UG; j->text.road = MAHIP_TEXT_ROAD_HOST; j->text.reason = MAHIP_TEXT_NO_SEQ;

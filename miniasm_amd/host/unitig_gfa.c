@@ -479,7 +479,8 @@ static void ug_seq_wanted(const sdict_t *d, const ma_sub_t *sub, const utg_place
 
 /* The reads file on the device (csrc/useq.hip): a plain file goes to HBM as it is; the device checks that it is in the regular form (include/mahip.h), looks
  * the names of the reads that sit on a unitig up among its records and copies their bases into the arena.  Returns 1 when the arena is filled, 0 with
- * ui->reason when the host reader has to run (the arena is untouched then), -1 on an error. */
+ * ui->reason when the host reader has to run (the arena is untouched then), -1 on an error.  pl == 0: the wanted reads are the table of the placement plan the
+ * context holds (mahip_useq_plan), nothing is gathered or uploaded here. */
 enum { LAP_LOAD, LAP_INDEX, LAP_LOOKUP, LAP_PLACE, LAP_DOWNLOAD, N_LAPS };
 static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, const char *fn, const utg_place_t *pl, const uint64_t *uoff, mahip_useq_info_t *ui, double *laps)
 {
@@ -487,8 +488,8 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	struct stat st;
 	unsigned char magic[2] = {0, 0};
 	mahip_fastx_info_t fi;
-	mahip_useq_want_t *want;
-	char *names;
+	mahip_useq_want_t *want = 0;
+	char *names = 0;
 	size_t n_want = 0, name_bytes = 0;
 	double t0, pl_laps[2];
 	int fd, rc;
@@ -523,9 +524,11 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	laps[LAP_INDEX] = (sys_realtime() - t0) * 1e3;
 	ui->format = fi.format; ui->n_records = fi.n_records;
 	if (!fi.regular) { ui->reason = fi.reason; mahip_fastx_release(c); return 0; }
-	ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
-	rc = mahip_useq_place_text(c, want, n_want, names, name_bytes, &ui->n_matched, &ui->n_dup, &ui->n_short, pl_laps);
-	free(want); free(names);
+	if (pl) {
+		ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
+		rc = mahip_useq_place_text(c, want, n_want, names, name_bytes, &ui->n_matched, &ui->n_dup, &ui->n_short, pl_laps);
+		free(want); free(names);
+	} else rc = mahip_useq_place_text_planned(c, &ui->n_matched, &ui->n_dup, &ui->n_short, pl_laps);
 	laps[LAP_LOOKUP] = pl_laps[0]; laps[LAP_PLACE] = pl_laps[1];
 	if (mahip_fastx_release(c) != 0 || rc != 0) return -1;
 	if (ui->n_short) { ui->reason = MAHIP_FASTX_SHORT_READ; return 0; }
@@ -553,20 +556,20 @@ size_t ma_fastx_piece(void)
  * ma_stream_q_t) while this one has the piece before uploaded, indexed, checked, looked up and placed.  Returns 1 when the whole input went that way; 0 when
  * a window got a verdict other than OK (ui->reason): the windows before it are placed, and f reads on from the first byte of that
  * window -- the window itself (fetched from the device at this moment only), what the producer had read ahead, then the rest of fp; nothing is read twice.
- * *keep: memory f points into, to be freed behind the host reader.  -1 on an error. */
+ * *keep: memory f points into, to be freed behind the host reader.  -1 on an error.  pl == 0: the plan's table, as in ug_seq_device. */
 enum { SLAP_PRODUCER, SLAP_UPLOAD, SLAP_INDEX, SLAP_LOOKUP, SLAP_PLACE, SLAP_WAIT, N_SLAPS };
 typedef struct { void *window; ma_stream_q_t q; int q_live; fq_pre_t pre; } stream_keep_t;
 static int ug_seq_stream(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, fq_stream_t *f, const utg_place_t *pl, const uint64_t *uoff, size_t piece_bytes, mahip_useq_info_t *ui,
                          mahip_useq_stream_report_t *sr, double *slaps, stream_keep_t *keep)
 {
-	mahip_useq_want_t *want;
-	char *names;
+	mahip_useq_want_t *want = 0;
+	char *names = 0;
 	size_t n_want = 0, name_bytes = 0;
 	ma_stream_q_t *q = &keep->q;
 	int i = 0, rc, handed = 0;
-	ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
+	if (pl) ug_seq_wanted(d, sub, pl, uoff, &want, &names, &n_want, &name_bytes);
 	mahip_mem_trim(c, 0);
-	rc = mahip_useq_stream_begin(c, want, n_want, names, name_bytes);
+	rc = pl ? mahip_useq_stream_begin(c, want, n_want, names, name_bytes) : mahip_useq_stream_begin_planned(c);
 	free(want); free(names);
 	if (rc != 0) return -1;
 	ma_stream_q_init(q, f->fp, piece_bytes);
@@ -663,20 +666,75 @@ struct ma_ug_seq_job {
 	double laps[N_LAPS], slaps[N_SLAPS];
 };
 
-int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn, ma_ug_seq_job_t **job)
+/* the job with its reads file open (opened before anything else, as the reference does: a missing file is an error, not a fallback; nothing is read through it
+ * unless the host reader runs); 0: it cannot be opened */
+static ma_ug_seq_job_t *ug_seq_open(const char *fn)
 {
 	ma_ug_seq_job_t *q = (ma_ug_seq_job_t*)calloc(1, sizeof(ma_ug_seq_job_t));
+	q->piece_bytes = ma_fastx_piece();
+	q->f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r");
+	if (q->f.fp == 0) { free(q); return 0; }
+	return q;
+}
+
+/* the plan of the context to the host, as the host reader wants it: pl[d->n_seq], q->uoff (asm.c:248-260, computed by mahip_useq_plan) */
+static utg_place_t *ug_seq_plan_fetch(ma_ug_seq_job_t *q, const sdict_t *d)
+{
+	mahip_useq_plan_info_t pi;
+	mahip_useq_place_t *dl;
+	utg_place_t *pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
+	uint32_t i;
+	mahip_useq_plan_last(q->c, &pi);
+	if (pi.n_reads != d->n_seq) { fprintf(stderr, "[E::%s] the plan describes %llu reads, the dictionary %u\n", __func__, (unsigned long long)pi.n_reads, d->n_seq); exit(1); }
+	dl = (mahip_useq_place_t*)malloc((d->n_seq ? d->n_seq : 1) * sizeof(mahip_useq_place_t));
+	if (q->uoff == 0) q->uoff = (uint64_t*)malloc((pi.n_utg + 1) * 8);
+	GPU(mahip_useq_plan_download(q->c, q->uoff, dl, 0, 0));
+	for (i = 0; i < d->n_seq; ++i) pl[i].utg = dl[i].utg, pl[i].ori = dl[i].ori, pl[i].start = dl[i].start, pl[i].len = dl[i].len;
+	free(dl);
+	return pl;
+}
+
+/* the three readers in their order under their switches (MA_FASTX_HOST, MA_FASTX_STREAM, MA_FASTX_PIECE) behind mahip_useq_begin, up to the finished arena.
+ * pl == 0: the plan is the context's (ma_ug_seq_place_planned) -- the device readers take its table where it lies, the host reader brings pl and uoff down */
+static void ug_seq_readers(ma_ug_seq_job_t *q, const sdict_t *d, const ma_sub_t *sub, const char *fn, utg_place_t *pl)
+{
+	mahip_ctx_t *c = q->c;
+	const int stream_mode = ma_fastx_stream_mode();
+	int forced, streamed = 0, on_device = 0;
+	{ const char *e = getenv("MA_FASTX_HOST"); forced = e && atoi(e) != 0; }
+	if (forced || stream_mode != 2) { /* the whole-file device reader first, as ever */
+		on_device = ug_seq_device(c, d, sub, fn, pl, q->uoff, &q->ui, q->laps);
+		if (on_device < 0) ma_gpu_fail(__func__);
+	}
+	if (!forced && !on_device && (stream_mode == 2 || (stream_mode == 1 && (q->ui.reason == MAHIP_FASTX_NOT_PLAIN || q->ui.reason == MAHIP_FASTX_NOMEM)))) { /* the streamed device reader */
+		memset(&q->ui, 0, sizeof(q->ui));
+		streamed = 1;
+		on_device = ug_seq_stream(c, d, sub, &q->f, pl, q->uoff, q->piece_bytes, &q->ui, &q->sr, q->slaps, &q->keep);
+		if (on_device < 0) ma_gpu_fail(__func__);
+	}
+	q->ui.reader = streamed ? MAHIP_USEQ_STREAM : on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
+	mahip_useq_note(c, &q->ui);
+	if (!on_device) {
+		utg_place_t *own = 0;
+		if (streamed) fprintf(stderr, "[W::%s] reads file handed to the host reader at piece %lld: %s\n", "ma_ug_seq", (long long)q->sr.refused_piece, mahip_fastx_reason_name(q->ui.reason));
+		else fprintf(stderr, "[W::%s] reads file read on the host: %s\n", "ma_ug_seq", mahip_fastx_reason_name(q->ui.reason));
+		if (pl == 0) pl = own = ug_seq_plan_fetch(q, d);
+		ug_seq_host(c, d, sub, &q->f, pl, q->uoff);
+		free(own);
+	}
+	GPU(mahip_useq_end(c, 0)); /* finished; it stays in HBM */
+	q->on_device = on_device; q->streamed = streamed;
+}
+
+int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const char *fn, ma_ug_seq_job_t **job)
+{
+	ma_ug_seq_job_t *q = ug_seq_open(fn);
 	mahip_ctx_t *c;
 	utg_place_t *pl;
 	uint64_t *uoff, tot = 0;
 	uint32_t i, j;
-	int on_device = 0;
-	const int stream_mode = ma_fastx_stream_mode();
-	int forced, streamed = 0;
 	*job = 0;
-	q->piece_bytes = ma_fastx_piece();
-	q->f.fp = fn && strcmp(fn, "-") ? gzopen(fn, "r") : gzdopen(fileno(stdin), "r"); /* (opened before anything else, as the reference does: a missing file is an error, not a fallback; */
-	if (q->f.fp == 0) { free(q); return -1; }                                         /*  nothing is read through it unless the host reader runs) */
+	if (q == 0) return -1;
 	c = q->c = ma_gpu();
 	pl = (utg_place_t*)calloc(d->n_seq ? d->n_seq : 1, sizeof(utg_place_t));
 	uoff = q->uoff = (uint64_t*)malloc((g->u.n + 1) * 8);
@@ -694,27 +752,28 @@ int ma_ug_seq_place(ma_ug_t *g, const sdict_t *d, const ma_sub_t *sub, const cha
 	}
 	q->tot = tot;
 	GPU(mahip_useq_begin(c, (size_t)tot));
-	{ const char *e = getenv("MA_FASTX_HOST"); forced = e && atoi(e) != 0; }
-	if (forced || stream_mode != 2) { /* the whole-file device reader first, as ever */
-		on_device = ug_seq_device(c, d, sub, fn, pl, uoff, &q->ui, q->laps);
-		if (on_device < 0) ma_gpu_fail(__func__);
-	}
-	if (!forced && !on_device && (stream_mode == 2 || (stream_mode == 1 && (q->ui.reason == MAHIP_FASTX_NOT_PLAIN || q->ui.reason == MAHIP_FASTX_NOMEM)))) { /* the streamed device reader */
-		memset(&q->ui, 0, sizeof(q->ui));
-		streamed = 1;
-		on_device = ug_seq_stream(c, d, sub, &q->f, pl, uoff, q->piece_bytes, &q->ui, &q->sr, q->slaps, &q->keep);
-		if (on_device < 0) ma_gpu_fail(__func__);
-	}
-	q->ui.reader = streamed ? MAHIP_USEQ_STREAM : on_device ? MAHIP_USEQ_DEVICE : MAHIP_USEQ_HOST;
-	mahip_useq_note(c, &q->ui);
-	if (!on_device) {
-		if (streamed) fprintf(stderr, "[W::%s] reads file handed to the host reader at piece %lld: %s\n", "ma_ug_seq", (long long)q->sr.refused_piece, mahip_fastx_reason_name(q->ui.reason));
-		else fprintf(stderr, "[W::%s] reads file read on the host: %s\n", "ma_ug_seq", mahip_fastx_reason_name(q->ui.reason));
-	}
-	if (!on_device) ug_seq_host(c, d, sub, &q->f, pl, uoff);
-	GPU(mahip_useq_end(c, 0)); /* finished; it stays in HBM */
-	q->on_device = on_device; q->streamed = streamed;
+	ug_seq_readers(q, d, sub, fn, pl);
 	free(pl);
+	*job = q;
+	return 0;
+}
+
+/* ma_ug_seq_place without ma_ug_t: the plan (asm.c:248-260 and the wanted table) is made on the device from the unitigs mahip_ug_gen left in c, the names of
+ * mahip_text_names and the kept intervals (mahip_useq_plan; no member word comes down), then the same readers run.  0: placed; -1: the reads file cannot be opened
+ * (the plan stays, nothing is placed); 1: the plan was refused (pi->reason; nothing in the context changed, the caller takes ma_ug_seq_place).  d: the dictionary the names
+ * describe, with its index (the host reader looks names up in it).  Then ma_ug_seq_drop, or ma_ug_seq_fetch with a ma_ug_t unpacked for it. */
+int ma_ug_seq_place_planned(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, const char *fn, mahip_useq_plan_info_t *pi, ma_ug_seq_job_t **job)
+{
+	ma_ug_seq_job_t *q;
+	*job = 0;
+	memset(pi, 0, sizeof(*pi));
+	GPU(mahip_useq_plan(c, sub != 0, pi)); /* (before the file is opened: a refusal leaves it, stdin included, to ma_ug_seq_place) */
+	if (pi->road != MAHIP_PLAN_ROAD_DEVICE) return 1;
+	if ((q = ug_seq_open(fn)) == 0) return -1;
+	q->c = c;
+	q->tot = pi->arena_bytes;
+	GPU(mahip_useq_begin_planned(c));
+	ug_seq_readers(q, d, sub, fn, 0);
 	*job = q;
 	return 0;
 }
@@ -753,6 +812,10 @@ void ma_ug_seq_fetch(ma_ug_t *g, ma_ug_seq_job_t *q)
 	const double t_dl = sys_realtime();
 	uint32_t i;
 	GPU(mahip_useq_end(q->c, arena));
+	if (q->uoff == 0) { /* a planned placement whose host reader did not run: where the strings start is still on the device alone */
+		q->uoff = (uint64_t*)malloc(((size_t)g->u.n + 1) * 8);
+		GPU(mahip_useq_plan_download(q->c, q->uoff, 0, 0, 0));
+	}
 	q->laps[LAP_DOWNLOAD] = (sys_realtime() - t_dl) * 1e3;
 	for (i = 0; i < g->u.n; ++i) { /* ma_ug_destroy frees every string on its own */
 		ma_utg_t *u = &g->u.a[i];

@@ -6,7 +6,8 @@ input of the tests (pafgen -r 3000 -n 80000 -s 41).  Per dump the settings alter
 within the parent's own spread); this build with MA_TEXT_DEVICE=1 for every MA_TEXT_SLAB of --slabs (Mi records).  --reps rounds (at least 5 for a result that
 decides anything).  The unitig GFA (--dumps ug,ug_S6,ug_f; DESIGN 3.20, the ug kind) has inputs of its own: `ug` runs on the graph-heavy input (pafgen -L fixed,
 50 lines per read: -r 2000000 -n 100000000 -s 4, divided by --div), `ug_S6` and `ug_f` (-p ug -f <a FASTQ readgen makes for that PAF>) on the noisy input
-(-r 1000000 -n 50000000 -s 3 -L uniform -d 0.35 -x 0.03, divided by --div); median and min-max of each setting are reported, with the [T::text] line, the child's ru_maxrss and the CRC-32 of the output, which must be the
+(-r 1000000 -n 50000000 -s 3 -L uniform -d 0.35 -x 0.03, divided by --div); `ug_f` also runs MA_TEXT_DEVICE=1 with MA_USEQ_PLAN_HOST=1 (the placement plan on the host, as
+before it was made on the device) and records the [T::ug_plan] line and the `unitigs/graph to host` lap of [T::tail] of every run; median and min-max of each setting are reported, with the [T::text] line, the child's ru_maxrss and the CRC-32 of the output, which must be the
 same in every setting.  Stdout of every run goes to one file in the work directory.  Every GPU step runs under its own `timeout -k 10`; the first one that fails
 ends the script.  Result: one JSON line, also written to --out (merged into what --out already holds for other --div / dumps).
 
@@ -30,7 +31,7 @@ UG_INPUT = {"ug": "graph", "ug_S6": "noisy", "ug_f": "noisy"}  # the unitig GFA'
 def timed(cmd, env, out_path, limit):
     """one GPU step under its own time limit, as a child of its own so that ru_maxrss is its alone; anything but exit 0 ends the script"""
     e = dict(os.environ, MA_PIPE_TIMING="1")
-    for k in ("MA_TEXT_DEVICE", "MA_TEXT_SLAB"):
+    for k in ("MA_TEXT_DEVICE", "MA_TEXT_SLAB", "MA_USEQ_PLAN_HOST"):
         e.pop(k, None)
     e.update(env)
     # (RUSAGE_CHILDREN is a maximum over all children so far: a helper process per run makes it this run's; the clock runs around the command alone)
@@ -66,6 +67,19 @@ def text_line(log):
                    laps_ms={"names": float(g[6]), "export": float(g[7]), "format": float(g[8]), "copy_write": float(g[9])})
         if g[4] is not None:
             out["seq_bytes"] = int(g[4])
+    return out
+
+
+def plan_laps(log):
+    """-p ug -f: the [T::ug_plan] line (road; the plan's own ms on the device road, the reason otherwise; None: the binary prints none) and the `unitigs/graph to host`
+    lap of [T::tail], ms -- the fetch that brings the members down and unpacks ma_ug_t when the plan is the host's (the host walk itself has no lap of its own)"""
+    out = {"plan": None, "ug_to_host_ms": None}
+    m = re.search(r"^\[T::ug_plan\] (device|host)(?:: .*; ([\d.]+) ms| \((.*)\))$", log, flags=re.M)
+    if m:
+        out["plan"] = {"road": m.group(1), "ms": float(m.group(2))} if m.group(1) == "device" else {"road": "host", "reason": m.group(3)}
+    m = re.search(r"^\[T::tail\] names\+sub [\d.]+  device cleaners [\d.]+  unitigs/graph to host ([\d.]+) ms$", log, flags=re.M)
+    if m:
+        out["ug_to_host_ms"] = float(m.group(1))
     return out
 
 
@@ -108,6 +122,8 @@ def main():
                     tail = ["-f", extra["reads"]]
             settings = [("parent", a.parent, {}), ("device_off", a.miniasm, {"MA_TEXT_DEVICE": "0"})]
             settings += [("device_%dMi" % s, a.miniasm, {"MA_TEXT_DEVICE": "1", "MA_TEXT_SLAB": str(s << 20)}) for s in slabs]
+            if dump == "ug_f":  # the device text road with the plan forced to the host: what MA_TEXT_DEVICE=1 did before the plan was made on the device
+                settings += [("device_%dMi_host_plan" % slabs[-1], a.miniasm, {"MA_TEXT_DEVICE": "1", "MA_TEXT_SLAB": str(slabs[-1] << 20), "MA_USEQ_PLAN_HOST": "1"})]
             runs = {name: {"wall_s": [], "maxrss_kib": [], "text": None} for name, _, _ in settings}
             crcs, sizes = set(), set()
             for rep in range(a.reps):
@@ -123,6 +139,14 @@ def main():
                     runs[name]["wall_s"].append(round(dt, 4))
                     runs[name]["maxrss_kib"].append(rss)
                     runs[name]["text"] = t
+                    if dump == "ug_f":
+                        pl = plan_laps(log)
+                        runs[name].setdefault("ug_to_host_ms", []).append(pl["ug_to_host_ms"])
+                        runs[name].setdefault("plan_ms", []).append(pl["plan"]["ms"] if pl["plan"] and pl["plan"]["road"] == "device" else None)
+                        runs[name]["plan"] = pl["plan"]
+                        want_road = None if name in ("parent", "device_off") else "host" if name.endswith("_host_plan") else "device"
+                        if (pl["plan"] or {}).get("road") != want_road:
+                            sys.exit("%s %s: the wrong placement plan ran:\n%s" % (dump, name, log[-2000:]))
                     print("%s %s rep %d %s: %.3f s, max RSS %.0f MiB, %d bytes, %s" % (key, dump, rep, name, dt, rss / 1024.0, n, t), flush=True)
             for name in runs:
                 w = runs[name]["wall_s"]
