@@ -542,13 +542,13 @@ int mahip_text_first_nl(mahip_ctx_t *c, const void *d_text, uint64_t from, uint6
 int mahip_bgzf_last(mahip_ctx_t *c, mahip_bgzf_info_t *out); /* what the context's last BGZF load (or mahip_bgzf_note) decided */
 void mahip_bgzf_note(mahip_ctx_t *c, const mahip_bgzf_info_t *in); /* a caller that did not get as far as a load (MA_BGZF_HOST) says so */
 const char *mahip_bgzf_reason_name(int reason);
-/* ---- plain gzip input (one member, one deflate stream: what `gzip -1` writes) inflated on the device (csrc/xfer.hip: k_gz_*, csrc/gzip_core.h).
+/* ---- plain gzip input (one member, one deflate stream: what `gzip -1` writes; concatenated members: further below) inflated on the device (csrc/xfer.hip: k_gz_*, csrc/gzip_core.h).
  * The host reads the member's header and trailer; the compressed file goes to HBM as it is; its payload is cut into chunks of `chunk` bytes.  k_gz_sync_count:
  * one wave per chunk looks in its own bits for the first dynamic-block header that holds and that a trial decode of the block confirms (chunk 0 starts at bit
  * 0), then decodes on WITHOUT output, summing the output length, to the first dynamic block start in a later chunk, or to the end of the stream: one row per
  * chunk.  The host follows the rows from chunk 0 (`end_bit` of one must be `sync_bit` of the chunk it falls into): the chain's items, their output offsets,
  * the text size.  k_gz_decode: one wave per item writes 16-bit symbols (a byte, or a cell of the unknown 32 KiB in front of the item); k_gz_windows: one
- * workgroup makes every item's window from the one before it; k_gz_resolve writes the text, k_gz_crc checks it against the trailer.  Every refusal is a
+ * workgroup a member makes every item's window from the one before it; k_gz_resolve writes the text, k_gz_crc checks it against the trailer.  Every refusal is a
  * `reason`, not an error: nothing is loaded and the caller inflates with zlib.
  *   BAD_HEADER: not a gzip member, CM != 8, a reserved flag, an extra field with a `BC` subfield, or too short for header and trailer;
  *   MULTI_MEMBER: the stream's final block does not end 8 bytes in front of the end of the file (a second member, trailing bytes);
@@ -557,7 +557,8 @@ const char *mahip_bgzf_reason_name(int reason);
  *   BAD_BTYPE .. OUT_SHORT: the status of an item on the chain, as for BGZF; CRC; NOMEM, NOT_SEEKABLE, FORCED (the switch is off), EMPTY: as for BGZF. */
 enum { MAHIP_GZIP_OK = 0, MAHIP_GZIP_BAD_HEADER, MAHIP_GZIP_MULTI_MEMBER, MAHIP_GZIP_NO_SYNC, MAHIP_GZIP_SYNC_MISMATCH, MAHIP_GZIP_ISIZE,
        MAHIP_GZIP_BAD_BTYPE, MAHIP_GZIP_STORED_LEN, MAHIP_GZIP_BAD_LENGTHS, MAHIP_GZIP_BAD_SYMBOL, MAHIP_GZIP_DIST_TOO_FAR, MAHIP_GZIP_OUT_OVERFLOW, MAHIP_GZIP_IN_EXHAUSTED,
-       MAHIP_GZIP_OUT_SHORT, MAHIP_GZIP_CRC, MAHIP_GZIP_NOMEM, MAHIP_GZIP_NOT_SEEKABLE, MAHIP_GZIP_FORCED, MAHIP_GZIP_EMPTY };
+       MAHIP_GZIP_OUT_SHORT, MAHIP_GZIP_CRC, MAHIP_GZIP_NOMEM, MAHIP_GZIP_NOT_SEEKABLE, MAHIP_GZIP_FORCED, MAHIP_GZIP_EMPTY,
+       MAHIP_GZIP_TOO_MANY_CANDIDATES /* the *_members forms: the member scan found more candidate positions than its list holds */ };
 #define MAHIP_GZIP_CHUNK_DEFAULT ((size_t)1 << 20) /* bytes of payload per chunk; MA_GZIP_CHUNK (a power of two, 1024 .. 16 MiB) overrides it */
 typedef struct {
 	uint64_t comp_bytes, text_bytes;       /* the file; the items' total output */
@@ -586,6 +587,40 @@ const char *mahip_gzip_reason_name(int reason);
 /* the rows of the context's last plain-gzip load (n_chunks of them; none when it stopped at the header); valid until the next load.  Returns the number
  * of rows copied (at most cap). */
 uint64_t mahip_gzip_items_download(mahip_ctx_t *c, mahip_gzip_item_t *out, uint64_t cap);
+/* ---- concatenated gzip members (`cat a.gz b.gz`; what zlib's gzread reads as one text).  The three entry points above keep their contract: one member, and
+ * MULTI_MEMBER otherwise.  The *_members forms take the same arguments and inflate every member into ONE text:
+ *   k_gz_member_scan   every byte position behind the first header whose bytes read 1f 8b 08 and a FLG with bits 5..7 clear is a CANDIDATE (a list of at most
+ *                      `cand_cap` positions; more: TOO_MANY_CANDIDATES).  The host sorts the list and reads a header at each one; a candidate whose header does
+ *                      not parse is dropped.  False candidates are expected (a stored block may hold any bytes) and cost nothing: the chain never visits them.
+ *   k_gz_heads         one wave per surviving candidate decodes, counting, from the first bit behind its header -- as k_gz_sync_count does for chunk 0 -- to the
+ *                      first dynamic block start in a later chunk, or to BFINAL: one row per candidate (a HEAD ITEM; it may end in the chunk it starts in).
+ *   the chain          where a member's final block ends (byte-aligned) + 8 is the end of the file or a position q.  If q is a candidate with a head row the
+ *                      trailer at q - 8 closes the member (ISIZE against the member's own total) and the chain goes on with q's head row; else MULTI_MEMBER:
+ *                      trailing bytes that begin no member this reader takes (zlib has its own rules for those and stays the one that applies them).
+ *   history            a distance may not reach in front of its own member: DIST_TOO_FAR, as zlib fails on it.  k_gz_windows runs one workgroup per MEMBER.
+ *   CRC                k_gz_crc works on pieces that never straddle a member; every member's CRC is compared with its own trailer.
+ * A member without text (`gzip < /dev/null`) is legal and contributes nothing.  Chunks, bits and rows count from the first bit behind the FIRST member's header,
+ * as above; headers and trailers of later members lie among the chunks' bytes. */
+typedef struct {
+	uint64_t n_members, n_candidates, n_heads; /* members on the chain (the one a refusal is about included); candidates the scan found; those with a header that parses */
+	int64_t bad_member;                        /* the member (its number in the file, from 0) the reason is about, else -1 */
+	uint64_t cand_cap;                         /* the capacity of the candidate list of this load */
+	double laps_ms[2];                         /* the member scan (with the headers read on the host); the head items */
+} mahip_gzip_members_info_t;
+typedef struct {
+	uint64_t comp_off, hdr_len;  /* where the member starts in the file; its header's length */
+	uint64_t text_off, text_len; /* where its text lies in the whole text */
+	uint32_t crc, isize;         /* its trailer (zero for a member the chain did not close) */
+	uint64_t n_items;            /* chain items of this member */
+} mahip_gzip_member_t;
+#define MAHIP_GZIP_CAND_CAP_DEFAULT ((size_t)1 << 16) /* MA_GZIP_CAND_CAP overrides it (tests) */
+int mahip_gzip_load_fd_members(mahip_ctx_t *c, int fd, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info);
+int mahip_gzip_load_mem_members(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info);
+int mahip_gzip_inflate_mem_members(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info);
+/* the member facts of the context's last plain-gzip load (all zero, bad_member -1, after a load through the one-member entry points) */
+int mahip_gzip_members_last(mahip_ctx_t *c, mahip_gzip_members_info_t *out);
+/* one row per member of the last load, in file order; returns the number of rows copied (at most cap) */
+uint64_t mahip_gzip_members_download(mahip_ctx_t *c, mahip_gzip_member_t *out, uint64_t cap);
 uint32_t mahip_asg_n_arc(mahip_ctx_t *c);
 /* how many device-wide scans (csrc/scan.hip) of this context, since it was created, took each form: one tile (k_scan_down alone, n <= 2048), the chained
  * launch (k_scan_chain, up to 256 tiles = 524 288 elements), reduce / scan of the tile sums / downsweep (k_scan_reduce, above).  Host bookkeeping only. */

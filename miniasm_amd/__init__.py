@@ -159,7 +159,15 @@ class GzipItem(C.Structure):  # include/mahip.h: mahip_gzip_item_t
 
 # include/mahip.h: MAHIP_GZIP_* reasons
 GZIP_REASONS = ["OK", "BAD_HEADER", "MULTI_MEMBER", "NO_SYNC", "SYNC_MISMATCH", "ISIZE", "BAD_BTYPE", "STORED_LEN", "BAD_LENGTHS", "BAD_SYMBOL", "DIST_TOO_FAR", "OUT_OVERFLOW",
-                "IN_EXHAUSTED", "OUT_SHORT", "CRC", "NOMEM", "NOT_SEEKABLE", "FORCED", "EMPTY"]
+                "IN_EXHAUSTED", "OUT_SHORT", "CRC", "NOMEM", "NOT_SEEKABLE", "FORCED", "EMPTY", "TOO_MANY_CANDIDATES"]
+
+
+class GzipMembersInfo(C.Structure):  # include/mahip.h: mahip_gzip_members_info_t
+    _fields_ = [("n_members", C.c_uint64), ("n_candidates", C.c_uint64), ("n_heads", C.c_uint64), ("bad_member", C.c_int64), ("cand_cap", C.c_uint64), ("laps_ms", C.c_double * 2)]
+
+
+class GzipMember(C.Structure):  # include/mahip.h: mahip_gzip_member_t
+    _fields_ = [("comp_off", C.c_uint64), ("hdr_len", C.c_uint64), ("text_off", C.c_uint64), ("text_len", C.c_uint64), ("crc", C.c_uint32), ("isize", C.c_uint32), ("n_items", C.c_uint64)]
 
 
 def _gzip_dict(g):
@@ -349,6 +357,12 @@ def lib():
         L.mahip_gzip_load_mem.argtypes = [vp, vp, sz, i32, sz, C.POINTER(GzipInfo)]
         L.mahip_gzip_inflate_mem.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(GzipInfo)]
         L.mahip_gzip_last.argtypes = [vp, C.POINTER(GzipInfo)]
+        L.mahip_gzip_load_fd_members.argtypes = [vp, i32, sz, i32, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_load_mem_members.argtypes = [vp, vp, sz, i32, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_inflate_mem_members.argtypes = [vp, vp, sz, sz, vp, sz, C.POINTER(GzipInfo)]
+        L.mahip_gzip_members_last.argtypes = [vp, C.POINTER(GzipMembersInfo)]
+        L.mahip_gzip_members_download.restype = C.c_uint64
+        L.mahip_gzip_members_download.argtypes = [vp, C.POINTER(GzipMember), C.c_uint64]
         L.mahip_gzip_reason_name.restype = C.c_char_p
         L.mahip_gzip_reason_name.argtypes = [i32]
         L.mahip_gzip_items_download.restype = C.c_uint64
@@ -791,21 +805,36 @@ class Ctx:
         return _bgzf_dict(bi)
 
     # ---- plain gzip input inflated on the device (csrc/xfer.hip: k_gz_*, csrc/gzip_core.h)
-    def gzip_inflate(self, comp, chunk=None, out_cap=None):
+    def gzip_inflate(self, comp, chunk=None, out_cap=None, members=False):
         """a gzip image (bytes) -> (text, info dict); text is None when the device refused it (info["reason"] says why); chunk: bytes of payload per chunk (None:
-        MA_GZIP_CHUNK or the default) -- nothing stays loaded either way"""
+        MA_GZIP_CHUNK or the default) -- nothing stays loaded either way.  members: concatenated members are one text (else a second member is MULTI_MEMBER)"""
         gi = GzipInfo()
         cap = out_cap if out_cap is not None else 1032 * len(comp) + 64  # deflate's best ratio
         out = C.create_string_buffer(max(cap, 1))
-        _chk(lib().mahip_gzip_inflate_mem(self.h, comp, len(comp), chunk or 0, out, cap, C.byref(gi)), "gzip_inflate_mem")
+        fn = lib().mahip_gzip_inflate_mem_members if members else lib().mahip_gzip_inflate_mem
+        _chk(fn(self.h, comp, len(comp), chunk or 0, out, cap, C.byref(gi)), "gzip_inflate_mem")
         info = _gzip_dict(gi)
         return (out.raw[:gi.text_bytes] if info["reason"] == "OK" else None), info
 
-    def gzip_load(self, comp, target="paf", chunk=None):
+    def gzip_load(self, comp, target="paf", chunk=None, members=False):
         """a gzip image into the text buffer of the PAF reader or of the reads-file reader, as mahip_paf_load_mem / mahip_fastx_load_mem leave it -> info dict"""
         gi = GzipInfo()
-        _chk(lib().mahip_gzip_load_mem(self.h, comp, len(comp), BGZF_TARGETS[target], chunk or 0, C.byref(gi)), "gzip_load_mem")
+        fn = lib().mahip_gzip_load_mem_members if members else lib().mahip_gzip_load_mem
+        _chk(fn(self.h, comp, len(comp), BGZF_TARGETS[target], chunk or 0, C.byref(gi)), "gzip_load_mem")
         return _gzip_dict(gi)
+
+    def gzip_members_info(self):
+        """the member facts of the last plain-gzip load: dict(n_members, n_candidates, n_heads, bad_member (-1: none), cand_cap, laps_ms)"""
+        mi = GzipMembersInfo()
+        _chk(lib().mahip_gzip_members_last(self.h, C.byref(mi)), "gzip_members_last")
+        return dict(n_members=mi.n_members, n_candidates=mi.n_candidates, n_heads=mi.n_heads, bad_member=mi.bad_member, cand_cap=mi.cand_cap, laps_ms=dict(zip(("scan", "heads"), mi.laps_ms)))
+
+    def gzip_members(self):
+        """one row per member of the last load with members=True, in file order: dict(comp_off, hdr_len, text_off, text_len, crc, isize, n_items)"""
+        n = self.gzip_members_info()["n_members"]
+        rows = (GzipMember * max(n, 1))()
+        n = lib().mahip_gzip_members_download(self.h, rows, n)
+        return [dict(comp_off=r.comp_off, hdr_len=r.hdr_len, text_off=r.text_off, text_len=r.text_len, crc=r.crc, isize=r.isize, n_items=r.n_items) for r in rows[:n]]
 
     def gzip_last(self):
         """what the context's last plain-gzip load decided"""

@@ -1,4 +1,5 @@
-/* gzip_core.h -- a plain gzip member's ONE deflate stream inflated by many waves (csrc/xfer.hip: k_gz_sync_count, k_gz_decode).
+/* gzip_core.h -- a plain gzip member's ONE deflate stream inflated by many waves (csrc/xfer.hip: k_gz_sync_count, k_gz_heads, k_gz_decode).
+ * Concatenated members are one stream each: k_gz_heads starts a wave at the first bit behind a later member's header exactly as chunk 0's wave starts at bit 0.
  *
  * The payload is cut into chunks of C bytes.  A wave's coordinates are LOCAL: bit 0 is the first bit of its chunk, `in` points there, and in_len is cut at
  * GZ_SPAN_MAX + 2 chunks + GZ_BLOCK_MAX bytes (or the end of the payload), so one wave reads a bounded piece of the input whatever the stream holds.

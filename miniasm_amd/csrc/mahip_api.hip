@@ -321,6 +321,7 @@ extern "C" void mahip_destroy(mahip_ctx_t *c)
 	text_free(c);
 	xfer_pool_free(c);
 	free(c->gzip_rows);
+	free(c->gzip_members);
 	dev_pool_destroy(c); // after everybody gave its buffers back
 	if (c->h_ctr) (void)hipHostFree(c->h_ctr);
 	if (c->own_stream) (void)hipStreamDestroy(c->st);

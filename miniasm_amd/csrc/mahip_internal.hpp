@@ -132,6 +132,9 @@ struct mahip_ctx {
 	mahip_gzip_info_t gzip_last = {}; // the same for plain gzip, and its rows (host memory; xfer.hip: mahip_gzip_items_download)
 	mahip_gzip_item_t *gzip_rows = nullptr;
 	uint64_t gzip_n_rows = 0;
+	mahip_gzip_members_info_t gzip_mlast = {0, 0, 0, -1, 0, {0, 0}}; // the member facts of that load, and its member rows (mahip_gzip_members_download)
+	mahip_gzip_member_t *gzip_members = nullptr;
+	uint64_t gzip_n_members = 0;
 
 	hipEvent_t mark_ev[64] = {}; // phase marks (mahip_mark)
 	hipStream_t sub_side[2] = {}; hipEvent_t sub_ev[3] = {}; // side streams of the coverage passes' size classes (hits.hip: SubFork)

@@ -580,16 +580,19 @@ extern "C" const char *mahip_bgzf_reason_name(int reason)
 }
 
 // ================================================================================================ plain gzip input, inflated on the device
-// One member, ONE deflate stream: what BGZF's headers give away -- where a block starts, how many bytes a piece inflates to, what the 32 KiB in front of a
+// A member is ONE deflate stream (concatenated members: one stream each, found by k_gz_member_scan / k_gz_heads): what BGZF's headers give away -- where a block starts, how many bytes a piece inflates to, what the 32 KiB in front of a
 // piece held -- is found here.  include/mahip.h has the scheme; gzip_core.h the per-lane header test and the wave's decode loop in its two forms.
 #include "gzip_core.h"
+#include <algorithm>
+#include <vector>
 
 #define GZ_CNT_WAVES 4u    // k_gz_sync_count: chunks per workgroup (tables only: 4 x 5.6 KiB of LDS)
 #define GZ_DEC_WAVES 2u    // k_gz_decode: items per workgroup (2 x sizeof(GzLds) = 137 KiB of the CU's 160 KiB)
 #define GZ_TILE 4096u      // k_gz_resolve: text bytes per workgroup
 #define GZ_CRC_PIECE 65536u
 #define GZ_CHUNK_MAX ((size_t)16 << 20) // (GZ_SPAN_MAX + 2) chunks + GZ_BLOCK_MAX stay below 2^32 / 8: a wave's local BIT positions fit 32 bits with room
-struct gz_chain_t { uint64_t sync_bit, end_bit, out_off, out_len; }; // one item of the chain; bits of the payload
+struct gz_chain_t { uint64_t sync_bit, end_bit, out_off, out_len, base; }; // one item of the chain; bits of the payload; base: where its member's text starts
+struct gz_piece_t { uint64_t text_off, behind; uint32_t size, member; }; // k_gz_crc: a piece of ONE member's text; the bytes of that member's text behind the piece
 
 // the input a wave whose chunk starts at byte0 of the payload may read
 __device__ __forceinline__ uint32_t gz_in_len(uint64_t payload_len, uint64_t byte0, uint64_t C)
@@ -604,10 +607,44 @@ __device__ __forceinline__ void gz_state(InfState &s, const uint8_t *in, uint32_
 }
 __device__ __forceinline__ uint32_t gz_reason(uint32_t st) { return st == GZ_NO_SYNC ? (uint32_t)MAHIP_GZIP_NO_SYNC : (uint32_t)MAHIP_GZIP_BAD_BTYPE + st - 1; }
 
-// One wave per chunk.  Chunk 0 starts at bit 0.  Every other chunk tries its own bits, 64 consecutive ones a round (one a lane: gz_holds), and the whole wave
-// confirms the survivors in ascending order by decoding the block (gz_item); the first confirmed one is the chunk's start, and the decode goes on from there,
-// counting, to the item's end.  TERMINATION: the search visits each of the chunk's <= 8 C bits once, each candidate's trial and the item's decode consume
-// input that is bounded by gz_in_len.  BOUNDS: the payload is read below byte0 + in_len <= payload_len only; one row is written, rows[k], k < n_chunks.
+// The count pass of one wave whose coordinates are chunk k's.  known >= 0: the item starts at that local bit (chunk 0's bit 0; the first bit behind a member's
+// header) and is not confirmed.  SEARCH and known < 0: the wave tries the chunk's own bits, 64 consecutive ones a round (one a lane: gz_holds), and
+// confirms the survivors in ascending order by decoding the block (gz_item); the first confirmed one is the chunk's start.  Either way the decode goes on from
+// there, counting, to the item's end.  Returns the item's row (sync_bit -1: no start found).  TERMINATION: the search visits each of the chunk's <= 8 C bits
+// once, each candidate's trial and the item's decode consume input that is bounded by gz_in_len.  BOUNDS: the payload is read below byte0 + in_len <=
+// payload_len only; nothing is written.
+template <bool SEARCH> __device__ __forceinline__ mahip_gzip_item_t gz_count(const uint8_t *__restrict__ payload, uint64_t payload_len, uint64_t C, uint64_t k, int64_t known, InfTabs &tab,
+                                                                             GzCand *cand, unsigned lane)
+{
+	const uint64_t byte0 = k * C, CB = C * 8;
+	InfState s;
+	gz_state(s, payload + byte0, gz_in_len(payload_len, byte0, C), lane);
+	GzOut o;
+	o.op = o.fp = o.lim = o.before = 0; o.out = nullptr;
+	uint64_t start = 0, end = 0;
+	uint32_t st = GZ_UNCONFIRMED, fin = 0, nblk[3] = {0, 0, 0};
+	if (!SEARCH || known >= 0) { start = (uint64_t)known; st = gz_item<false>(s, tab, nullptr, o, start, CB, 0, false, &end, &fin, nblk); }
+	else {
+		const uint64_t own_bits = payload_len - byte0 < C ? (payload_len - byte0) * 8 : CB;
+		for (uint64_t base = 0; base < own_bits && st == GZ_UNCONFIRMED; base += 64) {
+			const uint64_t bit = base + lane;
+			uint64_t m = wv_ballot(bit < own_bits && gz_holds(s.in, s.in_len, bit, cand->cnt[lane], cand->sym[lane]));
+			while (m) {
+				start = base + (uint64_t)(__ffsll((long long)m) - 1);
+				m &= m - 1;
+				o.op = 0;
+				st = gz_item<false>(s, tab, nullptr, o, start, CB, 0, true, &end, &fin, nblk);
+				if (st != GZ_UNCONFIRMED) break;
+			}
+		}
+	}
+	mahip_gzip_item_t r;
+	if (st == GZ_UNCONFIRMED) { r.sync_bit = -1; r.end_bit = 0; r.out_len = 0; r.status = 0; r.flags = 0; }
+	else { r.sync_bit = (int64_t)(byte0 * 8 + start); r.end_bit = byte0 * 8 + end; r.out_len = o.op; r.status = st ? gz_reason(st) : 0u; r.flags = fin ? MAHIP_GZIP_SAW_FINAL : 0u; }
+	return r;
+}
+
+// One wave per chunk: chunk 0 starts at bit 0, every other chunk looks for its first block start (gz_count).  One row is written, rows[k], k < n_chunks.
 __global__ __launch_bounds__(256) void k_gz_sync_count(const uint8_t *__restrict__ payload, uint64_t payload_len, uint64_t C, uint64_t n_chunks, mahip_gzip_item_t *__restrict__ rows)
 {
 	__shared__ InfTabs s_tab[GZ_CNT_WAVES];
@@ -615,37 +652,67 @@ __global__ __launch_bounds__(256) void k_gz_sync_count(const uint8_t *__restrict
 	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const uint64_t k = (uint64_t)blockIdx.x * GZ_CNT_WAVES + wave;
 	if (k >= n_chunks) return; // the whole wave; nothing below waits for another wave
-	const uint64_t byte0 = k * C, CB = C * 8;
-	InfState s;
-	gz_state(s, payload + byte0, gz_in_len(payload_len, byte0, C), lane);
-	const uint64_t own_bits = payload_len - byte0 < C ? (payload_len - byte0) * 8 : CB;
-	GzOut o;
-	o.op = o.fp = o.lim = o.before = 0; o.out = nullptr;
-	uint64_t start = 0, end = 0;
-	uint32_t st = GZ_UNCONFIRMED, fin = 0, nblk[3] = {0, 0, 0};
-	if (k == 0) st = gz_item<false>(s, s_tab[wave], nullptr, o, 0, CB, 0, false, &end, &fin, nblk);
-	else {
-		for (uint64_t base = 0; base < own_bits && st == GZ_UNCONFIRMED; base += 64) {
-			const uint64_t bit = base + lane;
-			uint64_t m = wv_ballot(bit < own_bits && gz_holds(s.in, s.in_len, bit, s_cand[wave].cnt[lane], s_cand[wave].sym[lane]));
-			while (m) {
-				start = base + (uint64_t)(__ffsll((long long)m) - 1);
-				m &= m - 1;
-				o.op = 0;
-				st = gz_item<false>(s, s_tab[wave], nullptr, o, start, CB, 0, true, &end, &fin, nblk);
-				if (st != GZ_UNCONFIRMED) break;
-			}
+	const mahip_gzip_item_t r = gz_count<true>(payload, payload_len, C, k, k == 0 ? 0 : -1, s_tab[wave], &s_cand[wave], lane);
+	if (lane == 0) rows[k] = r;
+}
+
+// Concatenated members (include/mahip.h).  Every byte position p in [from, nbytes - 4] whose four bytes read 1f 8b 08 FLG with FLG's bits 5..7 clear goes
+// into list[] (in any order: the host sorts it); *count = how many there are, which may exceed cap -- nothing is written at or behind list[cap].  A lane takes
+// the 4 positions of one aligned 32-bit word (it loads that word and the next), a wave 256 consecutive positions; a ballot says whether the wave has a hit at
+// all (it hardly ever has), and then ONE atomic of lane 0 reserves the wave's cells.  TERMINATION: a counted grid-stride loop, the same trip count for every
+// lane of a wave.  BOUNDS: comp is read below nbytes only (word loads where both words lie below it and comp is word-aligned, else bytewise).
+__global__ __launch_bounds__(256) void k_gz_member_scan(const uint8_t *__restrict__ comp, uint64_t nbytes, uint64_t from, uint64_t cap, uint64_t *__restrict__ list,
+                                                        unsigned long long *__restrict__ count)
+{
+	const unsigned lane = threadIdx.x & 63;
+	const uint64_t n_words = (nbytes + 3) / 4, stride = (uint64_t)gridDim.x * 256;
+	const bool aligned = ((uintptr_t)comp & 3u) == 0;
+	const uint32_t *w32 = (const uint32_t*)comp;
+	for (uint64_t base = ((uint64_t)blockIdx.x * 256 + threadIdx.x) - lane; base < n_words; base += stride) {
+		const uint64_t i = base + lane, b = 4 * i;
+		uint64_t v = 0;
+		if (aligned && b + 8 <= nbytes) v = (uint64_t)w32[i] | (uint64_t)w32[i + 1] << 32;
+		else for (uint32_t q = 0; q < 8; ++q) if (b + q < nbytes) v |= (uint64_t)comp[b + q] << (8 * q);
+		uint32_t hm = 0;
+		for (uint32_t q = 0; q < 4; ++q) {
+			const uint64_t p = b + q;
+			if (p >= from && p + 4 <= nbytes && ((uint32_t)(v >> (8 * q)) & 0xe0ffffffu) == 0x00088b1fu) hm |= 1u << q;
 		}
-	}
-	if (lane == 0) {
-		mahip_gzip_item_t r;
-		if (st == GZ_UNCONFIRMED) { r.sync_bit = -1; r.end_bit = 0; r.out_len = 0; r.status = 0; r.flags = 0; }
-		else { r.sync_bit = (int64_t)(byte0 * 8 + start); r.end_bit = byte0 * 8 + end; r.out_len = o.op; r.status = st ? gz_reason(st) : 0u; r.flags = fin ? MAHIP_GZIP_SAW_FINAL : 0u; }
-		rows[k] = r;
+		const uint64_t any = wv_ballot(hm != 0);
+		if (any == 0) continue; // (the whole wave)
+		const uint32_t mine = (uint32_t)__popc(hm);
+		uint32_t before = 0, total = 0;
+		for (uint64_t m = any; m; m &= m - 1) { // the lanes with a hit, ascending: a handful at the most
+			const unsigned l = (unsigned)(__ffsll((long long)m) - 1);
+			const uint32_t n = (uint32_t)__shfl((int)mine, (int)l, 64);
+			if (l < lane) before += n;
+			total += n;
+		}
+		unsigned long long at = 0;
+		if (lane == 0) at = atomicAdd(count, (unsigned long long)total);
+		const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)at, 0, 64), hi = (uint32_t)__shfl((int)(uint32_t)(at >> 32), 0, 64);
+		uint64_t cell = ((uint64_t)hi << 32 | lo) + before;
+		for (uint32_t q = 0; q < 4; ++q)
+			if (hm >> q & 1u) { if (cell < cap) list[cell] = b + q; ++cell; }
 	}
 }
 
-enum { GZ_RES_BAD = 0, GZ_RES_STORED, GZ_RES_FIXED, GZ_RES_DYNAMIC, GZ_RES_WORDS = 8 }; // res[GZ_RES_BAD] = min over the items with a status of item << 8 | status
+// One wave per candidate whose header parsed: the count pass from the first bit behind that header (head_bit[h], a bit of the payload), in the coordinates of
+// the chunk that bit lies in -- what k_gz_sync_count does for chunk 0, with the same limits (GZ_SPAN_MAX, gz_in_len).  Nothing is confirmed: whether a member
+// starts there the chain decides.  TERMINATION and BOUNDS: gz_count's; one row is written, rows[h], h < n_heads.
+__global__ __launch_bounds__(256) void k_gz_heads(const uint8_t *__restrict__ payload, uint64_t payload_len, uint64_t C, const uint64_t *__restrict__ head_bit, uint64_t n_heads,
+                                                  mahip_gzip_item_t *__restrict__ rows)
+{
+	__shared__ InfTabs s_tab[GZ_CNT_WAVES];
+	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+	const uint64_t h = (uint64_t)blockIdx.x * GZ_CNT_WAVES + wave;
+	if (h >= n_heads) return; // the whole wave
+	const uint64_t bit = head_bit[h], k = bit / (C * 8);
+	const mahip_gzip_item_t r = gz_count<false>(payload, payload_len, C, k, (int64_t)(bit - k * C * 8), s_tab[wave], nullptr, lane);
+	if (lane == 0) rows[h] = r;
+}
+
+enum { GZ_RES_BAD = 0, GZ_RES_STORED, GZ_RES_FIXED, GZ_RES_DYNAMIC, GZ_RES_CAND, GZ_RES_WORDS = 8 }; // res[GZ_RES_BAD] = min over the items with a status of item << 8 | status; res[GZ_RES_CAND]: k_gz_member_scan's count
 
 // One wave per chain item: the decode of the count pass again, now writing 16-bit symbols at sym[out_off ..] through the LDS ring of the last 32768 symbols.
 // It stops where the count pass stopped (end_bit) after as many symbols (out_len): anything else is a status.  BOUNDS: sym is written at out_off + p, p <
@@ -662,7 +729,7 @@ __global__ __launch_bounds__(128) void k_gz_decode(const uint8_t *__restrict__ p
 	InfState s;
 	gz_state(s, payload + byte0, gz_in_len(payload_len, byte0, C), lane);
 	GzOut o;
-	o.op = o.fp = 0; o.lim = it.out_len; o.before = it.out_off; o.out = sym + it.out_off;
+	o.op = o.fp = 0; o.lim = it.out_len; o.before = it.out_off - it.base; o.out = sym + it.out_off; // (before: the text of the item's OWN member in front of it)
 	uint64_t end = 0;
 	uint32_t fin = 0, nblk[3] = {0, 0, 0};
 	uint32_t st = gz_item<true>(s, s_lds[wave], s_lds[wave].ring, o, it.sync_bit - k * CB, CB, it.end_bit - k * CB, false, &end, &fin, nblk);
@@ -676,12 +743,18 @@ __global__ __launch_bounds__(128) void k_gz_decode(const uint8_t *__restrict__ p
 	}
 }
 
-// ONE workgroup, the only serial step: W[0] is the window in front of the stream (never referenced: k_gz_decode refuses a reach in front of the stream, it
-// knows out_off), W[j + 1] = the last 32768 cells of W[j] followed by item j's resolved symbols.  An item of fewer than 32768 bytes passes older cells on.
-// BOUNDS: W holds n_items windows; sym is read at out_off + [out_len - 32768, out_len) clipped to the item.
-__global__ __launch_bounds__(256) void k_gz_windows(const gz_chain_t *__restrict__ chain, uint64_t n_items, const uint16_t *__restrict__ sym, uint8_t *W)
+// One workgroup per MEMBER (item0[m] .. item0[m + 1] are its items), the only serial step, serial within a member only: the window of a member's first item
+// is the window in front of its stream, all zero and never referenced (k_gz_decode refuses a reach in front of the member, it knows how much of the member's
+// text lies in front of an item); W[j + 1] = the last 32768 cells of W[j] followed by item j's resolved symbols.  An item of fewer than 32768 bytes passes older
+// cells on.  BOUNDS: W holds n_items windows and a workgroup writes those of its own member's items only; sym is read at out_off + [out_len - 32768, out_len)
+// clipped to the item.
+__global__ __launch_bounds__(256) void k_gz_windows(const gz_chain_t *__restrict__ chain, const uint64_t *__restrict__ item0, const uint16_t *__restrict__ sym, uint8_t *W)
 {
-	for (uint64_t j = 0; j + 1 < n_items; ++j) {
+	const uint64_t j0 = item0[blockIdx.x], j1 = item0[blockIdx.x + 1];
+	if (j0 >= j1) return; // (the whole workgroup)
+	for (uint32_t i = threadIdx.x; i < GZ_WIN; i += 256) W[j0 * GZ_WIN + i] = 0;
+	__syncthreads();
+	for (uint64_t j = j0; j + 1 < j1; ++j) {
 		const uint64_t off = chain[j].out_off, n = chain[j].out_len;
 		const uint8_t *w0 = W + j * GZ_WIN;
 		uint8_t *w1 = W + (j + 1) * GZ_WIN;
@@ -714,9 +787,9 @@ __global__ __launch_bounds__(256) void k_gz_resolve(const gz_chain_t *__restrict
 	}
 }
 
-// one wave per GZ_CRC_PIECE bytes of text, as k_bgzf_crc per member; pc[piece] = the piece's CRC moved in front of ALL the text behind it (x^(8 n) with a 64-bit
-// n): the XOR of pc[] is the CRC of the text
-__global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text, uint64_t total, uint64_t n_pieces, uint32_t *__restrict__ pc)
+// one wave per piece of the table (at most GZ_CRC_PIECE bytes of ONE member's text), as k_bgzf_crc per member; pc[piece] = the piece's CRC moved in front of all
+// the text of its member that lies behind it (x^(8 n) with a 64-bit n): the XOR of a member's pc[] is the CRC of its text
+__global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text, const gz_piece_t *__restrict__ pieces, uint64_t n_pieces, uint32_t *__restrict__ pc)
 {
 	__shared__ uint32_t s_crc[256];
 	{
@@ -728,9 +801,9 @@ __global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text
 	const unsigned wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 	const uint64_t m = (uint64_t)blockIdx.x * 4 + wave;
 	if (m >= n_pieces) return;
-	const uint64_t p0 = m * GZ_CRC_PIECE;
-	const uint32_t size = total - p0 < GZ_CRC_PIECE ? (uint32_t)(total - p0) : GZ_CRC_PIECE;
-	const uint8_t *t = text + p0;
+	const gz_piece_t pp = pieces[m];
+	const uint32_t size = pp.size;
+	const uint8_t *t = text + pp.text_off;
 	const uint32_t piece = (size + 63u) / 64u;
 	const uint32_t b = lane * piece < size ? lane * piece : size, e = b + piece < size ? b + piece : size;
 	uint32_t crc = 0xffffffffu;
@@ -738,50 +811,80 @@ __global__ __launch_bounds__(256) void k_gz_crc(const uint8_t *__restrict__ text
 	crc = ~crc;
 	crc = inf_mulmod(crc, inf_xpow8(size - e));
 	for (int o = 32; o > 0; o >>= 1) crc ^= __shfl_xor(crc, o, 64);
-	if (lane == 0) pc[m] = inf_mulmod(crc, inf_xpow8_64(total - p0 - size));
+	if (lane == 0) pc[m] = inf_mulmod(crc, inf_xpow8_64(pp.behind));
 }
 
-extern "C" int ma_gzip_head(int fd, const void *mem, uint64_t nbytes, uint64_t *hdr_len, uint32_t *crc, uint32_t *isize);
+extern "C" int ma_gzip_head_at(int fd, const void *mem, uint64_t nbytes, uint64_t off, uint64_t *hdr_len);
+extern "C" int ma_gzip_trailer_at(int fd, const void *mem, uint64_t nbytes, uint64_t off, uint32_t *crc, uint32_t *isize);
 extern "C" size_t ma_gzip_chunk(void);
+extern "C" size_t ma_gzip_cand_cap(void);
 
-static void gzip_report(mahip_ctx *c, const mahip_gzip_info_t *info)
+static void gzip_report(mahip_ctx *c, const mahip_gzip_info_t *info, const mahip_gzip_members_info_t *mi)
 {
 	c->gzip_last = *info;
+	if (mi) c->gzip_mlast = *mi; else { memset(&c->gzip_mlast, 0, sizeof(c->gzip_mlast)); c->gzip_mlast.bad_member = -1; }
 	if (ma_timing_level() < 1) return;
 	fprintf(stderr, "[T::gzip] reader=%s reason=%d (%s) item=%lld chunks=%llu (%llu B each, %llu synced) items=%llu %.1f MB -> %.1f MB: upload %.3f sync+count %.3f decode %.3f windows %.3f resolve %.3f crc %.3f ms\n",
 	        info->reader == MAHIP_BGZF_DEVICE ? "device" : "host", info->reason, mahip_gzip_reason_name(info->reason), (long long)info->first_bad_item, (unsigned long long)info->n_chunks,
 	        (unsigned long long)info->chunk, (unsigned long long)info->n_synced, (unsigned long long)info->n_items, (double)info->comp_bytes / 1e6, (double)info->text_bytes / 1e6, info->laps_ms[0],
 	        info->laps_ms[1], info->laps_ms[2], info->laps_ms[3], info->laps_ms[4], info->laps_ms[5]);
+	if (mi) fprintf(stderr, "[T::gzip_members] members=%llu candidates=%llu heads=%llu member=%lld: scan %.3f heads %.3f ms\n", (unsigned long long)mi->n_members, (unsigned long long)mi->n_candidates,
+	                (unsigned long long)mi->n_heads, (long long)mi->bad_member, mi->laps_ms[0], mi->laps_ms[1]);
 }
 
-// the rows -> the chain (host; a few thousand rows).  Follows end_bit from chunk 0; returns the reason, *bad = the chain item it is about.
-static int gzip_chain(mahip_gzip_item_t *rows, uint64_t n_chunks, uint64_t CB, uint64_t hdr_len, uint64_t nbytes, uint32_t isize, gz_chain_t *chain, uint64_t *n_items, uint64_t *total, int64_t *bad)
+struct gz_head_t { uint64_t pos, hdr_len; }; // a candidate whose header parsed: where it starts in the file
+struct gz_src_t { int fd; const void *mem; uint64_t nbytes; };
+
+// the rows -> the chain (host; a few thousand rows).  Follows end_bit from chunk 0; where a member's final block ends it looks for the next member among the
+// candidates' head rows (include/mahip.h; none when the caller takes one member only).  Returns the reason, -1 on a read error; *bad = the chain item it is
+// about, *bad_member the member.  chain has room for n_chunks + n_heads + 1 items, mrows for n_heads + 1 members.
+static int gzip_chain(const gz_src_t &src, mahip_gzip_item_t *rows, uint64_t n_chunks, uint64_t CB, uint64_t hdr0, const gz_head_t *heads, mahip_gzip_item_t *head_rows, uint64_t n_heads,
+                      gz_chain_t *chain, uint64_t *n_items, uint64_t *total, int64_t *bad, mahip_gzip_member_t *mrows, uint64_t *n_members, int64_t *bad_member)
 {
-	uint64_t cur = 0, n = 0, tot = 0;
+	const uint64_t nbytes = src.nbytes;
+	uint64_t cur = 0, n = 0, tot = 0, m = 0, base = 0;
 	int reason = MAHIP_GZIP_OK;
-	*bad = -1;
+	mahip_gzip_item_t *r = &rows[0];
+	*bad = *bad_member = -1;
+	memset(&mrows[0], 0, sizeof(mrows[0]));
+	mrows[0].hdr_len = hdr0;
 	for (;;) {
-		mahip_gzip_item_t &r = rows[cur];
-		r.flags |= MAHIP_GZIP_ON_CHAIN;
-		chain[n].sync_bit = (uint64_t)r.sync_bit; chain[n].end_bit = r.end_bit; chain[n].out_off = tot; chain[n].out_len = r.out_len;
-		++n;
-		if (r.status) { reason = (int)r.status; *bad = (int64_t)n - 1; break; }
-		tot += r.out_len;
-		if (r.flags & MAHIP_GZIP_SAW_FINAL) {
-			if (hdr_len + (r.end_bit + 7) / 8 + 8 != nbytes) { reason = MAHIP_GZIP_MULTI_MEMBER; *bad = (int64_t)n - 1; }
-			break;
+		if (n >= n_chunks + n_heads) { reason = MAHIP_GZIP_SYNC_MISMATCH; *bad = (int64_t)n; *bad_member = (int64_t)m; break; } // (cannot be: every row is visited once at the most)
+		r->flags |= MAHIP_GZIP_ON_CHAIN;
+		chain[n].sync_bit = (uint64_t)r->sync_bit; chain[n].end_bit = r->end_bit; chain[n].out_off = tot; chain[n].out_len = r->out_len; chain[n].base = base;
+		++n; ++mrows[m].n_items;
+		if (r->status) { reason = (int)r->status; *bad = (int64_t)n - 1; *bad_member = (int64_t)m; break; }
+		tot += r->out_len;
+		mrows[m].text_len = tot - base;
+		if (r->flags & MAHIP_GZIP_SAW_FINAL) { // the member ends here: its trailer, and then the end of the file or the next member
+			const uint64_t q = hdr0 + (r->end_bit + 7) / 8 + 8;
+			uint64_t h = n_heads;
+			if (q < nbytes) {
+				uint64_t lo = 0, hi = n_heads;
+				while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (heads[mid].pos < q) lo = mid + 1; else hi = mid; }
+				if (lo < n_heads && heads[lo].pos == q) h = lo;
+			}
+			if (q != nbytes && h == n_heads) { reason = MAHIP_GZIP_MULTI_MEMBER; *bad = (int64_t)n - 1; *bad_member = (int64_t)m; break; }
+			if (ma_gzip_trailer_at(src.fd, src.mem, nbytes, q - 8, &mrows[m].crc, &mrows[m].isize) != 0) return -1;
+			if ((uint32_t)(tot - base) != mrows[m].isize) { reason = MAHIP_GZIP_ISIZE; *bad_member = (int64_t)m; break; }
+			if (q == nbytes) break;
+			++m; base = tot;
+			memset(&mrows[m], 0, sizeof(mrows[m]));
+			mrows[m].comp_off = q; mrows[m].hdr_len = heads[h].hdr_len; mrows[m].text_off = tot;
+			r = &head_rows[h]; // (a head item may end in the chunk it starts in: a member may be far smaller than a chunk)
+			cur = (uint64_t)r->sync_bit / CB;
+			continue;
 		}
-		const uint64_t next = r.end_bit / CB;
-		if (next <= cur || next >= n_chunks || rows[next].sync_bit != (int64_t)r.end_bit) { reason = MAHIP_GZIP_SYNC_MISMATCH; *bad = (int64_t)n; break; } // (the first two cannot be: an item ends at a block start in a later chunk)
-		cur = next;
+		const uint64_t next = r->end_bit / CB;
+		if (next <= cur || next >= n_chunks || rows[next].sync_bit != (int64_t)r->end_bit) { reason = MAHIP_GZIP_SYNC_MISMATCH; *bad = (int64_t)n; *bad_member = (int64_t)m; break; } // (the first two cannot be: an item that is not the last of its member ends at a block start in a later chunk)
+		cur = next; r = &rows[next];
 	}
-	if (reason == MAHIP_GZIP_OK && (uint32_t)tot != isize) reason = MAHIP_GZIP_ISIZE;
-	*n_items = n; *total = tot;
+	*n_items = n; *total = tot; *n_members = m + 1;
 	return reason;
 }
 
-// as bgzf_run.  chunk 0: MA_GZIP_CHUNK or the default.
-static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int target, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info)
+// as bgzf_run.  chunk 0: MA_GZIP_CHUNK or the default.  members: concatenated members are taken (include/mahip.h), else the first must be the only one.
+static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int target, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info, bool members)
 {
 	HIPCHK(hipSetDevice(c->dev));
 	memset(info, 0, sizeof(*info));
@@ -790,25 +893,36 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 	if (chunk < 1024 || chunk > GZ_CHUNK_MAX || (chunk & (chunk - 1))) { mahip_set_error("mahip_gzip_load: chunk size %zu is not a power of two in 1024 .. %zu", chunk, GZ_CHUNK_MAX); return -1; }
 	info->chunk = chunk;
 	free(c->gzip_rows); c->gzip_rows = nullptr; c->gzip_n_rows = 0;
+	free(c->gzip_members); c->gzip_members = nullptr; c->gzip_n_members = 0;
+	mahip_gzip_members_info_t minfo;
+	memset(&minfo, 0, sizeof(minfo));
+	minfo.bad_member = -1; minfo.cand_cap = members ? ma_gzip_cand_cap() : 0;
+	const mahip_gzip_members_info_t *mi = members ? &minfo : nullptr;
+	const gz_src_t src = {fd, mem, nbytes};
 	uint64_t hdr_len = 0;
-	uint32_t crc = 0, isize = 0;
 	double t0 = bg_now(), t1;
-	const int hr = ma_gzip_head(fd, mem, nbytes, &hdr_len, &crc, &isize);
+	const int hr = ma_gzip_head_at(fd, mem, nbytes, 0, &hdr_len);
 	if (hr < 0) { mahip_set_error("mahip_gzip_load: cannot read the compressed input"); return -1; }
 	info->reason = hr;
-	if (hr != MAHIP_GZIP_OK) { gzip_report(c, info); return 0; }
+	if (hr != MAHIP_GZIP_OK) { gzip_report(c, info, mi); return 0; }
 	const uint64_t payload_len = nbytes - hdr_len - 8, n_chunks = payload_len ? (payload_len + chunk - 1) / chunk : 1, CB = (uint64_t)chunk * 8;
 	info->n_chunks = n_chunks;
-	DevBuf d_comp, d_rows, d_chain, d_sym, d_W, d_pc, d_res, d_own;
+	DevBuf d_comp, d_rows, d_chain, d_sym, d_W, d_pc, d_res, d_own, d_cand, d_hbit, d_hrows, d_item0, d_pieces;
 	void *d_text = nullptr;
 	mahip_gzip_item_t *rows = (mahip_gzip_item_t*)malloc((size_t)n_chunks * sizeof(*rows));
-	gz_chain_t *chain = (gz_chain_t*)malloc((size_t)(n_chunks + 1) * sizeof(*chain));
-	uint32_t *h_pc = nullptr;
-	uint64_t n_items = 0, total = 0, n_pieces = 0;
+	std::vector<gz_chain_t> chain;
+	std::vector<uint64_t> cand, hbit, item0;
+	std::vector<gz_head_t> heads;
+	std::vector<mahip_gzip_item_t> head_rows;
+	std::vector<mahip_gzip_member_t> mrows;
+	std::vector<gz_piece_t> pieces;
+	std::vector<uint32_t> h_pc;
+	uint64_t n_items = 0, total = 0, n_pieces = 0, n_members = 0;
 	int rc = 0;
 	bool said = false; // the error message is set
-	if (rows == nullptr || chain == nullptr) { free(rows); free(chain); mahip_set_error("mahip_gzip_load: out of host memory"); return -1; }
-	if (dev_reserve(c, d_comp, nbytes + 64) != 0 || dev_reserve(c, d_rows, (size_t)n_chunks * sizeof(*rows)) != 0 || dev_reserve(c, d_res, GZ_RES_WORDS * 8) != 0) info->reason = MAHIP_GZIP_NOMEM;
+	if (rows == nullptr) { mahip_set_error("mahip_gzip_load: out of host memory"); return -1; }
+	if (dev_reserve(c, d_comp, nbytes + 64) != 0 || dev_reserve(c, d_rows, (size_t)n_chunks * sizeof(*rows)) != 0 || dev_reserve(c, d_res, GZ_RES_WORDS * 8) != 0 ||
+	    (members && dev_reserve(c, d_cand, (size_t)minfo.cand_cap * 8) != 0)) info->reason = MAHIP_GZIP_NOMEM;
 	do { // (one pass; `break` with rc = -1: a real error; with rc = 0: done, info->reason says how)
 		if (info->reason != MAHIP_GZIP_OK) break;
 		const uint8_t *payload = (const uint8_t*)d_comp.p + hdr_len;
@@ -817,6 +931,32 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 		if (hipMemsetAsync(d_res.p, 0, GZ_RES_WORDS * 8, c->st) != hipSuccess || hipMemsetAsync(d_res.p, 0xff, 8, c->st) != hipSuccess) break;
 		if (hipStreamSynchronize(c->st) != hipSuccess) break;
 		info->laps_ms[0] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		if (members) { // where may a further member start?  Candidates from the device, their headers read here
+			unsigned long long n_cand = 0;
+			{
+				const uint64_t n_words = (nbytes + 3) / 4, want = (n_words + 255) / 256;
+				ProfScope ps(c, "k_gz_member_scan", (double)nbytes);
+				hipLaunchKernelGGL(k_gz_member_scan, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, c->st, (const uint8_t*)d_comp.p, (uint64_t)nbytes, hdr_len, (uint64_t)minfo.cand_cap,
+				                   (uint64_t*)d_cand.p, P<unsigned long long>(d_res) + GZ_RES_CAND);
+				if (hipGetLastError() != hipSuccess) break;
+			}
+			if (hipMemcpyAsync(&n_cand, P<unsigned long long>(d_res) + GZ_RES_CAND, 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+			minfo.n_candidates = n_cand;
+			if (n_cand > minfo.cand_cap) { info->reason = MAHIP_GZIP_TOO_MANY_CANDIDATES; rc = 0; break; }
+			cand.resize((size_t)n_cand);
+			if (n_cand && (hipMemcpyAsync(cand.data(), d_cand.p, (size_t)n_cand * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) break;
+			std::sort(cand.begin(), cand.end());
+			bool io = false;
+			for (uint64_t p : cand) {
+				uint64_t hl = 0;
+				const int r = ma_gzip_head_at(fd, mem, nbytes, p, &hl);
+				if (r < 0) { io = true; break; }
+				if (r == MAHIP_GZIP_OK) { heads.push_back({p, hl}); hbit.push_back((p + hl - hdr_len) * 8); } // (p + hl + 8 <= nbytes: the bit lies in the payload, or is its end)
+			}
+			if (io) { mahip_set_error("mahip_gzip_load: cannot read the compressed input"); said = true; break; }
+			minfo.n_heads = heads.size();
+			minfo.laps_ms[0] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
+		}
 		{
 			ProfScope ps(c, "k_gz_sync_count", (double)payload_len);
 			hipLaunchKernelGGL(k_gz_sync_count, dim3((unsigned)((n_chunks + GZ_CNT_WAVES - 1) / GZ_CNT_WAVES)), dim3(256), 0, c->st, payload, payload_len, (uint64_t)chunk, n_chunks, (mahip_gzip_item_t*)d_rows.p);
@@ -824,8 +964,30 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 		}
 		if (hipMemcpyAsync(rows, d_rows.p, (size_t)n_chunks * sizeof(*rows), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
 		for (uint64_t k = 0; k < n_chunks; ++k) info->n_synced += rows[k].sync_bit >= 0;
-		info->reason = gzip_chain(rows, n_chunks, CB, hdr_len, nbytes, isize, chain, &n_items, &total, &info->first_bad_item);
-		chain[n_items].sync_bit = chain[n_items].end_bit = 0; chain[n_items].out_off = total; chain[n_items].out_len = 0;
+		if (!heads.empty()) { // the head items: one wave per candidate that may begin a member
+			const uint64_t nh = heads.size();
+			const double th = bg_now();
+			head_rows.resize((size_t)nh);
+			if (dev_reserve(c, d_hbit, (size_t)nh * 8) != 0 || dev_reserve(c, d_hrows, (size_t)nh * sizeof(mahip_gzip_item_t)) != 0) { info->reason = MAHIP_GZIP_NOMEM; rc = 0; break; }
+			if (hipMemcpyAsync(d_hbit.p, hbit.data(), (size_t)nh * 8, hipMemcpyHostToDevice, c->st) != hipSuccess) break;
+			{
+				ProfScope ps(c, "k_gz_heads", (double)payload_len);
+				hipLaunchKernelGGL(k_gz_heads, dim3((unsigned)((nh + GZ_CNT_WAVES - 1) / GZ_CNT_WAVES)), dim3(256), 0, c->st, payload, payload_len, (uint64_t)chunk, (const uint64_t*)d_hbit.p, nh, (mahip_gzip_item_t*)d_hrows.p);
+				if (hipGetLastError() != hipSuccess) break;
+			}
+			if (hipMemcpyAsync(head_rows.data(), d_hrows.p, (size_t)nh * sizeof(mahip_gzip_item_t), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
+			minfo.laps_ms[1] = ((t1 = bg_now()) - th) * 1e3;
+			t0 += t1 - th; // (the lap below is the chunks' pass and the chain, as ever)
+		}
+		chain.resize((size_t)(n_chunks + heads.size() + 1));
+		mrows.resize(heads.size() + 1);
+		{
+			const int cr = gzip_chain(src, rows, n_chunks, CB, hdr_len, heads.data(), head_rows.data(), heads.size(), chain.data(), &n_items, &total, &info->first_bad_item, mrows.data(), &n_members, &minfo.bad_member);
+			if (cr < 0) { mahip_set_error("mahip_gzip_load: cannot read the compressed input"); said = true; break; }
+			info->reason = cr;
+		}
+		minfo.n_members = n_members;
+		chain[n_items].sync_bit = chain[n_items].end_bit = 0; chain[n_items].out_off = total; chain[n_items].out_len = 0; chain[n_items].base = total;
 		info->n_items = n_items; info->text_bytes = total;
 		info->laps_ms[1] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
 		rc = 0;
@@ -840,14 +1002,28 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 			if (dev_reserve(c, d_own, (size_t)total + 64) != 0) { info->reason = MAHIP_GZIP_NOMEM; break; }
 			d_text = d_own.p;
 		}
-		n_pieces = (total + GZ_CRC_PIECE - 1) / GZ_CRC_PIECE;
-		if (dev_reserve(c, d_chain, (size_t)(n_items + 1) * sizeof(*chain)) != 0 || dev_reserve(c, d_sym, 2 * (size_t)total + 64) != 0 || dev_reserve(c, d_W, (size_t)n_items * GZ_WIN) != 0 ||
-		    dev_reserve(c, d_pc, (size_t)n_pieces * 4 + 64) != 0) { info->reason = MAHIP_GZIP_NOMEM; break; }
-		h_pc = (uint32_t*)malloc((size_t)n_pieces * 4 + 4);
+		// the members' first items, and the CRC's pieces: at most GZ_CRC_PIECE bytes, none across a member's end
+		item0.resize((size_t)n_members + 1);
+		item0[0] = 0;
+		for (uint64_t m = 0; m < n_members; ++m) {
+			item0[m + 1] = item0[m] + mrows[m].n_items;
+			for (uint64_t o = 0; o < mrows[m].text_len; o += GZ_CRC_PIECE) {
+				gz_piece_t pp;
+				pp.size = mrows[m].text_len - o < GZ_CRC_PIECE ? (uint32_t)(mrows[m].text_len - o) : GZ_CRC_PIECE;
+				pp.text_off = mrows[m].text_off + o; pp.behind = mrows[m].text_len - o - pp.size; pp.member = (uint32_t)m;
+				pieces.push_back(pp);
+			}
+		}
+		n_pieces = pieces.size();
+		if (dev_reserve(c, d_chain, (size_t)(n_items + 1) * sizeof(gz_chain_t)) != 0 || dev_reserve(c, d_sym, 2 * (size_t)total + 64) != 0 || dev_reserve(c, d_W, (size_t)n_items * GZ_WIN) != 0 ||
+		    dev_reserve(c, d_pc, (size_t)n_pieces * 4 + 64) != 0 || dev_reserve(c, d_item0, (size_t)(n_members + 1) * 8) != 0 || dev_reserve(c, d_pieces, (size_t)n_pieces * sizeof(gz_piece_t) + 64) != 0) {
+			info->reason = MAHIP_GZIP_NOMEM; break;
+		}
+		h_pc.resize((size_t)n_pieces + 1);
 		rc = -1;
-		if (h_pc == nullptr) break;
-		if (hipMemcpyAsync(d_chain.p, chain, (size_t)(n_items + 1) * sizeof(*chain), hipMemcpyHostToDevice, c->st) != hipSuccess) break;
-		if (hipMemsetAsync(d_W.p, 0, GZ_WIN, c->st) != hipSuccess) break;
+		if (hipMemcpyAsync(d_chain.p, chain.data(), (size_t)(n_items + 1) * sizeof(gz_chain_t), hipMemcpyHostToDevice, c->st) != hipSuccess) break;
+		if (hipMemcpyAsync(d_item0.p, item0.data(), (size_t)(n_members + 1) * 8, hipMemcpyHostToDevice, c->st) != hipSuccess) break;
+		if (n_pieces && hipMemcpyAsync(d_pieces.p, pieces.data(), (size_t)n_pieces * sizeof(gz_piece_t), hipMemcpyHostToDevice, c->st) != hipSuccess) break;
 		unsigned long long h_res[GZ_RES_WORDS];
 		{
 			ProfScope ps(c, "k_gz_decode", (double)payload_len + 2.0 * (double)total);
@@ -858,10 +1034,14 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 		if (hipMemcpyAsync(h_res, d_res.p, GZ_RES_WORDS * 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
 		info->laps_ms[2] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
 		info->n_stored = h_res[GZ_RES_STORED]; info->n_fixed = h_res[GZ_RES_FIXED]; info->n_dynamic = h_res[GZ_RES_DYNAMIC];
-		if (h_res[GZ_RES_BAD] != ~0ull) { info->reason = (int)(h_res[GZ_RES_BAD] & 255u); info->first_bad_item = (int64_t)(h_res[GZ_RES_BAD] >> 8); rc = 0; break; }
+		if (h_res[GZ_RES_BAD] != ~0ull) {
+			info->reason = (int)(h_res[GZ_RES_BAD] & 255u); info->first_bad_item = (int64_t)(h_res[GZ_RES_BAD] >> 8); rc = 0;
+			for (uint64_t m = 0; m < n_members; ++m) if ((uint64_t)info->first_bad_item >= item0[m] && (uint64_t)info->first_bad_item < item0[m + 1]) minfo.bad_member = (int64_t)m;
+			break;
+		}
 		{
 			ProfScope ps(c, "k_gz_windows", 3.0 * (double)n_items * GZ_WIN);
-			hipLaunchKernelGGL(k_gz_windows, dim3(1), dim3(256), 0, c->st, (const gz_chain_t*)d_chain.p, n_items, (const uint16_t*)d_sym.p, (uint8_t*)d_W.p);
+			hipLaunchKernelGGL(k_gz_windows, dim3((unsigned)n_members), dim3(256), 0, c->st, (const gz_chain_t*)d_chain.p, (const uint64_t*)d_item0.p, (const uint16_t*)d_sym.p, (uint8_t*)d_W.p);
 			if (hipGetLastError() != hipSuccess) break;
 		}
 		if (hipStreamSynchronize(c->st) != hipSuccess) break;
@@ -874,59 +1054,90 @@ static int gzip_run(mahip_ctx *c, int fd, const void *mem, size_t nbytes, int ta
 		}
 		if (hipStreamSynchronize(c->st) != hipSuccess) break;
 		info->laps_ms[4] = ((t1 = bg_now()) - t0) * 1e3; t0 = t1;
-		uint32_t got = 0;
 		if (n_pieces) {
 			{
 				ProfScope ps(c, "k_gz_crc", (double)total);
-				hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, c->st, (const uint8_t*)d_text, total, n_pieces, (uint32_t*)d_pc.p);
+				hipLaunchKernelGGL(k_gz_crc, dim3((unsigned)((n_pieces + 3) / 4)), dim3(256), 0, c->st, (const uint8_t*)d_text, (const gz_piece_t*)d_pieces.p, n_pieces, (uint32_t*)d_pc.p);
 				if (hipGetLastError() != hipSuccess) break;
 			}
-			if (hipMemcpyAsync(h_pc, d_pc.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
-			for (uint64_t m = 0; m < n_pieces; ++m) got ^= h_pc[m];
+			if (hipMemcpyAsync(h_pc.data(), d_pc.p, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) break;
 		}
 		info->laps_ms[5] = (bg_now() - t0) * 1e3;
 		rc = 0;
-		if (got != crc) { info->reason = MAHIP_GZIP_CRC; break; }
+		{ // every member's pieces against its own trailer (a member without text: no piece, CRC 0)
+			std::vector<uint32_t> got((size_t)n_members, 0u);
+			for (uint64_t k = 0; k < n_pieces; ++k) got[pieces[k].member] ^= h_pc[k];
+			for (uint64_t m = 0; m < n_members && info->reason == MAHIP_GZIP_OK; ++m) if (got[m] != mrows[m].crc) { info->reason = MAHIP_GZIP_CRC; minfo.bad_member = (int64_t)m; }
+		}
+		if (info->reason != MAHIP_GZIP_OK) break;
 		if (target == 0 && total) rc = xfer_copy(c, d_text, out, (size_t)total, 0);
 	} while (0);
 	if (rc != 0 && !said) mahip_set_error("mahip_gzip_load: upload, launch or copy failed (%s)", hipGetErrorString(hipGetLastError()));
 	(void)hipStreamSynchronize(c->st);
 	dev_free(c, d_comp); dev_free(c, d_rows); dev_free(c, d_chain); dev_free(c, d_sym); dev_free(c, d_W); dev_free(c, d_pc); dev_free(c, d_res); dev_free(c, d_own);
-	free(chain); free(h_pc);
+	dev_free(c, d_cand); dev_free(c, d_hbit); dev_free(c, d_hrows); dev_free(c, d_item0); dev_free(c, d_pieces);
 	c->gzip_rows = rows; c->gzip_n_rows = info->laps_ms[1] > 0 ? n_chunks : 0; // (rows that were never downloaded are not rows)
+	if (members && n_members) {
+		c->gzip_members = (mahip_gzip_member_t*)malloc((size_t)n_members * sizeof(mahip_gzip_member_t));
+		if (c->gzip_members) { memcpy(c->gzip_members, mrows.data(), (size_t)n_members * sizeof(mahip_gzip_member_t)); c->gzip_n_members = n_members; }
+	}
 	if (rc == 0 && info->reason == MAHIP_GZIP_OK) {
 		info->reader = MAHIP_BGZF_DEVICE;
 		if (target == MAHIP_BGZF_PAF) paf_text_loaded(c); else if (target == MAHIP_BGZF_FASTX) fx_text_loaded(c);
 	} else { // nothing stays loaded: the caller inflates with zlib
 		if (target == MAHIP_BGZF_PAF) (void)mahip_paf_release(c); else if (target == MAHIP_BGZF_FASTX) (void)mahip_fastx_release(c);
 	}
-	if (rc == 0) gzip_report(c, info); else c->gzip_last = *info;
+	if (rc == 0) gzip_report(c, info, mi); else { c->gzip_last = *info; c->gzip_mlast = minfo; }
 	return rc;
 }
 
+static int gzip_target_ok(int target, const char *who)
+{
+	if (target != MAHIP_BGZF_PAF && target != MAHIP_BGZF_FASTX) { mahip_set_error("%s: target %d", who, target); return -1; }
+	return 0;
+}
 extern "C" int mahip_gzip_load_fd(mahip_ctx_t *c, int fd, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
 {
-	if (target != MAHIP_BGZF_PAF && target != MAHIP_BGZF_FASTX) { mahip_set_error("mahip_gzip_load_fd: target %d", target); return -1; }
-	return gzip_run(c, fd, nullptr, nbytes, target, chunk, nullptr, 0, info);
+	if (gzip_target_ok(target, "mahip_gzip_load_fd") != 0) return -1;
+	return gzip_run(c, fd, nullptr, nbytes, target, chunk, nullptr, 0, info, false);
 }
 extern "C" int mahip_gzip_load_mem(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
 {
-	if (target != MAHIP_BGZF_PAF && target != MAHIP_BGZF_FASTX) { mahip_set_error("mahip_gzip_load_mem: target %d", target); return -1; }
-	return gzip_run(c, -1, comp, nbytes, target, chunk, nullptr, 0, info);
+	if (gzip_target_ok(target, "mahip_gzip_load_mem") != 0) return -1;
+	return gzip_run(c, -1, comp, nbytes, target, chunk, nullptr, 0, info, false);
 }
-extern "C" int mahip_gzip_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info) { return gzip_run(c, -1, comp, ncomp, 0, chunk, out, out_cap, info); }
+extern "C" int mahip_gzip_inflate_mem(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info) { return gzip_run(c, -1, comp, ncomp, 0, chunk, out, out_cap, info, false); }
+extern "C" int mahip_gzip_load_fd_members(mahip_ctx_t *c, int fd, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
+{
+	if (gzip_target_ok(target, "mahip_gzip_load_fd_members") != 0) return -1;
+	return gzip_run(c, fd, nullptr, nbytes, target, chunk, nullptr, 0, info, true);
+}
+extern "C" int mahip_gzip_load_mem_members(mahip_ctx_t *c, const void *comp, size_t nbytes, int target, size_t chunk, mahip_gzip_info_t *info)
+{
+	if (gzip_target_ok(target, "mahip_gzip_load_mem_members") != 0) return -1;
+	return gzip_run(c, -1, comp, nbytes, target, chunk, nullptr, 0, info, true);
+}
+extern "C" int mahip_gzip_inflate_mem_members(mahip_ctx_t *c, const void *comp, size_t ncomp, size_t chunk, void *out, size_t out_cap, mahip_gzip_info_t *info) { return gzip_run(c, -1, comp, ncomp, 0, chunk, out, out_cap, info, true); }
 extern "C" int mahip_gzip_last(mahip_ctx_t *c, mahip_gzip_info_t *out) { *out = c->gzip_last; return 0; }
-extern "C" void mahip_gzip_note(mahip_ctx_t *c, const mahip_gzip_info_t *in) { c->gzip_last = *in; }
+extern "C" void mahip_gzip_note(mahip_ctx_t *c, const mahip_gzip_info_t *in) { c->gzip_last = *in; memset(&c->gzip_mlast, 0, sizeof(c->gzip_mlast)); c->gzip_mlast.bad_member = -1; }
+extern "C" int mahip_gzip_members_last(mahip_ctx_t *c, mahip_gzip_members_info_t *out) { *out = c->gzip_mlast; return 0; }
 extern "C" uint64_t mahip_gzip_items_download(mahip_ctx_t *c, mahip_gzip_item_t *out, uint64_t cap)
 {
 	const uint64_t n = c->gzip_n_rows < cap ? c->gzip_n_rows : cap;
 	if (n) memcpy(out, c->gzip_rows, (size_t)n * sizeof(*out));
 	return n;
 }
+extern "C" uint64_t mahip_gzip_members_download(mahip_ctx_t *c, mahip_gzip_member_t *out, uint64_t cap)
+{
+	const uint64_t n = c->gzip_n_members < cap ? c->gzip_n_members : cap;
+	if (n) memcpy(out, c->gzip_members, (size_t)n * sizeof(*out));
+	return n;
+}
 extern "C" const char *mahip_gzip_reason_name(int reason)
 {
 	static const char *const nm[] = {"ok", "not a gzip header this reader takes", "more than one member, or trailing bytes", "no block start within the span", "an item ends where the next does not start",
 	                                 "the items' total is not ISIZE", "block type 3", "stored block: LEN does not match NLEN", "invalid code lengths", "invalid symbol", "a distance reaches in front of the stream",
-	                                 "more output than counted", "the deflate bytes end early", "less output than counted", "CRC mismatch", "not enough device memory", "not a regular file", "MA_GZIP_DEVICE is off", "no text"};
+	                                 "more output than counted", "the deflate bytes end early", "less output than counted", "CRC mismatch", "not enough device memory", "not a regular file", "MA_GZIP_DEVICE is off", "no text",
+	                                 "more member candidates than the list holds"};
 	return reason >= 0 && reason < (int)(sizeof(nm) / sizeof(nm[0])) ? nm[reason] : "?";
 }

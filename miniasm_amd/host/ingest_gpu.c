@@ -2,7 +2,7 @@
  *
  * The host only moves bytes: a plain file goes from the page cache straight into pinned staging slots and on to
  * HBM (mahip_paf_load_fd); a bgzip-compressed (BGZF) file goes to HBM as it is and is inflated there, one wave per block (mahip_bgzf_load_fd; the walk over
- * its member chain is below); a plain gzip file can be cut into chunks and inflated there too (MA_GZIP_DEVICE=1: mahip_gzip_load_fd; its header and trailer are
+ * its member chain is below); a plain gzip file, one member or several, can be cut into chunks and inflated there too (MA_GZIP_DEVICE=1: mahip_gzip_load_fd_members; headers and trailers are
  * read below); otherwise gzip / stdin input is read by zlib (as the reference does through gzread) one PIECE of whole lines at a time, and piece k is uploaded
  * and parsed (mahip_paf_stream_piece_mem) while a second thread inflates piece k + 1 (ma_hit_ingest_stream below); MA_INGEST_STREAM=0, -R (unless
  * MA_STREAM_NOCONT=1: ma_hit_ingest_stream_excl) and ma_paf_load_file inflate the whole text into memory first and upload it.  Lines, columns, numbers, the span/match filter, the name dictionary with the reference's
@@ -128,19 +128,20 @@ int ma_bgzf_walk(int fd, const void *mem, uint64_t nbytes, mahip_bgzf_member_t *
 	return MAHIP_BGZF_OK;
 }
 
-/* ---- plain gzip: the header and the trailer of the FIRST member (RFC 1952); whether it is the only one the device finds out (include/mahip.h).
- * returns MAHIP_GZIP_OK (*hdr_len = where the deflate stream starts; the trailer's CRC32 and ISIZE) or MAHIP_GZIP_BAD_HEADER; -1 on a read error */
-int ma_gzip_head(int fd, const void *mem, uint64_t nbytes, uint64_t *hdr_len, uint32_t *crc, uint32_t *isize)
+/* ---- plain gzip: a member's header and trailer (RFC 1952) at any offset of the file; which offsets begin a member the device finds out (include/mahip.h).
+ * ma_gzip_head_at: the header at byte `off`: MAHIP_GZIP_OK (*hdr_len = its length: the deflate stream starts at off + *hdr_len, and at least a trailer's 8 bytes
+ * follow) or MAHIP_GZIP_BAD_HEADER; -1 on a read error */
+int ma_gzip_head_at(int fd, const void *mem, uint64_t nbytes, uint64_t off, uint64_t *hdr_len)
 {
 	bg_src_t src;
 	unsigned char h[12], b[8];
-	uint64_t p = 10;
+	uint64_t p = off + 10;
 	int k;
 	memset(&src, 0, sizeof(src));
 	src.fd = fd; src.mem = (const unsigned char*)mem; src.n = nbytes;
-	*hdr_len = 0; *crc = *isize = 0;
-	if (nbytes < 10 + 8) return MAHIP_GZIP_BAD_HEADER;
-	if (bg_get(&src, 0, 10, h) != 0) return -1;
+	*hdr_len = 0;
+	if (off > nbytes || nbytes - off < 10 + 8) return MAHIP_GZIP_BAD_HEADER;
+	if (bg_get(&src, off, 10, h) != 0) return -1;
 	if (h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xe0)) return MAHIP_GZIP_BAD_HEADER; /* CM 8; FLG bits 5..7 are reserved */
 	if (h[3] & 4) { /* FEXTRA: skipped, unless a `BC` subfield says that this is BGZF's business */
 		uint64_t x, xend;
@@ -169,9 +170,30 @@ int ma_gzip_head(int fd, const void *mem, uint64_t nbytes, uint64_t *hdr_len, ui
 		}
 	if (h[3] & 2) p += 2; /* FHCRC */
 	if (p > nbytes || nbytes - p < 8) return MAHIP_GZIP_BAD_HEADER;
-	if (bg_get(&src, nbytes - 8, 8, b) != 0) return -1;
-	*hdr_len = p; *crc = bg_le32(b); *isize = bg_le32(b + 4);
+	*hdr_len = p - off;
 	return MAHIP_GZIP_OK;
+}
+
+/* the trailer whose 8 bytes start at byte `off`: 0, or -1 on a read error (or when it does not lie in the file) */
+int ma_gzip_trailer_at(int fd, const void *mem, uint64_t nbytes, uint64_t off, uint32_t *crc, uint32_t *isize)
+{
+	bg_src_t src;
+	unsigned char b[8];
+	memset(&src, 0, sizeof(src));
+	src.fd = fd; src.mem = (const unsigned char*)mem; src.n = nbytes;
+	*crc = *isize = 0;
+	if (off > nbytes || nbytes - off < 8 || bg_get(&src, off, 8, b) != 0) return -1;
+	*crc = bg_le32(b); *isize = bg_le32(b + 4);
+	return 0;
+}
+
+/* MA_GZIP_CAND_CAP: the capacity of the member scan's candidate list (tests make it small); anything else is the default */
+size_t ma_gzip_cand_cap(void)
+{
+	const char *s = getenv("MA_GZIP_CAND_CAP");
+	long long v = s ? atoll(s) : 0;
+	if (v >= 1 && v <= (1ll << 24)) return (size_t)v;
+	return MAHIP_GZIP_CAND_CAP_DEFAULT;
 }
 
 /* MA_GZIP_CHUNK: bytes of payload per chunk, a power of two in 1024 .. 16 MiB; anything else is the default */
@@ -294,7 +316,7 @@ static int paf_load_ladder(mahip_ctx_t *c, const char *fn, gzFile *stream_fp, in
 			} else {
 				if (mahip_bgzf_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, &bi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
 				if (bi.reason == MAHIP_BGZF_OK) { close(fd); return 0; }
-				if (bi.reason == MAHIP_BGZF_NOT_BGZF) { /* plain gzip: one deflate stream, cut into chunks on the device (include/mahip.h); any reason leaves it to zlib */
+				if (bi.reason == MAHIP_BGZF_NOT_BGZF) { /* plain gzip: deflate streams (one a member; `cat a.gz b.gz` has several), cut into chunks on the device (include/mahip.h); any reason leaves it to zlib */
 					mahip_gzip_info_t gi;
 					if (!ma_gzip_device_enabled()) {
 						memset(&gi, 0, sizeof(gi));
@@ -302,7 +324,7 @@ static int paf_load_ladder(mahip_ctx_t *c, const char *fn, gzFile *stream_fp, in
 						mahip_gzip_note(c, &gi);
 						if (ma_timing_level() >= 1) fprintf(stderr, "[T::gzip] reader=host reason=%d (%s) item=-1 chunks=0 items=0\n", gi.reason, mahip_gzip_reason_name(gi.reason));
 					} else {
-						if (mahip_gzip_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, 0, &gi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
+						if (mahip_gzip_load_fd_members(c, fd, (size_t)st.st_size, MAHIP_BGZF_PAF, 0, &gi) != 0) { close(fd); fprintf(stderr, "[W::%s] device-side parse not possible (%s); using the host reader\n", __func__, mahip_strerror()); mahip_paf_release(c); return -2; }
 						if (gi.reason == MAHIP_GZIP_OK) { close(fd); return 0; }
 					}
 				}

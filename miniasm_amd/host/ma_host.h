@@ -122,6 +122,7 @@ size_t ma_fastx_piece(void);    /* MA_FASTX_PIECE or 16 MiB, clamped to [256, 1 
 int ma_gpu_parse_enabled(void); /* 0 when MA_HOST_PARSE=1 */
 int ma_gzip_device_enabled(void); /* MA_GZIP_DEVICE: plain gzip files are cut into chunks and inflated on the device (ingest_gpu.c) */
 size_t ma_gzip_chunk(void);       /* MA_GZIP_CHUNK or the default */
+size_t ma_gzip_cand_cap(void);    /* MA_GZIP_CAND_CAP or the default: the member scan's candidate list (include/mahip.h) */
 int ma_bgzf_enabled(void);      /* 0 when MA_BGZF_HOST=1: bgzip'ed input is inflated by zlib on the host */
 /* the member chain of a BGZF file (fd >= 0) or image (mem) -> the block table of include/mahip.h; returns a MAHIP_BGZF_* reason, -1 on a read error */
 int ma_bgzf_walk(int fd, const void *mem, uint64_t nbytes, mahip_bgzf_member_t **tab, uint64_t *n_members, uint64_t *n_empty, uint64_t *text_bytes, int64_t *bad);

@@ -500,7 +500,7 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 	if (fstat(fd, &st) != 0 || !S_ISREG(st.st_mode) || st.st_size <= 0 || pread(fd, magic, 2, 0) < 1) { close(fd); return 0; }
 	t0 = sys_realtime();
 	mahip_mem_trim(c, 0); /* what the passes before left idle in the pool: the text may need it */
-	if (magic[0] == 0x1f && magic[1] == 0x8b) { /* compressed: bgzip's blocks are inflated on the device into the same text buffer (include/mahip.h); anything else is NOT_PLAIN, as ever */
+	if (magic[0] == 0x1f && magic[1] == 0x8b) { /* compressed: bgzip's blocks are inflated on the device into the same text buffer (include/mahip.h), plain gzip too under MA_GZIP_DEVICE=1; anything else is NOT_PLAIN, as ever */
 		mahip_bgzf_info_t bi;
 		if (!ma_bgzf_enabled()) {
 			memset(&bi, 0, sizeof(bi));
@@ -510,9 +510,17 @@ static int ug_seq_device(mahip_ctx_t *c, const sdict_t *d, const ma_sub_t *sub, 
 			return 0;
 		}
 		rc = mahip_bgzf_load_fd(c, fd, (size_t)st.st_size, MAHIP_BGZF_FASTX, &bi);
-		close(fd);
-		if (rc != 0) { mahip_fastx_release(c); return -1; }
-		if (bi.reason != MAHIP_BGZF_OK) return 0;
+		if (rc != 0) { close(fd); mahip_fastx_release(c); return -1; }
+		if (bi.reason == MAHIP_BGZF_NOT_BGZF && ma_gzip_device_enabled()) { /* plain gzip, one member or several: the chunked inflater (MA_GZIP_DEVICE=1); any refusal is NOT_PLAIN */
+			mahip_gzip_info_t gi;
+			rc = mahip_gzip_load_fd_members(c, fd, (size_t)st.st_size, MAHIP_BGZF_FASTX, 0, &gi);
+			close(fd);
+			if (rc != 0) { mahip_fastx_release(c); return -1; }
+			if (gi.reason != MAHIP_GZIP_OK) return 0;
+		} else {
+			close(fd);
+			if (bi.reason != MAHIP_BGZF_OK) return 0;
+		}
 	} else {
 		rc = mahip_fastx_load_fd(c, fd, (size_t)st.st_size);
 		close(fd);

@@ -194,7 +194,7 @@ def write_reads(rng, paf, path):
         open(path, "wb").write(data)
 
 
-def write_gzip(rng, data, path):
+def gzip_member(rng, data):
     """`data` as ONE plain gzip member the way no single tool writes it: random level, memLevel, strategy, sync / full flush points and header fields"""
     flg = rng.choice([0, 0, 8, 1, 2, 4, 16, 8 | 16, 2 | 4 | 8 | 16])
     h = b"\x1f\x8b\x08" + bytes([flg]) + struct.pack("<I", rng.choice([0, 1700000000])) + b"\x00\x03"
@@ -213,7 +213,54 @@ def write_gzip(rng, data, path):
         body += co.compress(data[last:c]) + co.flush(rng.choice([zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH]))
         last = c
     body += co.compress(data[last:]) + co.flush()
-    open(path, "wb").write(h + body + struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff))
+    return h + body + struct.pack("<II", zlib.crc32(data), len(data) & 0xffffffff)
+
+
+def write_gzip(rng, data, path):
+    open(path, "wb").write(gzip_member(rng, data))
+
+
+_members = None
+
+
+def members_image(rng, data):
+    """`data` as concatenated gzip members (`cat a.gz b.gz ...`): a random member count, cuts at any byte (equal cuts: a member without text), every member with
+    its own random header and deflate knobs"""
+    n = rng.choice([1, 2, 2, 3, 5, 8, 30, 70])
+    cuts = sorted(rng.randrange(len(data) + 1) for _ in range(n - 1))
+    if rng.random() < 0.2 and cuts:
+        cuts.append(cuts[-1])  # an empty member for sure
+        cuts.sort()
+    edges = [0] + cuts + [len(data)]
+    return b"".join(gzip_member(rng, data[a:b]) for a, b in zip(edges, edges[1:])), len(edges) - 1
+
+
+def members_case(rng, image, data, n_members, tally):
+    """the stage API of the CPU build on the image, and on the image with one flipped bit: EITHER the reason is OK and the text is the text, OR there is no text"""
+    global _members
+    if _members is None:
+        os.environ["MA_EMU_BUILD"] = os.path.basename(os.path.dirname(EMU))
+        sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import emu_plugin  # noqa: F401  (points the ctypes harness at the CPU build)
+        import miniasm_amd as ma
+        _members = ma.Ctx(0)
+    ctx = _members
+    chunk = 1024 << rng.randint(0, 4)
+    text, info = ctx.gzip_inflate(image, chunk, members=True)
+    mi = ctx.gzip_members_info()
+    key = "stage: " + info["reason"]
+    tally[key] = tally.get(key, 0) + 1
+    assert (text is None) == (info["reason"] != "OK"), info
+    assert text is None or (text == data and mi["n_members"] == n_members), ("a wrong text", info, mi)
+    assert info["reason"] in ("OK", "SYNC_MISMATCH", "NO_SYNC"), ("a valid image is refused for another reason than a false block start or the span", info, mi)
+    byte, bit = rng.randrange(len(image)), rng.randrange(8)
+    flipped = image[:byte] + bytes([image[byte] ^ (1 << bit)]) + image[byte + 1:]
+    text, info = ctx.gzip_inflate(flipped, chunk, members=True)
+    key = "stage, one flipped bit: " + info["reason"]
+    tally[key] = tally.get(key, 0) + 1
+    assert (text is None) == (info["reason"] != "OK"), info
+    assert text is None or text == data, ("a wrong text from a damaged image", byte, bit, info)
 
 
 _stream = None
@@ -274,6 +321,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stream", action="store_true", help="the streamed ingest: the text cut at random line borders through mahip_paf_stream_* (against the whole parse, the host reader, the reference library), and the command line under MA_INGEST_STREAM=1 with a random MA_INGEST_PIECE")
     ap.add_argument("--gzip", action="store_true", help="every case also runs on its PAF text as a plain gzip file (random level, memLevel, strategy, flush points, header fields) with MA_GZIP_DEVICE=1 and a random MA_GZIP_CHUNK: the chunked device inflater; the road taken is tallied by reason")
+    ap.add_argument("--gz-members", action="store_true", help="every case also runs on its PAF text as CONCATENATED gzip members (random member count and cut points, every member with its own random header and deflate knobs) with MA_GZIP_DEVICE=1 and a random MA_GZIP_CHUNK, against the reference on the same file; and the image, whole and with one flipped bit, goes through the stage API: OK and the right text, or a refusal and no text")
     ap.add_argument("--seq", action="store_true", help="unitig sequences: every case also gets a random reads file and runs with -f (ma_ug_seq; the device byte gather)")
     ap.add_argument("--dumps", action="store_true", help="every case asks for -p paf / -p sg / -p bed / -p ug at a random -S and runs with the device text writer forced (MA_TEXT_DEVICE=1, random MA_TEXT_SLAB)")
     ap.add_argument("--text", action="store_true", help="damage the PAF text (reader / dictionary semantics) instead of varying the options")
@@ -340,6 +388,20 @@ def main():
         if a.gzip:
             write_gzip(rng, open(paf, "rb").read(), paf + ".gz")
             runs.append(("emu gzip", {"MA_GZIP_DEVICE": "1", "MA_GZIP_CHUNK": str(1024 << rng.randint(0, 6)), "FILE": paf + ".gz"}))
+        if a.gz_members:
+            data = open(paf, "rb").read()
+            image, n_members = members_image(rng, data)
+            open(paf + ".cat.gz", "wb").write(image)
+            runs.append(("emu gzip members", {"MA_GZIP_DEVICE": "1", "MA_GZIP_CHUNK": str(1024 << rng.randint(0, 6)), "FILE": paf + ".cat.gz"}))
+            if len(image) <= (1 << 20):
+                try:
+                    members_case(rng, image, data, n_members, readers)
+                except AssertionError as e:
+                    bad += 1
+                    print("case %d MISMATCH [gzip members, stage]: pafgen %s: %s" % (k, " ".join(gen), str(e)[:400]))
+                    if a.keep:
+                        os.makedirs(a.keep, exist_ok=True)
+                        open(os.path.join(a.keep, "case%d.cat.gz" % k), "wb").write(image)
         if a.stream:
             runs.append(("emu stream", {"MA_INGEST_STREAM": "1", "MA_INGEST_PIECE": str(max(256, os.path.getsize(paf) // rng.choice([1, 2, 7, 40, 200])))}))
         if a.seq:  # the same case with the host reader of the reads file: both must equal the reference
@@ -363,6 +425,9 @@ def main():
                 if ln.startswith("[T::gzip]"):
                     mm = re.search(r"reader=(\w+) reason=\d+ \(([^)]*)\)", ln)
                     key = "gzip: %s (%s)" % (mm.group(1), mm.group(2))
+                    readers[key] = readers.get(key, 0) + 1
+                if ln.startswith("[T::gzip_members]"):
+                    key = "gzip members: %s" % ("one" if " members=1 " in ln else "several")
                     readers[key] = readers.get(key, 0) + 1
                 if ln.startswith("[T::text]"):
                     key = "text: " + " ".join(ln.split()[1:3]).rstrip(":")
@@ -390,7 +455,7 @@ def main():
         if (k + 1) % 20 == 0:
             print("%d cases, %d mismatches" % (k + 1, bad), flush=True)
     print("tie paths taken:", paths)
-    if a.seq or a.gzip or a.dumps:
+    if a.seq or a.gzip or a.gz_members or a.dumps:
         print("readers taken:", readers)
     if a.stream:
         print("pieces handed to mahip_paf_stream_piece_mem:", n_pieces_cut)
